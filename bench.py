@@ -10,17 +10,23 @@ non-default stream; with N > 1 the step also all-gathers every rank's int32
 scores (RCCL over xGMI), the exchange step of SURVEY.md §8(e).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--pairs P]
+                  [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the last timed step's
+outputs when --dump-outputs is given, and prints the result line.  Everything
+else the benchmark measures or checks runs under --full.
 
 Multi-GPU: one process per GPU.  Under torchrun (WORLD_SIZE set) the ranks come
 from the environment; `--gpus N` without WORLD_SIZE starts N ranks itself
 (torch.distributed.run, 127.0.0.1) before any GPU call.  Timing is bracketed by
 a barrier + synchronize on both sides, the max over ranks is reported.
 
-After the timed steps every rank checks its shard's device outputs against the
+--full: after the timed steps every rank checks its shard's device outputs against the
 CPU oracle (oracle/, the reference's kernels restated in C), bit-exactly for
 integer outputs, rtol 1e-5 for PairHMM, and rank 0 checks the gathered scores;
 the line carries "parity".  At N = 1 the same oracle run is timed as the CPU
-baseline (the box's cores), beside a 1-core sample.
+baseline (the box's cores), beside a 1-core sample, and the host-staged
+(PCIe-inclusive) entry points are timed as "end_to_end".
 """
 import argparse
 import dataclasses
@@ -137,7 +143,8 @@ def parse():
     ap.add_argument("--workload", default="sw_local", choices=sorted(WORKLOADS))
     ap.add_argument("--cpu-seconds", type=float, default=8.0, help="1-core CPU baseline sample budget")
     ap.add_argument("--parity-pairs", type=int, default=2_000_000,
-                    help="per rank: check at most this many pairs of the shard against the oracle (0 = none)")
+                    help="--full, per rank: check at most this many pairs of the shard against the oracle "
+                         "(0 = none)")
     ap.add_argument("--streams", type=int, default=None,
                     help="GASAL workloads: engines (gasal_gpu_storage) on their own streams, steps "
                          "issued round-robin as the reference's host program drives gasal_aln_async "
@@ -145,8 +152,15 @@ def parse():
                          "2 for the traceback and WITH_START workloads (a step's walk or reverse-pass prep runs "
                          "beside the next step's DP), 3 for config 3 (profiles/r04/p_nw_tb_s*.json: 2 -> 3,860, "
                          "3 -> 4,189, 4 -> 3,727 GCUPS in one session), else 1")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline timings")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the host-staged (PCIe-inclusive) timing")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the parity "
+                         "check against the CPU oracle, the CPU baseline timings and the host-staged "
+                         "(PCIe-inclusive) timings (see --parity-pairs, --no-cpu, --no-e2e)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32 or float64, at "
+                         "most 64 MB in all: a fixed seeded sample of the pairs when the outputs are larger)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline timings")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip the host-staged (PCIe-inclusive) timing")
     ap.add_argument("--no-gather", action="store_true", help="N > 1: leave out the all-gather of scores")
     ap.add_argument("--force-int32", action="store_true",
                     help="probe: every block on the int32 kernels (GASALX_PACKED16=0), as pairs outside the "
@@ -163,7 +177,11 @@ def parse():
                     help="boundary workload: pairs per host batch (test_prog's STREAM_BATCH_SIZE = 5,000)")
     ap.add_argument("--dry-run", action="store_true",
                     help="print each rank's shard of the global batch as a JSON line and exit (no GPU call)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:
+        # a plain run: nothing beyond the timed steps (and the dump of their outputs)
+        args.no_cpu, args.no_e2e, args.parity_pairs = True, True, 0
+    return args
 
 
 # ----------------------------------------------------------------- launch ---
@@ -431,6 +449,55 @@ def compare_align(g, o, fields, batch=None, cigar=False):
     return mism, extra
 
 
+# ------------------------------------------------------------------ dump ----
+DUMP_BYTES = 64 * 1000 * 1000 - 65536   # --dump-outputs: 64 MB in all, less room for the .npy headers
+DUMP_SEED = 0x5EEDD0
+
+
+def dump_outputs(path, res, q_offsets=None, q_lens=None, suffix=""):
+    """Write a step's host results as path/<name><suffix>.npy: integer outputs as float64
+    (exact), fp32 results as float32.  The CIGAR bytes go out as one row per pair
+    (pairs x the widest slot): the first min(n_ops, slot) bytes of the pair's pad8(ql)
+    slot, zeros after them, and a row of zeros for a pair whose own or whose left
+    neighbour's CIGAR overflows its slot (those bytes depend on the order the pairs are
+    written in, compare_align).  When all of it would exceed DUMP_BYTES a fixed seeded
+    sample of the pairs is written, the same pairs in every array, their indices as
+    sample_index.npy.  Returns {name: shape}."""
+    per_pair = {k: np.asarray(v) for k, v in res.items() if k != "cigar"}
+    n = len(next(iter(per_pair.values())))
+    width = {k: 4 if v.dtype == np.float32 else 8 for k, v in per_pair.items()}
+    row = sum(width.values())
+    slot = None
+    if "cigar" in res:
+        slot = (np.asarray(q_lens).astype(np.int64) + 7) // 8 * 8
+        row += 4 * int(slot.max(initial=0))
+    idx = None
+    if n * row > DUMP_BYTES:
+        keep = max(1, DUMP_BYTES // (row + 8))
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, keep, replace=False))
+    out = {k: (v if idx is None else v[idx]).astype(np.float32 if width[k] == 4 else np.float64)
+           for k, v in per_pair.items()}
+    if idx is not None:
+        out["sample_index"] = idx.astype(np.float64)
+    if slot is not None:
+        nops = np.asarray(res["n_ops"]).astype(np.int64)
+        over = nops > slot
+        ok = ~over
+        ok[1:] &= ~over[:-1]
+        valid = np.where(ok, np.minimum(nops, slot), 0)
+        sel = np.arange(n) if idx is None else idx
+        cols = np.arange(int(slot.max(initial=0)), dtype=np.int64)
+        mask = cols[None, :] < valid[sel][:, None]
+        src = np.asarray(q_offsets).astype(np.int64)[sel][:, None] + cols[None, :]
+        rows = np.zeros(mask.shape, np.float32)
+        rows[mask] = np.asarray(res["cigar"])[src[mask]]
+        out["cigar"] = rows
+    os.makedirs(path, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(path, f"{k}{suffix}.npy"), v)
+    return {k: list(v.shape) for k, v in out.items()}
+
+
 # ------------------------------------------------------------------ e2e -----
 def end_to_end(eng, kind, data, params, cells, reps=5, seed_score=None):
     """PCIe-inclusive rate through the host-buffer entry point (gasalx_align_host /
@@ -578,7 +645,10 @@ def run_cpu_plumbing(args, wl):
     # this workload is the CPU path itself: its baseline is the same timing, stated like every other line's
     out["cpu_baseline"] = {"value": out["value"], "unit": "GCUPS", "cores": 1, "kind": "port",
                            "sample": f"the whole workload ({n} pairs x {args.steps} passes, 1 thread)"}
-    if torch.cuda.is_available():
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, {f: o[f] for f in ("score", "q_end", "t_end")})
+        out["config"]["dumped_outputs_rank0"] = dumped
+    if args.full and torch.cuda.is_available():
         eng = G.Engine(0)
         g = eng.align_host(batch, G.make_params(**pkw), fields=["score", "q_end", "t_end"])
         mism, _ = compare_align(g, o, ("score", "q_end", "t_end"))
@@ -628,9 +698,32 @@ def run_boundary(args, wl):
         runs.append(line)
         dumps[T] = dump
     best = max(runs, key=lambda x: x["gcups"])
+    batch = G.Batch.from_pairs(q, t)
+    params = G.make_params(**wl["params"])
+    mq, mt = int(batch.q_lens.max()), int(batch.t_lens.max())
+    plan = G.describe_plan(params, mq, mt)
+    out = {"metric": METRICS["boundary"], "value": best["gcups"], "unit": "GCUPS", "n_gpus": 1,
+           "steps": len(best["pass_ms"]), "warmup": 1 if args.warmup is None else max(1, args.warmup),
+           "ms_per_step": best["best_ms"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+           "dtype": dtype_label(plan, 2),
+           "data": "the reference's test_prog sample pairs (tests/golden/*_batch.fasta.gz), replicated",
+           "config": {"workload": wl["label"], "pairs": n, "base_pairs": base, "replicas": repl, "cells": cells,
+                      "threads_best": best["threads"], "storages_per_thread": best["storages"],
+                      "batch_pairs": best["batch"], "plan_of_a_batch": plan},
+           "runs": runs,
+           "vs_reference_a100_derived": {"end_to_end_48.6": round(best["gcups"] / 48.6, 2),
+                                         "kernel_window_80": round(best["gcups"] / 80.0, 2),
+                                         "source": "BASELINE.md section 1 (CDP/GASAL2/test_prog/report1.sqlite)"}}
+    if args.dump_outputs:
+        # the last pass of the run the headline figure comes from
+        got = np.fromfile(dumps[best["threads"]], np.int32).reshape(5, n)
+        out["config"]["dumped_outputs_rank0"] = dump_outputs(
+            args.dump_outputs, {f: got[k] for k, f in enumerate(("score", "q_end", "t_end"))})
+    if not args.full:
+        print(json.dumps(out), flush=True)
+        return
     # parity: the oracle over the 20K sample pairs, every replica of every run against it
     O = _oracle(native=not args.no_cpu)
-    batch = G.Batch.from_pairs(q, t)
     t_o = time.perf_counter()
     ref = oracle_align(O, batch, wl["params"], oracle_threads())
     oracle_s = time.perf_counter() - t_o
@@ -648,7 +741,6 @@ def run_boundary(args, wl):
                   np.tile(batch.t_data, repl),
                   (batch.t_offsets[None, :].astype(np.int64) + np.arange(repl)[:, None] * batch.t_bytes)
                   .reshape(-1).astype(np.uint32), np.tile(batch.t_lens, repl))
-    params = G.make_params(**wl["params"])
     eng = G.Engine(0)
     fields = ["score", "q_end", "t_end"]
     eng.align_host(big, params, fields=fields)
@@ -666,7 +758,6 @@ def run_boundary(args, wl):
          "q_end": torch.empty(n, dtype=torch.int32, device=dev), "t_end": torch.empty(n, dtype=torch.int32, device=dev)}
     ptrs = {k: v.data_ptr() for k, v in d.items()}
     stream = torch.cuda.Stream(dev)
-    mq, mt = int(big.q_lens.max()), int(big.t_lens.max())
     for _ in range(3):
         eng.align_device_ptrs(params, ptrs, big.q_bytes, big.t_bytes, n, mq, mt, stream.cuda_stream)
     torch.cuda.synchronize(dev)
@@ -679,20 +770,8 @@ def run_boundary(args, wl):
     dev_ms = float(np.mean([a.elapsed_time(b) for a, b in evs]))
     dev_bad = sum(int(np.count_nonzero(d[k].cpu().numpy().reshape(repl, base) != ref[f][None, :]))
                   for k, f in (("aln_score", "score"), ("q_end", "q_end"), ("t_end", "t_end")))
-    plan = G.describe_plan(params, mq, mt)
     eng.close()
-    out = {"metric": METRICS["boundary"], "value": best["gcups"], "unit": "GCUPS", "n_gpus": 1,
-           "steps": len(best["pass_ms"]), "warmup": 1 if args.warmup is None else max(1, args.warmup),
-           "ms_per_step": best["best_ms"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-           "dtype": dtype_label(plan, 2),
-           "data": "the reference's test_prog sample pairs (tests/golden/*_batch.fasta.gz), replicated",
-           "config": {"workload": wl["label"], "pairs": n, "base_pairs": base, "replicas": repl, "cells": cells,
-                      "threads_best": best["threads"], "storages_per_thread": best["storages"],
-                      "batch_pairs": best["batch"], "plan_of_a_batch": G.describe_plan(params, mq, mt)},
-           "runs": runs,
-           "vs_reference_a100_derived": {"end_to_end_48.6": round(best["gcups"] / 48.6, 2),
-                                         "kernel_window_80": round(best["gcups"] / 80.0, 2),
-                                         "source": "BASELINE.md section 1 (CDP/GASAL2/test_prog/report1.sqlite)"},
+    out.update({
            "flat_host_entry": {"value": round(cells / min(th) / 1e9, 2), "ms": round(min(th) * 1e3, 3),
                                "mismatches": host_bad,
                                "path": "gasalx_align_host on the same pairs (pageable arrays; chunks on two streams)"},
@@ -701,7 +780,7 @@ def run_boundary(args, wl):
                                "path": "gasalx_align_device on the same pairs in HBM (HIP events around the call)"},
            "parity": {"pairs_checked": n * len(dumps), "mismatches": sum(mism.values()), "by_run": mism,
                       "tolerance": "bit-exact", "against": "oracle/ over the 20K sample pairs; every replica of "
-                                                          "every run's last pass compared with it"}}
+                                                          "every run's last pass compared with it"}})
     if not args.no_cpu:
         out["cpu_baseline"] = {"value": round(cells / repl / oracle_s / 1e9, 4), "unit": "GCUPS",
                                "cores": oracle_threads(), "kind": "port",
@@ -963,7 +1042,15 @@ def main():
         # is its share of the wall time
         kern_ms = elapsed * 1e3 / args.steps
 
-    # ---- parity: this rank's shard against the oracle (the CPU baseline at N = 1) ----
+    dumped = None
+    if args.dump_outputs:
+        # what the last timed step left in its set's output buffers
+        k_last = (args.warmup + args.steps - 1) % n_sets
+        last = results(k_last) if kind not in (5, 6) else results()
+        dumped = dump_outputs(args.dump_outputs, last, q_offsets=getattr(data, "q_offsets", None),
+                              q_lens=getattr(data, "q_lens", None), suffix=f"_rank{rank}" if world > 1 else "")
+
+    # ---- --full, parity: this rank's shard against the oracle (the CPU baseline at N = 1) ----
     parity, cpu = None, None
     O = _oracle(native=world == 1 and not args.no_cpu) if (args.parity_pairs > 0 or (world == 1 and not args.no_cpu)) \
         else None
@@ -1169,7 +1256,8 @@ def main():
                        **({"streams": f"{n_sets} engines on {n_sets} streams, steps round-robin "
                                       f"(gasal_aln_async per storage, test_prog.cpp's NB_STREAMS)"}
                           if n_sets > 1 else {}),
-                       "synth_s_rank0": round(synth_s, 2)},
+                       "synth_s_rank0": round(synth_s, 2),
+                       **({"dumped_outputs_rank0": dumped} if dumped is not None else {})},
             "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic,
                          "bytes_per_pair": wl["bytes"], "kernel_ms": round(kern_ms, 4),

@@ -7,7 +7,7 @@ ROOT="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 cd $ROOT
 O=$ROOT/gpurun_out/${REPRO_TAG:-repro}; mkdir -p $O
 for w in ${WORKLOADS:-sw_local nw_tb semi pairhmm sw_local_300 sw_local_start sw_local_tb semi_start semi_banded nvbio_gotoh nvbio_banded ksw nw_score cpu_plumbing}; do
-  timeout -k 10 400 python3 bench.py --workload $w > $O/bench_$w.json 2> $O/bench_$w.err
+  timeout -k 10 400 python3 bench.py --full --workload $w > $O/bench_$w.json 2> $O/bench_$w.err
   rc=$?
   python3 - "$O/bench_$w.json" "$w" "$rc" <<'PY'
 import json, sys

@@ -41,29 +41,29 @@ step() {  # step NAME SECONDS CMD...
 }
 if has bench; then
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-step bench_default 600 python bench.py
-step bench_sw_local_start 600 python bench.py --workload sw_local_start --cpu-seconds 8
-step bench_sw_local_start_s1 600 python bench.py --workload sw_local_start --streams 1 --no-cpu
-step bench_sw_local_tb 600 python bench.py --workload sw_local_tb --cpu-seconds 8
-step bench_sw_local_300 600 python bench.py --workload sw_local_300 --no-cpu
-step bench_sw_local_match2 600 python bench.py --workload sw_local --scores 2,4,6,1 --no-cpu
-step bench_nw_tb 600 python bench.py --workload nw_tb --cpu-seconds 8
-step bench_nw_tb_s1 600 python bench.py --workload nw_tb --streams 1 --no-cpu
-step bench_nw_score 600 python bench.py --workload nw_score --no-cpu
-step bench_semi 600 python bench.py --workload semi --cpu-seconds 8
-step bench_semi_start 600 python bench.py --workload semi_start --no-cpu
-step bench_semi_banded 600 python bench.py --workload semi_banded --no-cpu
-step bench_pairhmm 600 python bench.py --workload pairhmm --cpu-seconds 8
-step bench_nvbio_gotoh 600 python bench.py --workload nvbio_gotoh --no-cpu
-step bench_nvbio_banded 600 python bench.py --workload nvbio_banded --no-cpu
-step bench_ksw 600 python bench.py --workload ksw --no-cpu
-step bench_boundary 600 python bench.py --workload boundary
+step bench_default 600 python bench.py --full
+step bench_sw_local_start 600 python bench.py --full --workload sw_local_start --cpu-seconds 8
+step bench_sw_local_start_s1 600 python bench.py --full --workload sw_local_start --streams 1 --no-cpu
+step bench_sw_local_tb 600 python bench.py --full --workload sw_local_tb --cpu-seconds 8
+step bench_sw_local_300 600 python bench.py --full --workload sw_local_300 --no-cpu
+step bench_sw_local_match2 600 python bench.py --full --workload sw_local --scores 2,4,6,1 --no-cpu
+step bench_nw_tb 600 python bench.py --full --workload nw_tb --cpu-seconds 8
+step bench_nw_tb_s1 600 python bench.py --full --workload nw_tb --streams 1 --no-cpu
+step bench_nw_score 600 python bench.py --full --workload nw_score --no-cpu
+step bench_semi 600 python bench.py --full --workload semi --cpu-seconds 8
+step bench_semi_start 600 python bench.py --full --workload semi_start --no-cpu
+step bench_semi_banded 600 python bench.py --full --workload semi_banded --no-cpu
+step bench_pairhmm 600 python bench.py --full --workload pairhmm --cpu-seconds 8
+step bench_nvbio_gotoh 600 python bench.py --full --workload nvbio_gotoh --no-cpu
+step bench_nvbio_banded 600 python bench.py --full --workload nvbio_banded --no-cpu
+step bench_ksw 600 python bench.py --full --workload ksw --no-cpu
+step bench_boundary 600 python bench.py --full --workload boundary
 fi
 has prof || exit 0
 cd /tmp && export TMPDIR=/tmp
 for w in sw_local pairhmm semi semi_start sw_local_start sw_local_tb nw_tb; do
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$w -o run -- \
-    python3 $ROOT/bench.py --workload $w --no-cpu --no-e2e --parity-pairs 1000 > $O/prof_$w.json 2> $O/prof_$w.err
+    python3 $ROOT/bench.py --full --workload $w --no-cpu --no-e2e --parity-pairs 1000 > $O/prof_$w.json 2> $O/prof_$w.err
   rc=$?; echo "[prof $w] rc=$rc"; if fatal $rc; then exit $rc; fi
 done
 exit 0

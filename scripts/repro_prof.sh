@@ -8,7 +8,7 @@ O=$ROOT/gpurun_out/${REPRO_TAG:-repro}; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 for w in sw_local nw_tb semi pairhmm sw_local_300 sw_local_start sw_local_tb semi_start semi_banded nvbio_gotoh nvbio_banded ksw nw_score; do
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$w -o run -- \
-    python3 $ROOT/bench.py --no-cpu --no-e2e --workload $w --steps 5 --warmup 1 --parity-pairs 20000 > $O/prof_$w.json 2> $O/prof_$w.err
+    python3 $ROOT/bench.py --full --no-cpu --no-e2e --workload $w --steps 5 --warmup 1 --parity-pairs 20000 > $O/prof_$w.json 2> $O/prof_$w.err
   rc=$?; echo "prof $w rc=$rc"
   case $rc in 0) ;; *) tail -3 $O/prof_$w.err; exit $rc;; esac
 done

@@ -276,7 +276,7 @@ def test_bench_ranks_gloo_one_gpu(workload, pairs, checked, world, warm):
     # exchange buffers; pairhmm gathers fp32 results (config 5, "1 -> 8 GPUs"); semi at world 4.
     # warm None: the default time-based warmup, whose stop decision the ranks take together
     # (each rank's own clock could leave the ranks in different collectives)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--dist-backend", "gloo",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(world), "--dist-backend", "gloo",
            "--workload", workload, "--pairs", str(pairs), "--steps", "3", "--no-e2e"]
     cmd += ["--warmup", warm] if warm else ["--warmup-seconds", "0.3"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
