@@ -2,6 +2,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <cerrno>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -655,14 +656,25 @@ static int64_t nv_score_mag(const gasalx_nv_aligner *al) {
 // nvbio traceback workspace per call (the engine's: flags of every cell, one DP row per pair) and
 // the chunk budget the device entry points split a batch by
 static constexpr uint64_t kNvTbBudget = 4ull << 30;
+// GASALX_NV_TB_BUDGET (bytes) replaces it for tests that force several chunks; read on every
+// call, and unset, empty, zero or unparsable leave the 4 GiB
+static uint64_t nv_tb_budget() {
+    const char *e = std::getenv("GASALX_NV_TB_BUDGET");
+    if (!e || !*e) return kNvTbBudget;
+    for (const char *c = e; *c; c++)
+        if (*c < '0' || *c > '9') return kNvTbBudget;
+    errno = 0;
+    const unsigned long long v = std::strtoull(e, nullptr, 10);
+    return (errno || !v) ? kNvTbBudget : (uint64_t)v;
+}
 uint64_t gasalx_nv_traceback_workspace(uint32_t max_p, uint32_t max_t, uint32_t n) {
     const uint64_t per = (uint64_t)((max_p + 7) / 8) * 8 * max_t + (uint64_t)max_t * 8;
-    const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(n, kNvTbBudget / std::max<uint64_t>(per, 1)));
+    const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(n, nv_tb_budget() / std::max<uint64_t>(per, 1)));
     return per * chunk + 128;
 }
 uint64_t gasalx_nv_banded_traceback_workspace(uint32_t max_p, uint32_t band, uint32_t n) {
     const uint64_t per = (uint64_t)max_p * ((band + 3) / 4) * 4;
-    const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(n, kNvTbBudget / std::max<uint64_t>(per, 1)));
+    const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(n, nv_tb_budget() / std::max<uint64_t>(per, 1)));
     return per * chunk + 64;
 }
 
@@ -697,9 +709,9 @@ int gasalx_nv_traceback_device(gasalx_engine *eng, const gasalx_nv_aligner *al, 
     int rc = nv_tb_checks(al, max_p, max_t, ops_stride);
     if (rc) return rc;
     // the batch runs in chunks whose workspace (flags of every cell + one row per pair) stays
-    // within kNvTbBudget (1 M 150 x 182 pairs would otherwise take 28 GB of HBM)
+    // within nv_tb_budget() (1 M 150 x 182 pairs would otherwise take 28 GB of HBM)
     const uint64_t per = gasalx_nv_traceback_workspace(max_p, max_t, 1);
-    const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n, kNvTbBudget / per));
+    const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n, nv_tb_budget() / per));
     CK(eng->nv_dir.reserve((size_t)((max_p + 7) / 8) * 8 * max_t * chunk + 64));
     CK(eng->nv_row.reserve((size_t)max_t * chunk * 8 + 64));
     for (uint32_t s = 0; s < n; s += chunk) {
@@ -787,7 +799,7 @@ int gasalx_nv_banded_traceback_device(gasalx_engine *eng, const gasalx_nv_aligne
     int rc = nv_btb_checks(al, band, max_p, ops_stride);
     if (rc) return rc;
     const uint64_t per = gasalx_nv_banded_traceback_workspace(max_p, band, 1);
-    const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n, kNvTbBudget / per));
+    const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n, nv_tb_budget() / per));
     CK(eng->nv_dir.reserve((size_t)max_p * ((band + 3) / 4) * 4 * chunk + 64));
     for (uint32_t s = 0; s < n; s += chunk) {
         const uint32_t m = std::min(chunk, n - s);

@@ -636,6 +636,25 @@ def nv_describe_plan(aligner: "NvAligner", max_p: int, max_t: int, per_pair_text
     return buf.value.decode()
 
 
+def _u64_call(name: str, *args) -> int:
+    f = getattr(lib(), name)
+    f.restype = ctypes.c_uint64
+    f.argtypes = [ctypes.c_uint32] * len(args)
+    return int(f(*args))
+
+
+def nv_traceback_workspace(max_p: int, max_t: int, n: int) -> int:
+    """Bytes of engine workspace a full-DP traceback call of n pairs takes (gasalx_nv_traceback_workspace);
+    the device entry point runs chunks of budget / nv_traceback_workspace(max_p, max_t, 1) pairs, the
+    budget 4 GiB or GASALX_NV_TB_BUDGET bytes."""
+    return _u64_call("gasalx_nv_traceback_workspace", max_p, max_t, n)
+
+
+def nv_banded_traceback_workspace(max_p: int, band: int, n: int) -> int:
+    """As nv_traceback_workspace, for the banded traceback (gasalx_nv_banded_traceback_workspace)."""
+    return _u64_call("gasalx_nv_banded_traceback_workspace", max_p, band, n)
+
+
 @dataclass
 class HmmData:
     """PairHMM pairs in the reference's input terms: reads with base / insertion /

@@ -297,7 +297,9 @@ int gasalx_nv_banded_score_host(gasalx_engine *eng, const gasalx_nv_aligner *ali
  * (max pattern + max text + 2) * max |score| <= 32767, and pattern x text <= 16 M cells.
  * Workspace: pad8(pattern) x text bytes + 8 bytes per text symbol per pair, held by the engine; a
  * batch runs in chunks of at most 4 GB of it (gasalx_nv_traceback_workspace gives the bytes a
- * call reserves).  Calls that share an engine must be serialised (one workspace per engine). */
+ * call reserves; the environment variable GASALX_NV_TB_BUDGET, in bytes, replaces the 4 GB for
+ * both tracebacks: a test knob).  Calls that share an engine must be serialised (one workspace
+ * per engine). */
 uint64_t gasalx_nv_traceback_workspace(uint32_t max_pattern_len, uint32_t max_text_len, uint32_t n_pairs);
 int gasalx_nv_traceback_device(gasalx_engine *eng, const gasalx_nv_aligner *aligner, uint32_t n_pairs,
                                const gasalx_nv_strings *dev_patterns, const gasalx_nv_strings *dev_texts,

@@ -17,7 +17,10 @@
  *   int16 scores)                                           NvB/sw-benchmark/sw-benchmark.cu:100-215
  * Every scheduler maps to the same MI355X kernel (nvbio.hpp: lane groups per pattern,
  * text in LDS; banded: nvbanded.hpp, one pair per thread with the band in registers);
- * there is no temporary storage, so max_temp_storage() is 0.  The TextBlockingTag /
+ * the scoring classes take no temporary storage, so their max_temp_storage() is 0.  The
+ * traceback classes report the engine's own workspace there (gasalx_nv_*traceback_workspace:
+ * the flags of every cell, in chunks of at most 4 GiB); enact() does not use the caller's
+ * temp buffer.  The TextBlockingTag /
  * PatternBlockingTag score semantics are provided (both give the same scores), full and
  * banded.  Traceback: BatchedAlignmentTraceback<CHECKPOINTS, stream_type> (full DP) and
  * BatchedBandedAlignmentTraceback<BAND_LEN, CHECKPOINTS, stream_type> for the edit-distance,

@@ -165,3 +165,67 @@ def test_reference_error_helpers_compile(tmp_path):
                    "          return CudaCheckKernelLaunch(); }\n")
     subprocess.run(["/opt/rocm/bin/hipcc", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-c", str(src), "-o",
                     str(tmp_path / "caller.o")], check=True, capture_output=True)
+
+
+# ---- nvbio traceback workspace and its chunk budget (gasalx_nv_*traceback_workspace) ----
+NV_TB_DEFAULT_BUDGET = 4 << 30
+
+
+def _nv_tb_expected(max_p, max_t, n, budget=NV_TB_DEFAULT_BUDGET):
+    # gasalx.h: pad8(pattern) x text flag bytes + 8 bytes per text symbol per pair, chunks within the budget
+    per = (max_p + 7) // 8 * 8 * max_t + 8 * max_t
+    return per * max(1, min(n, budget // max(per, 1))) + 128
+
+
+def _nv_btb_expected(max_p, band, n, budget=NV_TB_DEFAULT_BUDGET):
+    # gasalx.h: max pattern x pad4(band) flag bytes per pair
+    per = max_p * ((band + 3) // 4 * 4)
+    return per * max(1, min(n, budget // max(per, 1))) + 64
+
+
+NV_TB_SHAPES = [(G.nv_traceback_workspace, _nv_tb_expected, a, b)
+                for a, b in ((150, 182), (1, 1), (70, 96), (65, 7), (1024, 6000), (4000, 4000))] + \
+               [(G.nv_banded_traceback_workspace, _nv_btb_expected, a, b)
+                for a, b in ((150, 7), (160, 16), (1, 2), (1200, 31), (32000, 32))]
+NV_TB_COUNTS = (0, 1, 2, 3, 7, 8, 64, 203, 4097, 150_000, 1_000_000, 2**31, 2**32 - 1)
+
+
+@pytest.mark.parametrize("fn,expected,a,b", NV_TB_SHAPES, ids=lambda v: v.__name__.lstrip("_") if callable(v) else str(v))
+def test_nv_traceback_workspace_default_budget(monkeypatch, fn, expected, a, b):
+    # unset: the 4 GiB budget, the numbers of the documented formula (1 M 150 x 182 pairs: 147,492 per chunk)
+    monkeypatch.delenv("GASALX_NV_TB_BUDGET", raising=False)
+    got = [fn(a, b, n) for n in NV_TB_COUNTS]
+    assert got == [expected(a, b, n) for n in NV_TB_COUNTS]
+    assert got == sorted(got)
+    assert G.nv_traceback_workspace(150, 182, 1_000_000) == 29120 * 147492 + 128
+
+
+@pytest.mark.parametrize("fn,expected,a,b", NV_TB_SHAPES, ids=lambda v: v.__name__.lstrip("_") if callable(v) else str(v))
+def test_nv_traceback_workspace_under_budget(monkeypatch, fn, expected, a, b):
+    # with budget B: non-decreasing in n, at most one pair's workspace past B, and for large n the
+    # chunk of B / per pairs, per the bytes one more pair adds
+    one = expected(a, b, 1)
+    per = expected(a, b, 2, 1 << 62) - one
+    for budget in (1, per - 1, per, per + 1, 7 * per, 7 * per + per - 1, 7 * one, 64 * one, 1 << 20, (1 << 32) + 5,
+                   2**64 - 1):
+        monkeypatch.setenv("GASALX_NV_TB_BUDGET", str(budget))
+        got = [fn(a, b, n) for n in NV_TB_COUNTS]
+        assert got == [expected(a, b, n, budget) for n in NV_TB_COUNTS], budget
+        assert got == sorted(got), budget                            # non-decreasing in n
+        assert all(g <= budget + one for g in got), budget          # never more than one pair past the budget
+        c = max(1, budget // per)
+        if c < 2**32:
+            assert fn(a, b, 2**32 - 1) == fn(a, b, c), budget        # large n: the chunk of budget / per pairs
+
+
+@pytest.mark.parametrize("value", ["", "0", "000", "abc", "12abc", "-1", "+5", "0x1000", "1e9", " ", "4 096",
+                                   "18446744073709551616", "99999999999999999999999999"])
+def test_nv_traceback_budget_unparsable_is_unset(monkeypatch, value):
+    monkeypatch.setenv("GASALX_NV_TB_BUDGET", value)
+    assert G.nv_traceback_workspace(150, 182, 1_000_000) == _nv_tb_expected(150, 182, 1_000_000)
+    assert G.nv_banded_traceback_workspace(1200, 31, 1_000_000) == _nv_btb_expected(1200, 31, 1_000_000)
+    # and a value that parses is taken, read again on every call
+    monkeypatch.setenv("GASALX_NV_TB_BUDGET", "2912000")
+    assert G.nv_traceback_workspace(150, 182, 1_000_000) == 29120 * 100 + 128
+    monkeypatch.delenv("GASALX_NV_TB_BUDGET")
+    assert G.nv_traceback_workspace(150, 182, 1_000_000) == 29120 * 147492 + 128

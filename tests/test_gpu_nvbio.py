@@ -497,3 +497,329 @@ def test_banded_traceback_rejects(engine):
             engine.nv_banded_traceback_host(al, band, P, T)
     with pytest.raises(Exception):
         engine.nv_banded_traceback_host(G.NvAligner(G.NV_GOTOH, G.NV_GLOBAL, 3000, -1, -2, -1), 8, P, T)
+
+
+# ---- the traceback entry points' chunk loops (capi.cpp) and the device-resident entry points ----
+# The device entry points run a batch in chunks of budget / workspace(max lengths, 1) pairs, each
+# chunk a launch on pointers offset by its first pair s (offsets + s, scores + s, sources + 2s,
+# sinks + 2s, ops + s * ops_stride, n_ops + s) over a flag workspace laid out with the chunk's
+# pair count and the batch's maximum lengths.  GASALX_NV_TB_BUDGET = c * workspace(.., 1) makes
+# the chunk exactly c pairs.  Everything is compared bit for bit with the oracle.
+BUDGET = "GASALX_NV_TB_BUDGET"
+TB_N = 203
+TYPES = {"global": G.NV_GLOBAL, "local": G.NV_LOCAL, "semi": G.NV_SEMI_GLOBAL}
+TB_ALIGNERS = {"ed": G.NvAligner(G.NV_ED, 0),
+               "sw": G.NvAligner(G.NV_SW, 0, match=2, mismatch=-1, deletion=-1, insertion=-1),
+               "gotoh": G.NvAligner(G.NV_GOTOH, 0, 2, -1, -2, -1)}
+BTB_ALIGNERS = {"ed": G.NvAligner(G.NV_ED, 0),
+                "sw": G.NvAligner(G.NV_SW, 0, match=2, mismatch=-1, deletion=-2, insertion=-3),
+                "gotoh": G.NvAligner(G.NV_GOTOH, 0, 2, -3, -5, -2)}
+_cache = {}
+
+
+def _cached(key, make):
+    if key not in _cache:
+        _cache[key] = make()
+    return _cache[key]
+
+
+def _lens(S):
+    o = np.asarray(S.offsets, np.int64)
+    return o[1:] - o[:-1]
+
+
+def _chunk_edges(c):
+    firsts = set(range(0, TB_N, c))
+    return firsts, {min(s + c, TB_N) - 1 for s in firsts}
+
+
+def _tb_inputs():
+    """The full-DP set: 203 pairs, patterns 0..70 and texts 0..96 symbols, each text its pattern
+    between flanks with about 5 % edits.  The one longest pattern (#199) and the one longest text
+    (#200) lie in the last chunk of 7 and of 64, so every earlier chunk runs under maxima larger
+    than its own; an empty pattern opens a chunk of 7 (#7), an empty text closes one (#13)."""
+    def make():
+        rng = np.random.default_rng(0xC4A2)
+        fixed_m = {1: 7, 2: 8, 3: 9, 4: 63, 5: 64, 6: 65, 7: 0, 8: 1, 100: 0, 199: 70}
+        pats, texts = [], []
+        for k in range(TB_N):
+            m = fixed_m.get(k, int(rng.integers(1, 66)))
+            p = rng.integers(0, 4, m)
+            a, b = int(rng.integers(0, 13)), int(rng.integers(0, 13))
+            if k == 7:
+                a, b = 5, 6
+            if k == 200:
+                a, b = 13, 96 - 13 - m
+            t = np.concatenate([rng.integers(0, 4, a), p, rng.integers(0, 4, b)])
+            t[rng.random(len(t)) < 0.05] = rng.integers(0, 4)
+            if k in (13, 100):
+                t = t[:0]
+            pats.append(p.astype(np.uint32)); texts.append(t.astype(np.uint32))
+        P = G.PackedSet.pack(pats, bits=4, big_endian=True)
+        T = G.PackedSet.pack(texts, bits=2, big_endian=False)
+        S = G.PackedSet.pack([texts[200]], bits=2, big_endian=False, shared=True)
+        return P, T, S
+    return _cached("tb_inputs", make)
+
+
+def _assert_tb_inputs():
+    P, T, S = _tb_inputs()
+    pl, tl = _lens(P), _lens(T)
+    assert P.n == T.n == TB_N and S.length == 96
+    assert pl.min() == 0 and pl.max() == 70 and tl.min() == 0 and tl.max() == 96
+    assert {0, 7, 8, 9, 63, 64, 65, 70} <= set(pl.tolist())
+    for c in (7, 64):
+        last = (TB_N - 1) // c * c
+        assert int(np.argmax(pl)) >= last and (pl == pl.max()).sum() == 1 and pl[:last].max() < pl.max()
+        assert int(np.argmax(tl)) >= last and (tl == tl.max()).sum() == 1 and tl[:last].max() < tl.max()
+    firsts, lasts = _chunk_edges(7)
+    assert 7 in firsts and pl[7] == 0 and tl[7] > 0
+    assert 13 in lasts and tl[13] == 0 and pl[13] > 0
+    for k in (0, TB_N - 1):
+        assert pl[k] > 0 and tl[k] > 0
+    return int(pl.max()), int(tl.max())
+
+
+def _btb_inputs(band):
+    """The banded set, built as test_banded_traceback_random_pairs builds it: 203 pairs, patterns
+    0..160 (empty ones too), texts a little longer than their pattern or shorter than it (skipped
+    pairs), N in some patterns.  A skipped pair opens a chunk of 7 (#14) and another closes one
+    (#6); the one longest pattern (#199) lies in the last chunk."""
+    def make():
+        rng = np.random.default_rng(0xBA2D + band)
+        fixed_m = {0: 50, 3: 0, 6: 40, 14: 33, 199: 160, TB_N - 1: 77}
+        pats, texts = [], []
+        for k in range(TB_N):
+            m = fixed_m.get(k, int(rng.integers(0, 151)))
+            p = rng.integers(0, 4, m).astype(np.uint32)
+            cut = -2 if k in (6, 14) else 3 if k in (0, TB_N - 1, 199) else int(rng.integers(-2, band + 2))
+            t = np.concatenate([rng.integers(0, 4, int(rng.integers(0, band))), p,
+                                rng.integers(0, 4, band)])[: max(0, m + cut)].copy()
+            t[rng.random(len(t)) < 0.06] = rng.integers(0, 4)
+            if k % 9 == 4 and m:
+                p[int(rng.integers(0, m))] = 4   # N
+            pats.append(p); texts.append(t.astype(np.uint32))
+        P = G.PackedSet.pack(pats, bits=4, big_endian=True)
+        T = G.PackedSet.pack(texts, bits=2, big_endian=False)
+        S = G.PackedSet.pack([texts[199]], bits=2, big_endian=False, shared=True)
+        return P, T, S
+    return _cached(("btb_inputs", band), make)
+
+
+def _assert_btb_inputs(band):
+    P, T, S = _btb_inputs(band)
+    pl, tl = _lens(P), _lens(T)
+    assert P.n == T.n == TB_N
+    assert pl.min() == 0 and pl.max() == 160 and (pl == 160).sum() == 1 and int(np.argmax(pl)) == 199
+    firsts, lasts = _chunk_edges(7)
+    assert 14 in firsts and tl[14] < pl[14]          # skipped pairs at a chunk's two ends
+    assert 6 in lasts and tl[6] < pl[6]
+    assert (tl < pl).sum() >= 4 and (tl >= pl).sum() > TB_N // 2
+    for k in (0, TB_N - 1):
+        assert 0 < pl[k] <= tl[k]
+    return int(pl.max())
+
+
+def _tb_oracle(al, shared):
+    P, T, S = _tb_inputs()
+    return _cached(("tb", al.aligner, al.type, al.match, shared), lambda: O.nv_traceback(al, P, S if shared else T))
+
+
+def _btb_oracle(al, band, shared):
+    P, T, S = _btb_inputs(band)
+    return _cached(("btb", band, al.aligner, al.type, shared),
+                   lambda: O.nv_banded_traceback(al, band, P, S if shared else T))
+
+
+def _same_traceback(g, o, what):
+    """score, source, sink, n_ops and every push of every pair equal."""
+    n = len(o["ops"])
+    assert len(g["ops"]) == n == len(g["score"])
+    for f in ("score", "source", "sink"):
+        bad = np.nonzero(np.asarray(g[f]).reshape(n, -1) != np.asarray(o[f]).reshape(n, -1))[0]
+        assert bad.size == 0, f"{what}: {f} of {np.unique(bad).size} pairs differ, first #{bad[0]}"
+    gn, on = [len(x) for x in g["ops"]], [len(x) for x in o["ops"]]
+    bad = [k for k in range(n) if gn[k] != on[k]]
+    assert not bad, f"{what}: n_ops of {len(bad)} pairs differ, first #{bad[0]}: {gn[bad[0]]} != {on[bad[0]]}"
+    bad = [k for k in range(n) if not np.array_equal(g["ops"][k], o["ops"][k])]
+    assert not bad, f"{what}: pushes of {len(bad)} pairs differ, first #{bad[0]}"
+
+
+def _assert_empty_pairs(o, empty):
+    # a pair the kernels do not run: score INT32_MIN, ends 0xFFFFFFFF, no pushes (the oracle's definition too)
+    for k in np.nonzero(empty)[0]:
+        assert o["score"][k] == np.iinfo(np.int32).min and len(o["ops"][k]) == 0
+        assert (o["source"][k] == 0xFFFFFFFF).all() and (o["sink"][k] == 0xFFFFFFFF).all()
+
+
+def _tb_budgets():
+    n = TB_N
+    cases = [(a, t, f"c{c}") for a in TB_ALIGNERS for t in TYPES for c in (7, 64)]
+    cases += [("gotoh", "local", f"c{c}") for c in (1, 65, n - 1, n, n + 1)]
+    cases += [("gotoh", "local", "c7_plus_per_minus_1"), ("gotoh", "local", "one_byte")]
+    return cases
+
+
+def _budget_bytes(spec, per):
+    """(budget in bytes, the chunk it gives): per = workspace(max lengths, 1), the device loop's divisor."""
+    if spec == "one_byte":
+        return 1, 1                        # 1 / per = 0, clamped to chunks of 1
+    if spec == "c7_plus_per_minus_1":
+        return 7 * per + per - 1, 7
+    c = int(spec[1:])
+    return c * per, c
+
+
+@pytest.mark.parametrize("aligner,type_,budget", _tb_budgets(), ids=lambda v: str(v))
+def test_traceback_chunked(engine, monkeypatch, aligner, type_, budget):
+    """gasalx_nv_traceback_host over several chunks (the loop of gasalx_nv_traceback_device with
+    s > 0): equal to the oracle and to the one-chunk call, per-pair texts and one shared text."""
+    max_p, max_t = _assert_tb_inputs()
+    P, T, S = _tb_inputs()
+    al = _al(TB_ALIGNERS[aligner], TYPES[type_])
+    for shared in (False, True):
+        texts = S if shared else T
+        o = _tb_oracle(al, shared)
+        pl, tl = _lens(P), (np.full(TB_N, S.length) if shared else _lens(T))
+        _assert_empty_pairs(o, (pl == 0) | (tl == 0))
+        assert (pl == 0).any() and (shared or (tl == 0).any())
+        per = G.nv_traceback_workspace(max_p, S.length if shared else max_t, 1)
+        b, c = _budget_bytes(budget, per)
+        monkeypatch.setenv(BUDGET, str(b))
+        assert b // per == (0 if budget == "one_byte" else c)
+        g = engine.nv_traceback_host(al, P, texts)
+        monkeypatch.delenv(BUDGET)
+        _same_traceback(g, o, f"chunks of {c}, shared={shared}")
+        g1 = engine.nv_traceback_host(al, P, texts)
+        _same_traceback(g, g1, f"chunks of {c} against one chunk, shared={shared}")
+
+
+def _btb_budgets():
+    n = TB_N
+    cases = [(band, a, t, f"c{c}") for band in (7, 16, 31) for a in BTB_ALIGNERS for t in TYPES for c in (7, 64)]
+    cases += [(31, "gotoh", "semi", f"c{c}") for c in (1, n - 1, n + 1)]
+    return cases
+
+
+@pytest.mark.parametrize("band,aligner,type_,budget", _btb_budgets(), ids=lambda v: str(v))
+def test_banded_traceback_chunked(engine, monkeypatch, band, aligner, type_, budget):
+    """gasalx_nv_banded_traceback_host over several chunks: equal to the oracle and to the
+    one-chunk call; a band of each register class, per-pair texts (and one shared text, band 7)."""
+    max_p = _assert_btb_inputs(band)
+    P, T, S = _btb_inputs(band)
+    al = _al(BTB_ALIGNERS[aligner], TYPES[type_])
+    per = G.nv_banded_traceback_workspace(max_p, band, 1)
+    b, c = _budget_bytes(budget, per)
+    for shared in ((False, True) if band == 7 else (False,)):
+        texts = S if shared else T
+        o = _btb_oracle(al, band, shared)
+        skipped = (np.full(TB_N, S.length) if shared else _lens(T)) < _lens(P)
+        _assert_empty_pairs(o, skipped)
+        monkeypatch.setenv(BUDGET, str(b))
+        g = engine.nv_banded_traceback_host(al, band, P, texts)
+        monkeypatch.delenv(BUDGET)
+        _same_traceback(g, o, f"band {band}, chunks of {c}, shared={shared}")
+        g1 = engine.nv_banded_traceback_host(al, band, P, texts)
+        _same_traceback(g, g1, f"band {band}, chunks of {c} against one chunk, shared={shared}")
+
+
+GUARD = 64                      # elements before and after each output region
+FILL32, FILL8 = 0x5A5A5A5A, 0xA5
+DEV_BAND = 16
+
+
+def _device_traceback(engine, kind, al, P, texts, ops_stride, max_p, max_t, stream=None):
+    """One call of gasalx_nv_traceback_device / gasalx_nv_banded_traceback_device on torch device
+    tensors; every output between two guard regions, which must come back untouched."""
+    import torch
+    n = P.n
+    dev = torch.device("cuda", 0)
+    u = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.int32)).to(dev)
+    pat = {"words": u(P.words), "offsets": u(P.offsets)}
+    txt = {"words": u(texts.words), "offsets": u(texts.offsets) if texts.offsets is not None else None}
+    sizes = {"score": n, "source": 2 * n, "sink": 2 * n, "ops": n * ops_stride, "n_ops": n}
+    outs = {k: (torch.full((sz + 2 * GUARD,), FILL8, dtype=torch.uint8, device=dev) if k == "ops"
+                else torch.full((sz + 2 * GUARD,), FILL32, dtype=torch.int32, device=dev)) for k, sz in sizes.items()}
+    ptrs = {k: v.data_ptr() + GUARD * v.element_size() for k, v in outs.items()}
+    mk = lambda d, S: {"words": d["words"].data_ptr(), "offsets": d["offsets"].data_ptr() if d["offsets"] is not None else 0,
+                       "length": int(S.length), "bits": S.bits, "big_endian": S.big_endian}
+    torch.cuda.synchronize()                                  # the fills, before the library's stream starts
+    st = stream.cuda_stream if stream is not None else 0
+    if kind == "full":
+        engine.nv_traceback_device_ptrs(al, n, mk(pat, P), mk(txt, texts), ptrs, ops_stride, max_pattern_len=max_p,
+                                        max_text_len=max_t, stream=st)
+    else:
+        engine.nv_banded_traceback_device_ptrs(al, DEV_BAND, n, mk(pat, P), mk(txt, texts), ptrs, ops_stride,
+                                               max_pattern_len=max_p, stream=st)
+    if stream is not None:
+        stream.synchronize()
+    else:
+        torch.cuda.synchronize()
+    host = {k: v.cpu().numpy() for k, v in outs.items()}
+    for k, a in host.items():
+        fill = FILL8 if k == "ops" else FILL32
+        assert (a[:GUARD] == fill).all() and (a[-GUARD:] == fill).all(), f"{k}: a guard element was written"
+    body = {k: a[GUARD:-GUARD] for k, a in host.items()}
+    nops = body["n_ops"].view(np.uint32)
+    assert int(nops.max()) <= ops_stride
+    return dict(score=body["score"], source=body["source"].view(np.uint32).reshape(n, 2),
+                sink=body["sink"].view(np.uint32).reshape(n, 2),
+                ops=[body["ops"][k * ops_stride:k * ops_stride + int(nops[k])] for k in range(n)])
+
+
+DEVICE_CASES = ["readback", "exact_min_stride", "loose_maxima", "stride_odd", "stride_plus_37", "own_stream",
+                "shared_text"]
+
+
+@pytest.mark.parametrize("case", DEVICE_CASES)
+@pytest.mark.parametrize("kind", ["full", "banded"])
+def test_traceback_device_entry(engine, monkeypatch, kind, case):
+    """gasalx_nv_traceback_device and gasalx_nv_banded_traceback_device called directly on device
+    tensors: maxima read back (0), exact and loose; ops_stride at its minimum, odd and larger; the
+    caller's stream; a shared text (full DP: with a wrong max_text_len, txt->length is what
+    counts).  Each in one chunk and in chunks of 7; guards around every output stay untouched."""
+    import torch
+    if kind == "full":
+        real_p, real_t = _assert_tb_inputs()
+        P, T, S = _tb_inputs()
+        aligners, oracle = TB_ALIGNERS, _tb_oracle
+        need = lambda mp, mt: mp + mt
+        per_of = lambda mp, mt: G.nv_traceback_workspace(mp, mt, 1)
+    else:
+        real_p, real_t = _assert_btb_inputs(DEV_BAND), 0
+        P, T, S = _btb_inputs(DEV_BAND)
+        aligners, oracle = BTB_ALIGNERS, (lambda al, shared: _btb_oracle(al, DEV_BAND, shared))
+        need = lambda mp, mt: 2 * mp + DEV_BAND
+        per_of = lambda mp, mt: G.nv_banded_traceback_workspace(mp, DEV_BAND, 1)
+    shared = case == "shared_text"
+    texts = S if shared else T
+    if shared:
+        real_t = S.length
+    # the maxima passed, and those the library then works with
+    pass_p, pass_t = real_p, real_t
+    used_p, used_t = real_p, real_t
+    if case == "readback":
+        pass_p, pass_t = 0, 0
+    elif case == "loose_maxima":
+        pass_p = used_p = real_p + 5
+        pass_t = used_t = real_t + 9
+    elif shared:
+        pass_t = real_t + 31                                  # wrong on purpose (full DP; the banded call has none)
+    stride = need(used_p, used_t) + {"stride_odd": 1, "stride_plus_37": 37}.get(case, 0)
+    if case == "stride_odd":
+        assert stride % 2 == 1                                # minimum + 1: every other pair's slot misaligned
+    streams = [None, torch.cuda.Stream()] if case == "own_stream" else [None]
+    per = per_of(used_p, used_t)
+    for name in ("ed", "sw", "gotoh"):
+        for type_ in (G.NV_LOCAL, G.NV_GLOBAL):
+            al = _al(aligners[name], type_)
+            o = oracle(al, shared)
+            for stream in streams:
+                for chunk in (None, 7):
+                    if chunk:
+                        monkeypatch.setenv(BUDGET, str(chunk * per))
+                    else:
+                        monkeypatch.delenv(BUDGET, raising=False)
+                    g = _device_traceback(engine, kind, al, P, texts, stride, pass_p, pass_t, stream)
+                    monkeypatch.delenv(BUDGET, raising=False)
+                    _same_traceback(g, o, f"{kind} {name} type {type_} chunk {chunk} stream {stream is not None}")
