@@ -19,6 +19,34 @@ Reference loop structure restated (paths under Non-CDP/GASAL2/src/kernels):
           global[ridx] = (h[8], e)
 Pad bases (N_CODE) are scored like the reference: LOCAL rule (N scores 0, or
 -N_PENALTY) for local/semi-global, no N rule for global (gasal_kernels.h:39-56).
+
+Beyond the score kernels this module also restates, each in a form of its own:
+  banded()          gasal_banded_tiled_kernel (banded.h:10-139): local-type cells inside a
+                    band of 8x8 tiles, H-based E/F (the "deprecated" core, Q4).
+  local_start()     the WITH_START reverse pass (local_kernel_template.h:441-511), see below.
+  pairhmm64()       the PairHMM forward model in float64, along anti-diagonals
+                    (PairHMM/inter_task/Synthetic_data/tile_1/tile_1.cu:95-175).
+  replay_cigar()    walks a forward CIGAR over the two sequences: consumed lengths, M/X
+                    labels against the bases, the affine score of the path.
+  global_textbook() plain affine global DP without any reference quirk, for rectangle checks.
+
+What the WITH_START coordinates mean.  The reverse pass does not start at the
+end cell (q_end, t_end).  It starts at the last base of the 8-base *word* that holds each
+end: rend_reg = (q_end >> 3) + 1 words of query, gend_reg = (t_end >> 3) + 1 words of target
+(:449-456), pad bases of a last word included.  It is a LOCAL alignment of the two reversed
+word-aligned prefixes, in the forward kernel's own strip-major order, that stops at the first
+cell where the running maximum reaches the forward score (:469,479,482).  So
+  - q_start is a true query coordinate, t_start is gidx + (m-1) where the true column is
+    gidx - (m-1) (Q8): true t_start = 2 * (8 * w + 7) - t_start with w = (t_start - 7) >> 3;
+  - (q_start, true t_start) is the start of *an* alignment worth `score` that ends inside
+    the end words, at or after the end cell; it need not be the alignment that ends at
+    (q_end, t_end), whose start the LOCAL+TB walk reports.  q[q_start:q_end+1] against
+    t[t_start:t_end+1] is therefore no rectangle of anything, even after undoing Q8;
+  - a forward score of 0 runs no reverse cell and reports (0, 0).
+The oracle and the HIP start pass (start.hpp) both read it this way; local_start() below
+restates it by running local() on the reversed prefixes and mapping the end it finds back.
+
+KSW is out of scope here: its only pin stays the Q16 hand KATs (tests/test_hand_kats.py).
 """
 from __future__ import annotations
 
@@ -199,3 +227,321 @@ def semi(batch, head=2, tail=2, a=1, b=4, o=6, e=1, n_code=0x4E, npen=None):
             maxHH = np.where(upd, v, maxHH)
         maxY = np.where(maxX != tl, ql, maxY)
     return {"score": maxHH, "q_end": maxX, "t_end": maxY}
+
+
+def banded(batch, k_band, a=1, b=4, o=6, e=1, n_code=0x4E, npen=None):
+    """gasal_banded_tiled_kernel (banded.h:10-139), launched with k_band >> 3 tiles
+    (gasal_align.h:80).  local() with two differences: a strip i visits only the query tiles
+    max(0, i - kother + 1) <= tile < min(kband + i, QR), kother = TR - (QR - kband) (:35,83-85),
+    and E/F open from H, not from diag + s (:104-110, Q4).  The per-strip h/f/p registers and
+    the row buffer are only written inside the band, so whatever they held before (zeros: a
+    tile's band strips are consecutive) is what the next band cell reads, as in the reference."""
+    q, qpad = _codes(batch.q_data, batch.q_offsets, batch.q_lens, n_code)
+    t, tpad = _codes(batch.t_data, batch.t_offsets, batch.t_lens, n_code)
+    n, R = q.shape
+    T = t.shape[1]
+    nval, OE = n_code & 15, o + e
+    QR, TR = qpad // 8, tpad // 8
+    kb = int(k_band) >> 3
+    kother = TR - (QR - kb)
+    gH = np.zeros((R, n), np.int32)
+    gE = np.zeros((R, n), np.int32)
+    maxHH = np.zeros(n, np.int32)
+    maxY = np.zeros(n, np.int32)
+    prev = np.zeros(n, np.int32)
+    maxX = np.zeros(n, np.int32)
+    for i in range(T // 8):
+        first = np.maximum(0, i - kother + 1)
+        last = np.minimum(kb + i, QR)
+        h = np.zeros((9, n), np.int32); f = np.zeros((9, n), np.int32); p = np.zeros((9, n), np.int32)
+        gb = t[:, i * 8:i * 8 + 8].T
+        for r in range(R):
+            ok = (i < TR) & (r // 8 >= first) & (r // 8 < last)
+            if not ok.any():
+                continue
+            h0 = gH[r]; ee = gE[r].copy()
+            rb = q[:, r]
+            left = h0
+            for m in range(1, 9):
+                s = _sub(rb, gb[m - 1], a, b, nval, npen, True)
+                fm = np.maximum(h[m] - OE, f[m] - e)
+                ee = np.maximum(left - OE, ee - e)
+                H = np.maximum(np.maximum(np.maximum(p[m] + s, fm), 0), ee)
+                upd = ok & (maxHH < H)
+                maxY = np.where(upd, i * 8 + m - 1, maxY)
+                maxHH = np.where(upd, H, maxHH)
+                p[m] = np.where(ok, left, p[m])
+                f[m] = np.where(ok, fm, f[m])
+                h[m] = np.where(ok, H, h[m])
+                left = H
+            gH[r] = np.where(ok, _i16(left), gH[r]); gE[r] = np.where(ok, _i16(ee), gE[r])
+            maxX = np.where(ok & (prev < maxHH), r, maxX)
+            prev = np.where(ok, np.maximum(maxHH, prev), prev)
+    return {"score": maxHH, "q_end": maxX, "t_end": maxY}
+
+
+class _Pairs:
+    """The six arrays local() reads, for a batch built in this module."""
+
+    def __init__(self, qs, ts, n_code):
+        def side(seqs):
+            lens = np.array([len(s) for s in seqs], np.uint32)
+            pad = (lens.astype(np.int64) + 7) // 8 * 8
+            offs = np.concatenate([[0], np.cumsum(pad)[:-1]]).astype(np.uint32)
+            data = np.full(max(int(pad.sum()), 8), n_code, np.uint8)
+            for o, s in zip(offs, seqs):
+                data[o:o + len(s)] = s
+            return data, offs, lens
+        self.q_data, self.q_offsets, self.q_lens = side(qs)
+        self.t_data, self.t_offsets, self.t_lens = side(ts)
+
+
+def start_true_t(t_start):
+    """Undo Q8: the true target coordinate of a WITH_START t_start.  The reverse pass records
+    gidx + (m-1) with gidx = 8*w + 7 where the cell it means is gidx - (m-1)
+    (local_kernel_template.h:41,468,476)."""
+    ts = np.asarray(t_start, np.int64)
+    w = (ts - 7) >> 3
+    return 2 * (8 * w + 7) - ts
+
+
+def local_start(batch, a=1, b=4, o=6, e=1, n_code=0x4E, npen=None, fwd=None):
+    """q_start / t_start of gasal_local_kernel<LOCAL, WITH_START> (local_kernel_template.h:441-511),
+    see the module docstring.  Restated as: local() over the reversed word-aligned prefixes
+    q[0 : 8*rend_reg], t[0 : 8*gend_reg] (pads of the end words included, :449-456,475,480);
+    its first maximum in strip-major order is the cell at which the reference's running
+    maximum reaches the forward score and every loop stops (:469,479,482); that cell (r', c')
+    maps back to q_start = 8*rend_reg-1-r' (:477,502) and, with Q8,
+    t_start = gidx + (m-1) = 8*(gend_reg - (c'>>3)) - 1 + (c'&7) (:468,476,41).
+    A forward score of 0 enters no loop: (0, 0) (:459-462,469)."""
+    if fwd is None:
+        fwd = local(batch, a, b, o, e, n_code, npen)
+    n = len(batch.q_lens)
+    rq = (fwd["q_end"].astype(np.int64) >> 3) + 1
+    rt = (fwd["t_end"].astype(np.int64) >> 3) + 1
+
+    def rev(data, offs, words):
+        return [np.asarray(data[int(o):int(o) + 8 * int(w)])[::-1] for o, w in zip(offs, words)]
+    r = local(_Pairs(rev(batch.q_data, batch.q_offsets, rq), rev(batch.t_data, batch.t_offsets, rt), n_code),
+              a, b, o, e, n_code, npen)
+    assert np.array_equal(r["score"], fwd["score"]), "reversed prefixes must reach the forward score"
+    rr, cc = r["q_end"].astype(np.int64), r["t_end"].astype(np.int64)
+    qs = 8 * rq - 1 - rr
+    ts = 8 * (rt - (cc >> 3)) - 1 + (cc & 7)
+    zero = fwd["score"] == 0
+    return {"q_start": np.where(zero, 0, qs).astype(np.int32), "t_start": np.where(zero, 0, ts).astype(np.int32)}
+
+
+def pairhmm64(reads, read_off, read_len, qm, delta, xiksi, alpha, haps, hap_off, hap_len):
+    """The PairHMM forward value of every pair in float64
+    (PairHMM/inter_task/Synthetic_data/tile_1/tile_1.cu:95-175, constants :228-234).
+    The fp32 parameter arrays and the reference's fp32 constants (c0 = 1.329228e+36f, 0.9f,
+    0.1f) are widened as given, so only the arithmetic differs from an fp32 evaluation.
+      D[-1][j] = c0/H, M[-1][j] = I[-1][j] = 0, column -1 is 0 (but D[-1][-1] = c0/H)
+      prior(i,j) = 1 - qm_i if read_i == hap_j else qm_i / 3
+      M[i][j] = prior(i,j) * (alpha_i*M[i-1][j-1] + 0.9*(I[i-1][j-1] + D[i-1][j-1]))
+      I[i][j] = delta_i*M[i-1][j] + 0.1*I[i-1][j]
+      D[i][j] = xi_i*M[i][j-1] + 0.1*D[i][j-1]
+      result  = sum_j M[R-1][j] + I[R-1][j]
+    Form: all pairs advance together one anti-diagonal d = i + j at a time; arrays are indexed
+    by read row (slot 0 is row -1), the diagonals d-1 and d-2 are kept."""
+    R = np.asarray(read_len, np.int64); H = np.asarray(hap_len, np.int64)
+    ro = np.asarray(read_off, np.int64); ho = np.asarray(hap_off, np.int64)
+    n = len(R)
+    if n == 0:
+        return np.zeros(0, np.float64)
+    Rm = int(R.max())
+    rows = np.arange(Rm)
+    ridx = np.minimum(ro[:, None] + rows[None, :], len(reads) - 1)
+    rd = np.asarray(reads, np.uint8)[ridx]
+    w = lambda x: np.asarray(x, np.float32).astype(np.float64)[ridx]
+    Qm, De, Xi, Al = w(qm), w(delta), w(xiksi), w(alpha)
+    p_eq, p_ne = 1.0 - Qm, Qm / 3.0
+    c0, c3, c4 = (float(np.float32(x)) for x in (1.329228e+36, 0.9, 0.1))
+    haps = np.asarray(haps, np.uint8)
+    row_ok = rows[None, :] < R[:, None]
+    zero = np.zeros((n, Rm + 1))
+    M1, I1, D1, M2, I2, D2 = (zero.copy() for _ in range(6))
+    D1[:, 0] = D2[:, 0] = c0 / H                      # row -1, any column
+    res = np.zeros(n)
+    pn = np.arange(n)
+    for d in range(int((R + H).max()) - 1):
+        j = d - rows[None, :]
+        ok = row_ok & (j >= 0) & (j < H[:, None])
+        hb = haps[np.clip(ho[:, None] + j, 0, len(haps) - 1)]
+        prior = np.where(hb == rd, p_eq, p_ne)
+        M = np.where(ok, prior * (Al * M2[:, :-1] + c3 * (I2[:, :-1] + D2[:, :-1])), 0.0)
+        I = np.where(ok, De * M1[:, :-1] + c4 * I1[:, :-1], 0.0)
+        D = np.where(ok, Xi * M1[:, 1:] + c4 * D1[:, 1:], 0.0)
+        jl = d - (R - 1)
+        last = (jl >= 0) & (jl < H)
+        res += np.where(last, M[pn, R - 1] + I[pn, R - 1], 0.0)
+        M2, I2, D2 = M1, I1, D1
+        M1 = np.concatenate([zero[:, :1], M], axis=1)
+        I1 = np.concatenate([zero[:, :1], I], axis=1)
+        D1 = np.concatenate([(c0 / H)[:, None], D], axis=1)
+    return res
+
+
+def _affine_rows(q, t, a, b, o, e, nval, npen, n_rule):
+    """H of the textbook affine global DP, [len(q)+1, len(t)+1] with the boundary row/column."""
+    q = np.asarray(q, np.int64) & 15; t = np.asarray(t, np.int64) & 15
+    nq, nt = len(q), len(t)
+    NEG = -(1 << 40)
+    cols = np.arange(nt + 1, dtype=np.int64)
+    H = np.empty((nq + 1, nt + 1), np.int64)
+    H[0] = np.where(cols == 0, 0, -(o + e * cols))
+    F = np.full(nt + 1, NEG, np.int64)
+    for i in range(1, nq + 1):
+        s = np.where(q[i - 1] == t, a, -b)
+        if n_rule:
+            s = np.where((q[i - 1] == nval) | (t == nval), -(npen or 0), s)
+        F = np.maximum(H[i - 1] - (o + e), F - e)
+        best = np.full(nt + 1, NEG, np.int64)
+        best[0] = -(o + e * i)
+        best[1:] = np.maximum(H[i - 1, :-1] + s, F[1:])
+        # E[j] = max_{k<j} best[k] - o - e*(j-k): a gap never opens from an E-derived cell
+        run = np.maximum.accumulate(best + e * cols)
+        E = np.full(nt + 1, NEG, np.int64)
+        E[1:] = run[:-1] - o - e * cols[1:]
+        H[i] = np.maximum(best, E)
+    return H
+
+
+def global_textbook(q, t, scores=(1, 4, 6, 1), n_code=0x4E, npen=None, n_rule=False, full=False):
+    """Plain affine global alignment score of byte sequences q and t (codes = byte & 15):
+    H = max(diag + s, E, F), gaps of k cost o + e*k on every side, no reference quirk
+    (no Q2 boundary, no Q4 shortcut, no int16 buffer).  n_rule: score N like the LOCAL
+    kernels (0, or -npen).  full: return the whole H matrix with its boundary."""
+    a, b, o, e = scores
+    H = _affine_rows(np.frombuffer(bytes(q), np.uint8), np.frombuffer(bytes(t), np.uint8), a, b, o, e,
+                     n_code & 15, npen, n_rule)
+    return H if full else int(H[-1, -1])
+
+
+LOCAL_MODE, GLOBAL_MODE = "local", "global"
+
+
+def replay_cigar(q, t, cigar, scores=(1, 4, 6, 1), mode=LOCAL_MODE, n_code=0x4E, npen=None):
+    """Walk the forward CIGAR text (gasal_ffi.decode_cigar) over byte sequences q and t.
+    Returns (q_used, t_used, score, bad, n_pairs): the bases each side consumed, the affine
+    score of the path (M/X by the bases' substitution score, a run of k I or D costs o + e*k),
+    the first (op index, op, q position, t position) whose M/X label disagrees with the
+    bases, or None, and the number of M/X base pairs that hold an N (LOCAL only, rule L1).
+    M consumes both, X both, I the query, D the target (get_tb.h:107-108).
+
+    LOCAL: q and t are the aligned slices q[q_start:q_end+1], t[t_start:t_end+1]; a base
+    pair with an N scores 0 (-npen with N_PENALTY) and is labelled by that score's sign
+    (gasal_kernels.h:39-51, local_kernel_template.h:49).
+      L1 the LOCAL walk stops when its own running sum reaches `score`, and that sum counts
+         every op-0 cell as +match (get_tb.h:100-103) although a pair with an N scored 0 in
+         the forward pass.  A path through n such pairs therefore stops n*match early (the
+         CIGAR is a suffix of the alignment: score here + n_pairs*match == `score`), or
+         steps over `score` without ever equalling it and runs off the matrix (a start
+         coordinate of -1).  Without N on the path the replayed score is `score` itself.
+
+    GLOBAL: q and t are the whole sequences; no N rule (gasal_kernels.h:53-54).  Reference
+    rules applied, each needed for the replay to close:
+      G1 the walk starts at the pad cell (i, j) = (tl, ql), one past both ends (get_tb.h:21-23,
+         Q9): the CIGAR ends with one M over the pad pair, which belongs to no base and is
+         left out of the score; q_used / t_used count it (ql + 1, tl + 1).
+      G2 a leading run of k I costs o + e*(k-1), and 0 for k = 1: the left boundary is
+         H(r,-1) = -(o + e*r), H(0,-1) = 0 (global.h:57-60, Q2).
+      G3 the last pair of an M run that is followed by an I or D run may hold unequal
+         bases: in gap mode a cell whose extend bit is clear ends the gap through that
+         cell's diagonal and is written as op 0 whatever the bases are (get_tb.h:74-82,
+         Q19; the gap opened from diag + s, not from H, global.h:7-12, Q4).  It scores
+         its real substitution value and is not a label disagreement."""
+    import re
+    a, b, o, e = scores
+    nval = n_code & 15
+    qc = np.frombuffer(bytes(q), np.uint8).astype(np.int64) & 15
+    tc = np.frombuffer(bytes(t), np.uint8).astype(np.int64) & 15
+    is_global = mode == GLOBAL_MODE
+    if is_global:                                   # G1: the pad pair
+        qc = np.append(qc, nval); tc = np.append(tc, nval)
+    ops = [(int(k), op) for k, op in re.findall(r"(\d+)([MXDI])", cigar)]
+    qi = ti = 0
+    score = n_pairs = 0
+    bad = None
+    for u, (k, op) in enumerate(ops):
+        if op in "MX":
+            for x in range(k):
+                if qi >= len(qc) or ti >= len(tc):
+                    return qi + (k - x), ti + (k - x), score, bad or (u, op, qi, ti), n_pairs
+                pad_pair = is_global and qi == len(qc) - 1 and ti == len(tc) - 1
+                s = a if qc[qi] == tc[ti] else -b
+                if not is_global and (qc[qi] == nval or tc[ti] == nval):
+                    s = -npen if npen is not None else 0
+                    n_pairs += 1
+                elif is_global and npen is not None and (qc[qi] == nval or tc[ti] == nval):
+                    s = -npen
+                want = "M" if s >= 0 else "X"
+                g3 = (is_global and op == "M" and x == k - 1 and u + 1 < len(ops) and ops[u + 1][1] in "ID")
+                if op != want and not g3 and bad is None:
+                    bad = (u, op, qi, ti)
+                if not pad_pair:
+                    score += s
+                qi += 1; ti += 1
+        else:
+            cost = o + e * k
+            if is_global and u == 0 and op == "I":                    # G2
+                cost = o + e * (k - 1) if k > 1 else 0
+            score -= cost
+            if op == "I":
+                qi += k
+            else:
+                ti += k
+    if is_global and (not ops or ops[-1][1] != "M") and bad is None:   # G1: the pad pair is an M
+        bad = (len(ops) - 1, ops[-1][1] if ops else "", qi, ti)
+    return qi, ti, score, bad, n_pairs
+
+
+def replay_batch(qs, ts, batch, res, scores, mode, decode, keep, rect=True):
+    """replay_cigar over every kept pair of a WITH_TB result (res: score, cigar, n_ops and,
+    LOCAL, the four coordinates; decode: gasal_ffi.decode_cigar).  Returns a dict of
+    counts: checked, zero (LOCAL pairs of score 0: no alignment to replay), n_path (LOCAL
+    pairs with an N pair on the path, rule L1), ran_off (of those, walks that left the
+    matrix), stepped (of those, match > 1: not checked further), and `failures`, a list of (pair, what, detail).  Per pair it checks the
+    consumed lengths, the labels, the replayed score and, LOCAL with rect, that
+    global_textbook of the start-to-end rectangle equals `score`."""
+    out = dict(checked=0, zero=0, n_path=0, ran_off=0, stepped=0, failures=[])
+    fail = lambda k, what, d: out["failures"].append((int(k), what, d))
+    a = scores[0]
+    for k in np.flatnonzero(keep):
+        cig = decode(res["cigar"], int(batch.q_offsets[k]), int(res["n_ops"][k]))
+        sc = int(res["score"][k])
+        if mode == GLOBAL_MODE:
+            qu, tu, s, bad, _ = replay_cigar(qs[k], ts[k], cig, scores, mode)
+            want = (len(qs[k]) + 1, len(ts[k]) + 1)
+            npairs = 0
+        else:
+            if sc == 0:
+                out["zero"] += 1
+                continue
+            q0, q1, t0, t1 = (int(res[f][k]) for f in ("q_start", "q_end", "t_start", "t_end"))
+            if q0 < 0 or t0 < 0:                     # L1: the walk stepped over `score`
+                out["n_path"] += 1; out["ran_off"] += 1
+                if replay_cigar(qs[k][max(q0, 0):q1 + 1], ts[k][max(t0, 0):t1 + 1], cig, scores, mode)[4] == 0:
+                    fail(k, "start", f"walk left the matrix without an N pair on the path: {cig}")
+                continue
+            q, t = qs[k][q0:q1 + 1], ts[k][t0:t1 + 1]
+            qu, tu, s, bad, npairs = replay_cigar(q, t, cig, scores, mode)
+            want = (len(q), len(t))
+            out["n_path"] += npairs > 0
+            if npairs and a != 1:                    # L1: the sum may have stepped over `score`
+                out["stepped"] += 1                  # and met it again anywhere; nothing to hold
+                continue
+            s += npairs * a                          # L1
+        out["checked"] += 1
+        if (qu, tu) != want:
+            fail(k, "lengths", f"consumed {(qu, tu)} of {want}: {cig}")
+        if bad is not None:
+            fail(k, "label", f"{bad}: {cig}")
+        if s != sc:
+            fail(k, "score", f"replayed {s}, reported {sc}: {cig}")
+        if mode == LOCAL_MODE and rect and npairs == 0:
+            g = global_textbook(q, t, scores, n_rule=True)
+            if g != sc:
+                fail(k, "rectangle", f"global alignment of the rectangle {g}, score {sc}")
+    return out

@@ -765,7 +765,10 @@ def test_pairhmm_random_long(engine):
         pairs.append(dict(read=read.decode(), hap=hap, bq=rng.integers(10, 41, R), iq=np.full(R, 45),
                           dq=np.full(R, 45)))
     args = _hmm_batch(pairs)
-    np.testing.assert_allclose(engine.pairhmm_host(*args), O.pairhmm(*args), rtol=1e-5)
+    o = O.pairhmm(*args)
+    np.testing.assert_allclose(engine.pairhmm_host(*args), o, rtol=1e-5)
+    print(f"oracle results that are exactly 0: {(o == 0).mean():.1%}")
+    assert (o == 0).mean() == 0     # share of 0-against-0 comparisons here: none (related reads)
 
 
 @pytest.mark.parametrize("scores", [(1, 4, 6, 1), (2, 3, 5, 2), (1, 1, 0, 1), (3, 6, 0, 0)])
@@ -871,7 +874,9 @@ def test_pairhmm_edge_lengths(engine):
             pairs.append(dict(read=read, hap=hap, bq=rng.integers(0, 60, R), iq=rng.integers(10, 60, R),
                               dq=rng.integers(10, 60, R)))
     args = _hmm_batch(pairs)
-    np.testing.assert_allclose(engine.pairhmm_host(*args), O.pairhmm(*args), rtol=1e-5)
+    o = O.pairhmm(*args)
+    np.testing.assert_allclose(engine.pairhmm_host(*args), o, rtol=1e-5)
+    print(f"oracle results that are exactly 0: {(o == 0).mean():.1%}")
     # every lane-group size with the longest read exactly filling the group's rows
     # (boundary select) and one row short of it (the top lane's first row absorbs
     # the boundary, pairhmm.hpp ABS)
@@ -879,6 +884,26 @@ def test_pairhmm_edge_lengths(engine):
         sub = [p for p in pairs if len(p["read"]) <= cap]
         a = _hmm_batch(sub)
         np.testing.assert_allclose(engine.pairhmm_host(*a), O.pairhmm(*a), rtol=1e-5, err_msg=f"reads <= {cap}")
+    # 24.4 % of the oracle results above are exactly 0 (22 of 90): 0 against 0,
+    # so every boundary length R >= 129 also gets a related read per H, whose oracle value is a
+    # normal fp32 number and is compared for real.  Where the haplotype is too short for that
+    # (helpers.hmm_insertion_bound: H in 1, 2 forces over 100 insertion rows at 0.1 each) no
+    # read has a normal value: there both sides must underflow
+    rel = []
+    for R in (129, 255, 256):
+        for H in helpers.hmm_hap_lens(R):
+            hap = helpers.random_seq(rng, H).decode()
+            rel.append(dict(read=helpers.hmm_related_read(rng, hap, R), hap=hap, bq=rng.integers(10, 41, R),
+                            iq=rng.integers(10, 26, R), dq=rng.integers(10, 60, R)))
+    forced = np.array([helpers.hmm_insertion_bound(len(p["read"]), len(p["hap"])) for p in rel])
+    for cap in (256, 255, 129):
+        sub = [p for p in rel if len(p["read"]) <= cap]
+        fo = forced[:len(sub)]
+        a = _hmm_batch(sub)
+        o, g = O.pairhmm(*a), engine.pairhmm_host(*a)
+        assert np.all(o[~fo] > np.finfo(np.float32).tiny)
+        np.testing.assert_allclose(g[~fo], o[~fo], rtol=1e-5, err_msg=f"related reads <= {cap}")
+        assert np.all(o[fo] == 0) and np.all(np.isfinite(g[fo]) & (g[fo] >= 0) & (g[fo] < np.finfo(np.float32).tiny))
 
 
 def test_pairhmm_prior_table_vs_compare(engine):
@@ -908,7 +933,10 @@ def test_pairhmm_prior_table_vs_compare(engine):
     assert np.array_equal(gp, gm[0::2])
     np.testing.assert_allclose(gp, O.pairhmm(*a), rtol=1e-5)
     m = _hmm_batch(mixed)
-    np.testing.assert_allclose(gm, O.pairhmm(*m), rtol=1e-5)
+    om = O.pairhmm(*m)
+    np.testing.assert_allclose(gm, om, rtol=1e-5)
+    print(f"oracle results that are exactly 0: pure {(O.pairhmm(*a) == 0).mean():.1%}, mixed {(om == 0).mean():.1%}")
+    # 16.7 % of the oracle results are exactly 0 in both batches (long unrelated reads): 0 against 0 there
 
 
 def test_host_pipeline_pinned_cigar(engine):

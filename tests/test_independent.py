@@ -86,3 +86,164 @@ def test_row_buffer_int16_wrap():
     b = G.Batch.from_pairs([q], [t])
     ref = O.align(b, O.make_params(algo=O.GLOBAL, gap_open=2000, gap_extend=900))
     _same(I.global_(b, 1, 4, 2000, 900), ref, ("score",))
+
+
+# ------------------------------------------------------------------ PairHMM ----
+FLT_MIN = float(np.finfo(np.float32).tiny)
+
+
+def test_pairhmm_oracle_against_float64():
+    """The fp32 oracle against the float64 model on related reads over the lane-boundary
+    grid.  Every cell whose haplotype is long enough for the read (helpers.hmm_insertion_bound)
+    must stay >= 1e-30 in float64 and agree to 1e-5; the cells where the model itself forces
+    the value below 1e-30 belong to the underflow class below."""
+    pairs = helpers.hmm_related_grid()
+    args = helpers.hmm_args(pairs, O.pairhmm_params)
+    f = I.pairhmm64(*args)
+    o = O.pairhmm(*args).astype(np.float64)
+    forced = np.array([helpers.hmm_insertion_bound(len(p["read"]), len(p["hap"])) for p in pairs])
+    assert forced.sum() == 10                      # R in 127, 128, 129, 255, 256 with H in 1, 2
+    assert np.all(f[~forced] >= 1e-30), f[~forced].min()
+    assert np.all(f[forced] < 1e-45) and np.all(o[forced] == 0.0)
+    rel = np.abs(o[~forced] - f[~forced]) / f[~forced]
+    print(f"pairhmm oracle vs float64: worst relative error {rel.max():.3g}, smallest value {f[~forced].min():.3g}")
+    # measured: worst 3.2e-06 (R = 1, H = 500), smallest value 3.4e-28
+    assert rel.max() <= 1e-5
+
+
+def test_pairhmm_oracle_underflow_class():
+    """What "the reference underflows" means: where the float64 value is below 1e-45 (under
+    the smallest fp32 denormal) the fp32 oracle returns exactly 0, never NaN or inf."""
+    pairs = helpers.hmm_unrelated(0xF10, (129, 256) * 6)
+    args = helpers.hmm_args(pairs, O.pairhmm_params)
+    f = I.pairhmm64(*args)
+    o = O.pairhmm(*args)
+    under = f < 1e-45
+    assert under.sum() >= 12, (int(under.sum()), f)
+    assert np.all(np.isfinite(o))
+    assert np.all(o[under] == 0.0)
+
+
+# -------------------------------------------------------------- CIGAR replay ----
+TB_SCORES = [(1, 4, 6, 1), (2, 3, 5, 2)]
+TB_ALPHABETS = [b"ACGT", b"ACGTACGTACGTN"]
+
+
+def _tb_pairs(alphabet, seed=9):
+    rng = np.random.default_rng(seed)
+    qs, ts = helpers.random_pairs(rng, 400, 1, 80, 1, 90, alphabet=alphabet)
+    return qs, ts, G.Batch.from_pairs(qs, ts)
+
+
+def _replay(algo, mode, sc, alphabet, cap_zero=0.02):
+    a, bb, o, e = sc
+    qs, ts, b = _tb_pairs(alphabet)
+    kw = dict(match=a, mismatch=bb, gap_open=o, gap_extend=e)
+    r = O.align(b, O.make_params(algo=algo, start_pos=O.WITH_TB, **kw))
+    keep = helpers.cigar_slots_kept(b.q_offsets, b.q_lens, r["n_ops"])
+    skipped = 1 - keep.mean()
+    assert skipped <= 0.02, skipped                 # Q14
+    st = I.replay_batch(qs, ts, b, r, sc, mode, G.decode_cigar, keep)
+    print(f"{mode} {sc} {alphabet.decode()}: Q14 skipped {skipped:.3%}, score 0 {st['zero']}, "
+          f"N on the path {st['n_path']} (ran off {st['ran_off']}, unchecked {st['stepped']}), checked {st['checked']}")
+    assert not st["failures"], (len(st["failures"]), st["failures"][:3])
+    assert st["zero"] <= cap_zero * b.n
+    ref = (I.local if mode == I.LOCAL_MODE else I.global_)(b, a, bb, o, e)
+    assert np.array_equal(r["score"], ref["score"])
+    return st
+
+
+@pytest.mark.parametrize("alphabet", TB_ALPHABETS)
+@pytest.mark.parametrize("sc", TB_SCORES + [(1, 1, 0, 1)])
+def test_local_tb_cigar_replay_and_rectangle(sc, alphabet):
+    """Every oracle LOCAL+TB CIGAR replayed over the bases: consumed lengths equal the
+    start-to-end rectangle, every M sits on a pair that scores >= 0 and every X on one that
+    scores < 0, the replayed affine score equals `score`, `score` equals independent.local(),
+    and the plain global alignment of the rectangle is worth `score` (the TB start is the
+    start of the alignment that ends at the end cell).  Paths through an N pair follow
+    rule L1 of replay_cigar and are not rectangles."""
+    st = _replay(O.LOCAL, I.LOCAL_MODE, sc, alphabet)
+    if alphabet == b"ACGT":
+        assert st["n_path"] == 0 and st["checked"] + st["zero"] == 400
+    # measured: Q14 skipped 0 everywhere, score 0: 0 pairs
+
+
+@pytest.mark.parametrize("alphabet", TB_ALPHABETS)
+@pytest.mark.parametrize("sc", TB_SCORES)
+def test_global_tb_cigar_replay(sc, alphabet):
+    """Every oracle GLOBAL+TB CIGAR replayed with the reference rules G1-G3 of replay_cigar:
+    both sequences consumed (plus the pad pair), labels agree with the bases, the replayed
+    score equals `score`, and `score` equals independent.global_().  G3 is what
+    explains the M labels over unequal bases that G1 and G2 alone leave (about 1 % of pairs)."""
+    _replay(O.GLOBAL, I.GLOBAL_MODE, sc, alphabet)
+    # measured: Q14 skipped 0 of 400 on both score sets
+
+
+def test_replay_cigar_rules_by_hand():
+    # G2 / Q2: TTACGT against ACGT is 2I4M(+pad M) worth -3, not the textbook -4
+    assert I.replay_cigar(b"TTACGT", b"ACGT", "2I5M", (1, 4, 6, 1), I.GLOBAL_MODE)[:4] == (7, 5, -3, None)
+    assert I.global_textbook(b"TTACGT", b"ACGT") == -4
+    # one leading I is free, one leading D is not
+    assert I.replay_cigar(b"TACG", b"ACG", "1I4M", (1, 4, 6, 1), I.GLOBAL_MODE)[2] == 3
+    assert I.replay_cigar(b"ACG", b"TACG", "1D4M", (1, 4, 6, 1), I.GLOBAL_MODE)[2] == -4
+    # a wrong label is found, and swapping I and D breaks the consumed lengths
+    assert I.replay_cigar(b"ACGT", b"ACCT", "5M", (1, 4, 6, 1), I.GLOBAL_MODE)[3] == (0, "M", 2, 2)
+    assert I.replay_cigar(b"ACGT", b"ACCT", "2M1X2M", (1, 4, 6, 1), I.GLOBAL_MODE)[:4] == (5, 5, -1, None)
+    assert I.replay_cigar(b"AACGT", b"ACGT", "1M1D4M", (1, 4, 6, 1), I.GLOBAL_MODE)[:2] != (6, 5)
+    # G3 / Q19: the M before a gap may sit on unequal bases and scores as the mismatch it is
+    assert I.replay_cigar(b"ACGTT", b"ACCAATT", "3M2D3M", (1, 4, 6, 1), I.GLOBAL_MODE)[2:4] == (2 - 4 - 8 + 2, None)
+    # LOCAL: N pairs score 0 and are labelled M
+    assert I.replay_cigar(b"ANG", b"ACG", "3M", (1, 4, 6, 1), I.LOCAL_MODE) == (3, 3, 2, None, 1)
+    assert I.global_textbook(b"ACGT", b"AGT", (1, 4, 6, 1)) == 3 - 7
+
+
+# -------------------------------------------------------------- WITH_START ----
+@pytest.mark.parametrize("alphabet", TB_ALPHABETS)
+@pytest.mark.parametrize("sc", TB_SCORES)
+def test_local_with_start_restated(sc, alphabet):
+    """WITH_START (module docstring of independent.py): the oracle's q_start and
+    t_start equal independent.local_start() on every pair, and the coordinates mean what
+    Q21 says: after undoing Q8 on t_start, some end cell inside the end words, at or after
+    (q_end, t_end), closes a plain global alignment from the start that is worth `score`."""
+    a, bb, o, e = sc
+    qs, ts, b = _tb_pairs(alphabet, seed=5)
+    kw = dict(match=a, mismatch=bb, gap_open=o, gap_extend=e)
+    r = O.align(b, O.make_params(algo=O.LOCAL, start_pos=O.WITH_START, **kw))
+    ref = I.local_start(b, a, bb, o, e)
+    _same(ref, r, ("q_start", "t_start"))
+    tt = I.start_true_t(r["t_start"])
+    tb = O.align(b, O.make_params(algo=O.LOCAL, start_pos=O.WITH_TB, **kw))
+    same = (r["q_start"] == tb["q_start"]) & (tt == tb["t_start"])
+    print(f"WITH_START {sc} {alphabet.decode()}: decoded start equals the LOCAL+TB start on {same.mean():.1%}")
+    for k in range(b.n):
+        if r["score"][k] == 0:
+            assert (r["q_start"][k], r["t_start"][k]) == (0, 0)
+            continue
+        q0, t0, q1, t1 = int(r["q_start"][k]), int(tt[k]), int(r["q_end"][k]), int(r["t_end"][k])
+        assert 0 <= q0 <= (q1 | 7) and 0 <= t0 <= (t1 | 7), (k, q0, t0, q1, t1)
+        # the end words, pads included (N scores 0 under the LOCAL rule)
+        q = (qs[k] + b"N" * 8)[q0:(q1 | 7) + 1]
+        t = (ts[k] + b"N" * 8)[t0:(t1 | 7) + 1]
+        H = I.global_textbook(q, t, sc, n_rule=True, full=True)
+        assert H.max() <= r["score"][k], (k, "an alignment from the start beats the local maximum")
+        ends = H[max(q1 - q0, 0) + 1:, 1:]
+        assert (ends == r["score"][k]).any(), (k, q0, t0, q1, t1, int(r["score"][k]))
+    if alphabet == b"ACGT":
+        assert same.mean() > 0.9                    # measured 95 %; with N (scores 0) under half
+
+
+# ------------------------------------------------------------------ banded ----
+@pytest.mark.parametrize("lens", [(1, 70, 1, 90), (120, 136, 120, 160)])
+@pytest.mark.parametrize("k_band", [0, 1, 2, 4, 8, 400])
+def test_banded(k_band, lens):
+    rng = np.random.default_rng(3 + k_band)
+    qs, ts = helpers.random_pairs(rng, 120, *lens, alphabet=b"ACGTN")
+    b = G.Batch.from_pairs(qs, ts)
+    for a, bb, o, e in SCORES[:2]:
+        ref = O.align(b, O.make_params(algo=O.BANDED, k_band=k_band, match=a, mismatch=bb, gap_open=o, gap_extend=e))
+        r = I.banded(b, k_band, a, bb, o, e)
+        _same(r, ref, ("score", "q_end", "t_end"))
+        if k_band == 400:
+            # the whole matrix is inside the band; H-based and diag-based E/F (Q4) agree
+            # while mismatch < open + 2*extend (an I next to a D never beats an X)
+            _same(I.local(b, a, bb, o, e), ref, ("score", "q_end", "t_end"))

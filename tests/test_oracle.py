@@ -103,6 +103,13 @@ def test_local_start_matches_traceback_start():
     r1 = O.align(b, O.make_params(algo=O.LOCAL, start_pos=O.WITH_TB))
     assert np.all(r1["score"] >= 40)
     assert np.all(r1["q_start"] <= 5) and np.all(r1["t_start"] <= 20)
+    r2 = O.align(b, O.make_params(algo=O.LOCAL, start_pos=O.WITH_START))
+    for f in ("score", "q_end", "t_end"):
+        assert np.array_equal(r1[f], r2[f]), f
+    # q_start is a true coordinate; t_start is gidx + (m-1) for the cell gidx - (m-1), gidx = 8w + 7 (Q8)
+    w = (r2["t_start"] - 7) >> 3
+    assert np.array_equal(r2["q_start"], r1["q_start"])
+    assert np.array_equal(2 * (8 * w + 7) - r2["t_start"], r1["t_start"])
 
 
 def test_q2_leading_query_gap_quirk():
