@@ -37,6 +37,9 @@ struct gasalx_engine {
     gx::DevBuf o_score, o_qe, o_te, o_qs, o_ts, o_s2, o_qe2, o_te2, o_cig, o_nops, lens_max;
     gx::DevBuf h_reads, h_ro, h_rl, h_qm, h_de, h_xi, h_al, h_haps, h_ho, h_hl, h_res;
     gx::DevBuf h_bq, h_iq, h_dq, h_perm, ph2pr;   // PairHMM from qualities: staging + the ph2pr table
+    // PairHMM log10 / float64: the fp32 pass's results, the rescue list (its count in the first of
+    // four words, then one word per pair), and the host forms' device outputs
+    gx::DevBuf hm_r32, hm_list, h_res64, h_used;
     gx::DevBuf nv_pw, nv_po, nv_tw, nv_to, nv_s, nv_s16;   // nvbio front-end staging
     gx::DevBuf nv_dir, nv_row, nv_src, nv_snk, nv_ops, nv_nops;   // nvbio traceback: workspace + staging
     void release() {
@@ -45,7 +48,7 @@ struct gasalx_engine {
         for (gx::DevBuf *b : {&q, &t, &qo, &to, &ql, &tl, &qop, &top, &seed, &o_score, &o_qe, &o_te, &o_qs, &o_ts,
                               &o_s2, &o_qe2, &o_te2, &o_cig, &o_nops, &lens_max, &h_reads, &h_ro, &h_rl, &h_qm,
                               &h_de, &h_xi, &h_al, &h_haps, &h_ho, &h_hl, &h_res, &h_bq, &h_iq, &h_dq, &h_perm,
-                              &ph2pr, &nv_pw, &nv_po, &nv_tw, &nv_to, &nv_s, &nv_s16, &nv_dir, &nv_row,
+                              &ph2pr, &hm_r32, &hm_list, &h_res64, &h_used, &nv_pw, &nv_po, &nv_tw, &nv_to, &nv_s, &nv_s16, &nv_dir, &nv_row,
                               &nv_src, &nv_snk, &nv_ops, &nv_nops})
             b->release();
     }
@@ -90,6 +93,28 @@ int stage_in(gx::DevBuf &d, const T *h, size_t count, hipStream_t st, T **dptr) 
     CK(d.reserve(count * sizeof(T) + 16));
     CK(hipMemcpyAsync(d.p, h, count * sizeof(T), hipMemcpyHostToDevice, st));
     *dptr = d.as<T>();
+    return GASALX_OK;
+}
+
+// Stage a host PairHMM batch (parameter form) into the engine's device buffers; db = its device image
+// with max_read_len / max_hap_len filled in.
+int hmm_stage_host(gasalx_engine *eng, const gasalx_hmm_batch *hb, hipStream_t st, gasalx_hmm_batch &db) {
+    const uint32_t n = hb->n_pairs;
+    db = *hb;
+    int rc;
+    uint8_t *p8; uint32_t *p32; float *pf;
+    if ((rc = stage_in(eng->h_reads, hb->reads, hb->read_bytes, st, &p8))) return rc; db.reads = p8;
+    if ((rc = stage_in(eng->h_ro, hb->read_offsets, n, st, &p32))) return rc; db.read_offsets = p32;
+    if ((rc = stage_in(eng->h_rl, hb->read_lens, n, st, &p32))) return rc; db.read_lens = p32;
+    if ((rc = stage_in(eng->h_qm, hb->qm, hb->read_bytes, st, &pf))) return rc; db.qm = pf;
+    if ((rc = stage_in(eng->h_de, hb->delta, hb->read_bytes, st, &pf))) return rc; db.delta = pf;
+    if ((rc = stage_in(eng->h_xi, hb->xiksi, hb->read_bytes, st, &pf))) return rc; db.xiksi = pf;
+    if ((rc = stage_in(eng->h_al, hb->alpha, hb->read_bytes, st, &pf))) return rc; db.alpha = pf;
+    if ((rc = stage_in(eng->h_haps, hb->haps, hb->hap_bytes, st, &p8))) return rc; db.haps = p8;
+    if ((rc = stage_in(eng->h_ho, hb->hap_offsets, n, st, &p32))) return rc; db.hap_offsets = p32;
+    if ((rc = stage_in(eng->h_hl, hb->hap_lens, n, st, &p32))) return rc; db.hap_lens = p32;
+    db.max_read_len = hb->max_read_len ? hb->max_read_len : host_max(hb->read_lens, n);
+    db.max_hap_len = hb->max_hap_len ? hb->max_hap_len : host_max(hb->hap_lens, n);
     return GASALX_OK;
 }
 
@@ -420,23 +445,11 @@ int gasalx_pairhmm_host(gasalx_engine *eng, const gasalx_hmm_batch *hb, float *h
     CK(hipSetDevice(eng->device));
     hipStream_t st = eng->stream;
     const uint32_t n = hb->n_pairs;
-    gasalx_hmm_batch db = *hb;
-    int rc;
-    uint8_t *p8; uint32_t *p32; float *pf;
-    if ((rc = stage_in(eng->h_reads, hb->reads, hb->read_bytes, st, &p8))) return rc; db.reads = p8;
-    if ((rc = stage_in(eng->h_ro, hb->read_offsets, n, st, &p32))) return rc; db.read_offsets = p32;
-    if ((rc = stage_in(eng->h_rl, hb->read_lens, n, st, &p32))) return rc; db.read_lens = p32;
-    if ((rc = stage_in(eng->h_qm, hb->qm, hb->read_bytes, st, &pf))) return rc; db.qm = pf;
-    if ((rc = stage_in(eng->h_de, hb->delta, hb->read_bytes, st, &pf))) return rc; db.delta = pf;
-    if ((rc = stage_in(eng->h_xi, hb->xiksi, hb->read_bytes, st, &pf))) return rc; db.xiksi = pf;
-    if ((rc = stage_in(eng->h_al, hb->alpha, hb->read_bytes, st, &pf))) return rc; db.alpha = pf;
-    if ((rc = stage_in(eng->h_haps, hb->haps, hb->hap_bytes, st, &p8))) return rc; db.haps = p8;
-    if ((rc = stage_in(eng->h_ho, hb->hap_offsets, n, st, &p32))) return rc; db.hap_offsets = p32;
-    if ((rc = stage_in(eng->h_hl, hb->hap_lens, n, st, &p32))) return rc; db.hap_lens = p32;
+    gasalx_hmm_batch db;
+    int rc = hmm_stage_host(eng, hb, st, db);
+    if (rc) return rc;
     CK(eng->h_res.reserve((size_t)n * 4 + 16));
-    uint32_t mr = hb->max_read_len ? hb->max_read_len : host_max(hb->read_lens, n);
-    uint32_t mh = hb->max_hap_len ? hb->max_hap_len : host_max(hb->hap_lens, n);
-    rc = gx::pairhmm_device(eng->ws, db, eng->h_res.as<float>(), st, mr, mh);
+    rc = gx::pairhmm_device(eng->ws, db, eng->h_res.as<float>(), st, db.max_read_len, db.max_hap_len);
     if (rc) { (void)hipStreamSynchronize(st); return rc; }
     CK(hipMemcpyAsync(hres, eng->h_res.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
     CK(hipStreamSynchronize(st));
@@ -488,14 +501,16 @@ int gasalx_pairhmm_quals_device(gasalx_engine *eng, const gasalx_hmm_qual_batch 
     return gx::pairhmm_quals_device(eng->ws, *b, res, st, tab, nullptr, nullptr, 0, mr, mh);
 }
 
-int gasalx_pairhmm_quals_host(gasalx_engine *eng, const gasalx_hmm_qual_batch *hb, float *hres) {
-    if (!eng || !hmm_qual_batch_ok(hb) || !hres) { gx::set_error("null argument"); return GASALX_EINVAL; }
+namespace {
+// The fp32 pass of a host batch in quality form: pairs staged into the engine's device buffers
+// (db = the device image, max lengths filled in), run sorted by (read length, haplotype length)
+// in classes of reads that share a lane-group size, results in eng->h_res by pair index.
+// perm: the slot order, the caller's so that it outlives its copy (until the stream is synchronised).
+int quals_host_fp32(gasalx_engine *eng, const gasalx_hmm_qual_batch *hb, hipStream_t st, gasalx_hmm_qual_batch &db,
+                    const float **tab_out, std::vector<uint32_t> &perm) {
     const uint32_t n = hb->n_pairs;
-    if (n == 0) return GASALX_OK;
-    CK(hipSetDevice(eng->device));
-    hipStream_t st = eng->stream;
     // slots in (read length, haplotype length) order (tile_1.cu:180-195 operator<, :325)
-    std::vector<uint32_t> perm(n);
+    perm.resize(n);
     for (uint32_t i = 0; i < n; i++) perm[i] = i;
     std::stable_sort(perm.begin(), perm.end(), [&](uint32_t x, uint32_t y) {
         const uint32_t rx = hb->read_lens[x], ry = hb->read_lens[y];
@@ -503,6 +518,7 @@ int gasalx_pairhmm_quals_host(gasalx_engine *eng, const gasalx_hmm_qual_batch *h
     });
     // classes: runs of slots whose reads need the same lane-group size
     std::vector<gx::HmmClass> classes;
+    uint32_t mr = 0, mh = 0;
     for (uint32_t s = 0; s < n; s++) {
         const uint32_t r = hb->read_lens[perm[s]], h = hb->hap_lens[perm[s]];
         const int g = gx::pairhmm_group(r);
@@ -511,8 +527,12 @@ int gasalx_pairhmm_quals_host(gasalx_engine *eng, const gasalx_hmm_qual_batch *h
         c.slot1 = s + 1;
         c.max_r = std::max(c.max_r, r);
         c.max_h = std::max(c.max_h, h);
+        mr = std::max(mr, r);
+        mh = std::max(mh, h);
     }
-    gasalx_hmm_qual_batch db = *hb;
+    db = *hb;
+    db.max_read_len = mr;
+    db.max_hap_len = mh;
     int rc;
     uint8_t *p8; uint32_t *p32;
     if ((rc = stage_in(eng->h_reads, hb->reads, hb->read_bytes, st, &p8))) return rc; db.reads = p8;
@@ -527,14 +547,206 @@ int gasalx_pairhmm_quals_host(gasalx_engine *eng, const gasalx_hmm_qual_batch *h
     uint32_t *dperm;
     if ((rc = stage_in(eng->h_perm, perm.data(), n, st, &dperm))) return rc;
     CK(eng->h_res.reserve((size_t)n * 4 + 16));
-    const float *tab;
-    if ((rc = ph2pr_device(eng, &tab))) return rc;
-    rc = gx::pairhmm_quals_device(eng->ws, db, eng->h_res.as<float>(), st, tab, dperm, classes.data(),
+    if ((rc = ph2pr_device(eng, tab_out))) return rc;
+    rc = gx::pairhmm_quals_device(eng->ws, db, eng->h_res.as<float>(), st, *tab_out, dperm, classes.data(),
                                   (int)classes.size(), 0, 0);
-    if (rc) { (void)hipStreamSynchronize(st); return rc; }
+    if (rc) (void)hipStreamSynchronize(st);
+    return rc;
+}
+}  // namespace
+
+int gasalx_pairhmm_quals_host(gasalx_engine *eng, const gasalx_hmm_qual_batch *hb, float *hres) {
+    if (!eng || !hmm_qual_batch_ok(hb) || !hres) { gx::set_error("null argument"); return GASALX_EINVAL; }
+    const uint32_t n = hb->n_pairs;
+    if (n == 0) return GASALX_OK;
+    CK(hipSetDevice(eng->device));
+    hipStream_t st = eng->stream;
+    gasalx_hmm_qual_batch db;
+    const float *tab;
+    std::vector<uint32_t> perm;
+    int rc = quals_host_fp32(eng, hb, st, db, &tab, perm);
+    if (rc) return rc;
     CK(hipMemcpyAsync(hres, eng->h_res.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
     CK(hipStreamSynchronize(st));
     return GASALX_OK;
+}
+
+// ---- PairHMM in float64 and the log10 entry points (pairhmm64.hip) ----
+namespace {
+
+// max lengths of a device batch: the caller's, or read back (synchronises st)
+int hmm_lens(gasalx_engine *eng, const uint32_t *rl, const uint32_t *hl, uint32_t n, hipStream_t st, uint32_t *mr,
+             uint32_t *mh) {
+    if ((!*mr || !*mh) && n) return device_max_lens(eng, rl, hl, n, st, mr, mh);
+    return GASALX_OK;
+}
+
+// The rescue pass after an fp32 pass whose results are at r32 (device): scratch from the engine.
+int log10_rescue(gasalx_engine *eng, const gx::Hmm64Src &src, uint32_t n, const float *r32, float min_accepted,
+                 double *out, uint8_t *used, hipStream_t st, uint32_t mr, uint32_t mh) {
+    CK(eng->hm_list.reserve(((size_t)n + 4) * 4));
+    uint32_t *count = eng->hm_list.as<uint32_t>();
+    return gx::pairhmm_log10_device(src, n, r32, min_accepted, out, used, count, count + 4, st, mr, mh);
+}
+
+// Host forms: device outputs in eng->h_res64 / h_used, copied back with the count.
+int log10_host_finish(gasalx_engine *eng, const gx::Hmm64Src &src, uint32_t n, float min_accepted, double *hlog,
+                      uint8_t *hused, uint32_t *n_rescued, hipStream_t st, uint32_t mr, uint32_t mh) {
+    CK(eng->h_res64.reserve((size_t)n * 8 + 16));
+    CK(eng->h_used.reserve((size_t)n + 16));
+    int rc = log10_rescue(eng, src, n, eng->h_res.as<float>(), min_accepted, eng->h_res64.as<double>(),
+                          hused ? eng->h_used.as<uint8_t>() : nullptr, st, mr, mh);
+    if (rc) { (void)hipStreamSynchronize(st); return rc; }
+    CK(hipMemcpyAsync(hlog, eng->h_res64.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    if (hused) CK(hipMemcpyAsync(hused, eng->h_used.p, (size_t)n, hipMemcpyDeviceToHost, st));
+    uint32_t cnt = 0;
+    CK(hipMemcpyAsync(&cnt, eng->hm_list.p, 4, hipMemcpyDeviceToHost, st));
+    CK(hipStreamSynchronize(st));
+    if (n_rescued) *n_rescued = cnt;
+    return GASALX_OK;
+}
+
+}  // namespace
+
+int gasalx_pairhmm64_device(gasalx_engine *eng, const gasalx_hmm_batch *b, double *res, void *stream) {
+    if (!eng || !b || !res) { gx::set_error("null argument"); return GASALX_EINVAL; }
+    CK(hipSetDevice(eng->device));
+    hipStream_t st = stream ? (hipStream_t)stream : eng->stream;
+    uint32_t mr = b->max_read_len, mh = b->max_hap_len;
+    int rc = hmm_lens(eng, b->read_lens, b->hap_lens, b->n_pairs, st, &mr, &mh);
+    if (rc) return rc;
+    return gx::pairhmm64_device(gx::Hmm64Src{b, nullptr, nullptr}, b->n_pairs, res, st, mr, mh);
+}
+
+int gasalx_pairhmm64_host(gasalx_engine *eng, const gasalx_hmm_batch *hb, double *hres) {
+    if (!eng || !hb || !hres) { gx::set_error("null argument"); return GASALX_EINVAL; }
+    CK(hipSetDevice(eng->device));
+    hipStream_t st = eng->stream;
+    const uint32_t n = hb->n_pairs;
+    if (n == 0) return GASALX_OK;
+    gasalx_hmm_batch db;
+    int rc = hmm_stage_host(eng, hb, st, db);
+    if (rc) return rc;
+    CK(eng->h_res64.reserve((size_t)n * 8 + 16));
+    rc = gx::pairhmm64_device(gx::Hmm64Src{&db, nullptr, nullptr}, n, eng->h_res64.as<double>(), st, db.max_read_len,
+                              db.max_hap_len);
+    if (rc) { (void)hipStreamSynchronize(st); return rc; }
+    CK(hipMemcpyAsync(hres, eng->h_res64.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    CK(hipStreamSynchronize(st));
+    return GASALX_OK;
+}
+
+int gasalx_pairhmm64_quals_device(gasalx_engine *eng, const gasalx_hmm_qual_batch *b, double *res, void *stream) {
+    if (!eng || !hmm_qual_batch_ok(b) || !res) { gx::set_error("null argument"); return GASALX_EINVAL; }
+    CK(hipSetDevice(eng->device));
+    hipStream_t st = stream ? (hipStream_t)stream : eng->stream;
+    uint32_t mr = b->max_read_len, mh = b->max_hap_len;
+    int rc = hmm_lens(eng, b->read_lens, b->hap_lens, b->n_pairs, st, &mr, &mh);
+    if (rc) return rc;
+    const float *tab;
+    if ((rc = ph2pr_device(eng, &tab))) return rc;
+    return gx::pairhmm64_device(gx::Hmm64Src{nullptr, b, tab}, b->n_pairs, res, st, mr, mh);
+}
+
+int gasalx_pairhmm64_quals_host(gasalx_engine *eng, const gasalx_hmm_qual_batch *hb, double *hres) {
+    if (!eng || !hmm_qual_batch_ok(hb) || !hres) { gx::set_error("null argument"); return GASALX_EINVAL; }
+    const uint32_t n = hb->n_pairs;
+    if (n == 0) return GASALX_OK;
+    CK(hipSetDevice(eng->device));
+    hipStream_t st = eng->stream;
+    gasalx_hmm_qual_batch db = *hb;
+    int rc;
+    uint8_t *p8; uint32_t *p32;
+    if ((rc = stage_in(eng->h_reads, hb->reads, hb->read_bytes, st, &p8))) return rc; db.reads = p8;
+    if ((rc = stage_in(eng->h_bq, hb->base_quals, hb->read_bytes, st, &p8))) return rc; db.base_quals = p8;
+    if ((rc = stage_in(eng->h_iq, hb->ins_quals, hb->read_bytes, st, &p8))) return rc; db.ins_quals = p8;
+    if ((rc = stage_in(eng->h_dq, hb->del_quals, hb->read_bytes, st, &p8))) return rc; db.del_quals = p8;
+    if ((rc = stage_in(eng->h_ro, hb->read_offsets, n, st, &p32))) return rc; db.read_offsets = p32;
+    if ((rc = stage_in(eng->h_rl, hb->read_lens, n, st, &p32))) return rc; db.read_lens = p32;
+    if ((rc = stage_in(eng->h_haps, hb->haps, hb->hap_bytes, st, &p8))) return rc; db.haps = p8;
+    if ((rc = stage_in(eng->h_ho, hb->hap_offsets, n, st, &p32))) return rc; db.hap_offsets = p32;
+    if ((rc = stage_in(eng->h_hl, hb->hap_lens, n, st, &p32))) return rc; db.hap_lens = p32;
+    const float *tab;
+    if ((rc = ph2pr_device(eng, &tab))) return rc;
+    CK(eng->h_res64.reserve((size_t)n * 8 + 16));
+    // one launch sized by the longest read, as the parameter form's
+    rc = gx::pairhmm64_device(gx::Hmm64Src{nullptr, &db, tab}, n, eng->h_res64.as<double>(), st,
+                              host_max(hb->read_lens, n), host_max(hb->hap_lens, n));
+    if (rc) { (void)hipStreamSynchronize(st); return rc; }
+    CK(hipMemcpyAsync(hres, eng->h_res64.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    CK(hipStreamSynchronize(st));
+    return GASALX_OK;
+}
+
+int gasalx_pairhmm_log10_device(gasalx_engine *eng, const gasalx_hmm_batch *b, float min_accepted, double *dlog,
+                                uint8_t *dused, void *stream) {
+    if (!eng || !b || !dlog) { gx::set_error("null argument"); return GASALX_EINVAL; }
+    const uint32_t n = b->n_pairs;
+    if (n == 0) return GASALX_OK;
+    CK(hipSetDevice(eng->device));
+    hipStream_t st = stream ? (hipStream_t)stream : eng->stream;
+    uint32_t mr = b->max_read_len, mh = b->max_hap_len;
+    int rc = hmm_lens(eng, b->read_lens, b->hap_lens, n, st, &mr, &mh);
+    if (rc) return rc;
+    CK(eng->hm_r32.reserve((size_t)n * 4 + 16));
+    if ((rc = gx::pairhmm_device(eng->ws, *b, eng->hm_r32.as<float>(), st, mr, mh))) return rc;
+    return log10_rescue(eng, gx::Hmm64Src{b, nullptr, nullptr}, n, eng->hm_r32.as<float>(), min_accepted, dlog, dused,
+                        st, mr, mh);
+}
+
+int gasalx_pairhmm_log10_host(gasalx_engine *eng, const gasalx_hmm_batch *hb, float min_accepted, double *hlog,
+                              uint8_t *hused, uint32_t *n_rescued) {
+    if (!eng || !hb || !hlog) { gx::set_error("null argument"); return GASALX_EINVAL; }
+    if (n_rescued) *n_rescued = 0;
+    const uint32_t n = hb->n_pairs;
+    if (n == 0) return GASALX_OK;
+    CK(hipSetDevice(eng->device));
+    hipStream_t st = eng->stream;
+    gasalx_hmm_batch db;
+    int rc = hmm_stage_host(eng, hb, st, db);
+    if (rc) return rc;
+    CK(eng->h_res.reserve((size_t)n * 4 + 16));
+    rc = gx::pairhmm_device(eng->ws, db, eng->h_res.as<float>(), st, db.max_read_len, db.max_hap_len);
+    if (rc) { (void)hipStreamSynchronize(st); return rc; }
+    return log10_host_finish(eng, gx::Hmm64Src{&db, nullptr, nullptr}, n, min_accepted, hlog, hused, n_rescued, st,
+                             db.max_read_len, db.max_hap_len);
+}
+
+int gasalx_pairhmm_quals_log10_device(gasalx_engine *eng, const gasalx_hmm_qual_batch *b, float min_accepted,
+                                      double *dlog, uint8_t *dused, void *stream) {
+    if (!eng || !hmm_qual_batch_ok(b) || !dlog) { gx::set_error("null argument"); return GASALX_EINVAL; }
+    const uint32_t n = b->n_pairs;
+    if (n == 0) return GASALX_OK;
+    CK(hipSetDevice(eng->device));
+    hipStream_t st = stream ? (hipStream_t)stream : eng->stream;
+    uint32_t mr = b->max_read_len, mh = b->max_hap_len;
+    int rc = hmm_lens(eng, b->read_lens, b->hap_lens, n, st, &mr, &mh);
+    if (rc) return rc;
+    const float *tab;
+    if ((rc = ph2pr_device(eng, &tab))) return rc;
+    CK(eng->hm_r32.reserve((size_t)n * 4 + 16));
+    if ((rc = gx::pairhmm_quals_device(eng->ws, *b, eng->hm_r32.as<float>(), st, tab, nullptr, nullptr, 0, mr, mh)))
+        return rc;
+    return log10_rescue(eng, gx::Hmm64Src{nullptr, b, tab}, n, eng->hm_r32.as<float>(), min_accepted, dlog, dused, st,
+                        mr, mh);
+}
+
+int gasalx_pairhmm_quals_log10_host(gasalx_engine *eng, const gasalx_hmm_qual_batch *hb, float min_accepted,
+                                    double *hlog, uint8_t *hused, uint32_t *n_rescued) {
+    if (!eng || !hmm_qual_batch_ok(hb) || !hlog) { gx::set_error("null argument"); return GASALX_EINVAL; }
+    if (n_rescued) *n_rescued = 0;
+    const uint32_t n = hb->n_pairs;
+    if (n == 0) return GASALX_OK;
+    CK(hipSetDevice(eng->device));
+    hipStream_t st = eng->stream;
+    gasalx_hmm_qual_batch db;
+    const float *tab;
+    std::vector<uint32_t> perm;
+    int rc = quals_host_fp32(eng, hb, st, db, &tab, perm);
+    if (rc) return rc;
+    // the rescue pass: one launch over the list, sized by the batch's longest read
+    return log10_host_finish(eng, gx::Hmm64Src{nullptr, &db, tab}, n, min_accepted, hlog, hused, n_rescued, st,
+                             db.max_read_len, db.max_hap_len);
 }
 
 namespace {

@@ -133,6 +133,25 @@ int pairhmm_quals_device(Workspace &ws, const gasalx_hmm_qual_batch &b, float *r
                          const float *ph2pr_dev, const uint32_t *perm, const HmmClass *classes, int n_classes,
                          uint32_t max_r, uint32_t max_h);
 
+// PairHMM in float64 (pairhmm64.hip, pairhmm64.hpp).  The pairs come in either input form:
+// quals (with ph2pr, the 128-entry device table) when set, otherwise params.
+struct Hmm64Src {
+    const gasalx_hmm_batch *params;
+    const gasalx_hmm_qual_batch *quals;
+    const float *ph2pr;
+};
+// lanes per pair and read rows per lane for reads of up to max_r rows (0: longer than 512)
+int pairhmm64_shape(uint32_t max_r, int *rows);
+// the raw forward value of every pair, initial constant 2^1020
+int pairhmm64_device(const Hmm64Src &src, uint32_t n, double *result, hipStream_t stream, uint32_t max_r,
+                     uint32_t max_h);
+// log10 likelihoods from the fp32 results r32: accepted pairs (r >= min_accepted, <= 0: 1e-28f,
+// and finite) directly, the others recomputed in float64.  count (one word) and list (n words)
+// are device scratch; count holds the number of rescued pairs afterwards.  No host round trip.
+int pairhmm_log10_device(const Hmm64Src &src, uint32_t n, const float *r32, float min_accepted, double *out,
+                         uint8_t *used, uint32_t *count, uint32_t *list, hipStream_t stream, uint32_t max_r,
+                         uint32_t max_h);
+
 // nvbio-style batched scoring (batched.hip, nvbio.hpp)
 int nv_score_device(const gasalx_nv_aligner &al, uint32_t n, const gasalx_nv_strings &pat,
                     const gasalx_nv_strings &txt, int32_t *scores, int16_t *scores16, uint32_t max_p, uint32_t max_t,

@@ -40,6 +40,9 @@ EXPORTS = (
     "gasalx_shard_bounds", "gasalx_multi_align_host", "gasalx_multi_pairhmm_host",
     "gasalx_multi_pairhmm_quals_host", "gasalx_multi_allgather", "gasalx_packed_pairs",
     "gasalx_multi_align_device", "gasalx_multi_pairhmm_device",
+    "gasalx_pairhmm64_device", "gasalx_pairhmm64_host", "gasalx_pairhmm64_quals_device",
+    "gasalx_pairhmm64_quals_host", "gasalx_pairhmm_log10_device", "gasalx_pairhmm_log10_host",
+    "gasalx_pairhmm_quals_log10_device", "gasalx_pairhmm_quals_log10_host",
 )
 MULTI_RCCL = 1
 
@@ -338,17 +341,58 @@ class Engine:
         _check(lib().gasalx_align_device(self._h, ctypes.byref(params), ctypes.byref(cb), ctypes.byref(cr),
                                          ctypes.c_void_p(stream or None)), "align_device")
 
-    def pairhmm_host(self, reads, read_off, read_len, qm, delta, xiksi, alpha, haps, hap_off, hap_len):
+    @staticmethod
+    def _hmm_batch(reads, read_off, read_len, qm, delta, xiksi, alpha, haps, hap_off, hap_len):
+        """(CHmmBatch over host arrays, the arrays it points into, n)"""
         c = lambda a, t: np.ascontiguousarray(a, t)
         reads, haps = c(reads, np.uint8), c(haps, np.uint8)
         arrs = [c(read_off, np.uint32), c(read_len, np.uint32), c(qm, np.float32), c(delta, np.float32),
                 c(xiksi, np.float32), c(alpha, np.float32), c(hap_off, np.uint32), c(hap_len, np.uint32)]
         n = len(arrs[1])
-        res = np.zeros(n, np.float32)
         hb = CHmmBatch(_p(reads), _p(arrs[0]), _p(arrs[1]), _p(arrs[2]), _p(arrs[3]), _p(arrs[4]), _p(arrs[5]),
                        _p(haps), _p(arrs[6]), _p(arrs[7]), len(reads), len(haps), n, 0, 0)
+        return hb, (reads, haps, arrs), n
+
+    def pairhmm_host(self, reads, read_off, read_len, qm, delta, xiksi, alpha, haps, hap_off, hap_len):
+        hb, _keep, n = self._hmm_batch(reads, read_off, read_len, qm, delta, xiksi, alpha, haps, hap_off, hap_len)
+        res = np.zeros(n, np.float32)
         _check(lib().gasalx_pairhmm_host(self._h, ctypes.byref(hb), _p(res)), "pairhmm_host")
         return res
+
+    def pairhmm64_host(self, reads, read_off, read_len, qm, delta, xiksi, alpha, haps, hap_off, hap_len):
+        """The float64 forward value of every pair, initial constant 2**1020 (gasalx_pairhmm64_host)."""
+        hb, _keep, n = self._hmm_batch(reads, read_off, read_len, qm, delta, xiksi, alpha, haps, hap_off, hap_len)
+        res = np.zeros(n, np.float64)
+        _check(lib().gasalx_pairhmm64_host(self._h, ctypes.byref(hb), _p(res)), "pairhmm64_host")
+        return res
+
+    def pairhmm64_quals_host(self, hmm: "HmmData"):
+        """pairhmm64_host from Phred qualities (gasalx_pairhmm64_quals_host)."""
+        res = np.zeros(hmm.n, np.float64)
+        hb = hmm.cstruct()
+        _check(lib().gasalx_pairhmm64_quals_host(self._h, ctypes.byref(hb), _p(res)), "pairhmm64_quals_host")
+        return res
+
+    def pairhmm_log10_host(self, reads, read_off, read_len, qm, delta, xiksi, alpha, haps, hap_off, hap_len,
+                           min_accepted=0.0):
+        """log10 likelihoods (gasalx_pairhmm_log10_host): the fp32 pass, pairs below min_accepted
+        (<= 0: 1e-28) recomputed in float64.  Returns (log10, used_double); the number of rescued
+        pairs is used_double.sum() and is kept in self.n_rescued as the library reported it."""
+        hb, _keep, n = self._hmm_batch(reads, read_off, read_len, qm, delta, xiksi, alpha, haps, hap_off, hap_len)
+        res, used, cnt = np.zeros(n, np.float64), np.zeros(n, np.uint8), ctypes.c_uint32(0)
+        _check(lib().gasalx_pairhmm_log10_host(self._h, ctypes.byref(hb), ctypes.c_float(min_accepted), _p(res),
+                                               _p(used), ctypes.byref(cnt)), "pairhmm_log10_host")
+        self.n_rescued = cnt.value
+        return res, used
+
+    def pairhmm_quals_log10_host(self, hmm: "HmmData", min_accepted=0.0):
+        """pairhmm_log10_host from Phred qualities; the fp32 pass runs in sorted length classes."""
+        res, used, cnt = np.zeros(hmm.n, np.float64), np.zeros(hmm.n, np.uint8), ctypes.c_uint32(0)
+        hb = hmm.cstruct()
+        _check(lib().gasalx_pairhmm_quals_log10_host(self._h, ctypes.byref(hb), ctypes.c_float(min_accepted), _p(res),
+                                                     _p(used), ctypes.byref(cnt)), "pairhmm_quals_log10_host")
+        self.n_rescued = cnt.value
+        return res, used
 
     def pairhmm_quals_host(self, hmm: "HmmData"):
         """PairHMM from Phred qualities (the reference's input files): sorted by length,
@@ -490,6 +534,26 @@ class Engine:
                        g("haps"), g("hap_offsets"), g("hap_lens"), read_bytes, hap_bytes, n, max_r, max_h)
         _check(lib().gasalx_pairhmm_device(self._h, ctypes.byref(hb), ctypes.c_void_p(result_ptr),
                                            ctypes.c_void_p(stream or None)), "pairhmm_device")
+
+    def pairhmm_log10_device_ptrs(self, ptrs: dict, read_bytes: int, hap_bytes: int, n: int, max_r: int, max_h: int,
+                                  log10_ptr: int, used_ptr: int = 0, min_accepted: float = 0.0, stream: int = 0):
+        """gasalx_pairhmm_log10_device over device addresses (pairhmm_device_ptrs' arrays): n doubles
+        at log10_ptr, n bytes at used_ptr (0: not wanted); asynchronous on the stream."""
+        g = lambda k: ptrs.get(k) or None
+        hb = CHmmBatch(g("reads"), g("read_offsets"), g("read_lens"), g("qm"), g("delta"), g("xiksi"), g("alpha"),
+                       g("haps"), g("hap_offsets"), g("hap_lens"), read_bytes, hap_bytes, n, max_r, max_h)
+        _check(lib().gasalx_pairhmm_log10_device(self._h, ctypes.byref(hb), ctypes.c_float(min_accepted),
+                                                 ctypes.c_void_p(log10_ptr), ctypes.c_void_p(used_ptr or None),
+                                                 ctypes.c_void_p(stream or None)), "pairhmm_log10_device")
+
+    def pairhmm64_device_ptrs(self, ptrs: dict, read_bytes: int, hap_bytes: int, n: int, max_r: int, max_h: int,
+                              result_ptr: int, stream: int = 0):
+        """gasalx_pairhmm64_device over device addresses: n doubles at result_ptr."""
+        g = lambda k: ptrs.get(k) or None
+        hb = CHmmBatch(g("reads"), g("read_offsets"), g("read_lens"), g("qm"), g("delta"), g("xiksi"), g("alpha"),
+                       g("haps"), g("hap_offsets"), g("hap_lens"), read_bytes, hap_bytes, n, max_r, max_h)
+        _check(lib().gasalx_pairhmm64_device(self._h, ctypes.byref(hb), ctypes.c_void_p(result_ptr),
+                                             ctypes.c_void_p(stream or None)), "pairhmm64_device")
 
 
 def shard_bounds(a, b, world: int) -> list:

@@ -197,6 +197,33 @@ int gasalx_pairhmm_quals_device(gasalx_engine *eng, const gasalx_hmm_qual_batch 
  * reference's 32-pair interleaved chunks (tile_1.cu:346-500). */
 int gasalx_pairhmm_quals_host(gasalx_engine *eng, const gasalx_hmm_qual_batch *host_batch, float *host_result);
 
+/* PairHMM in float64.  The fp32 entry points above start from the constant 2^120 and return 0
+ * for a read that fits its haplotype badly (the value underflows the fp32 range).  These run the
+ * same recurrence on the same fp32 inputs, widened, in double from the constant 2^1020.
+ *
+ * raw float64 forward value of every pair, initial constant 2^1020 */
+int gasalx_pairhmm64_device(gasalx_engine *eng, const gasalx_hmm_batch *dev_batch, double *dev_result, void *stream);
+int gasalx_pairhmm64_host(gasalx_engine *eng, const gasalx_hmm_batch *host_batch, double *host_result);
+int gasalx_pairhmm64_quals_device(gasalx_engine *eng, const gasalx_hmm_qual_batch *dev_batch, double *dev_result,
+                                  void *stream);
+int gasalx_pairhmm64_quals_host(gasalx_engine *eng, const gasalx_hmm_qual_batch *host_batch, double *host_result);
+
+/* log10 likelihoods: fp32 pass, pairs below min_accepted (<= 0: 1e-28f) rescued in float64.
+ * Output i is log10(value) - log10(initial constant) of pair i: log10(r) - 120 log10(2) from
+ * an accepted fp32 result, log10(r64) - 1020 log10(2) from a rescued pair.
+ * An fp32 result that is 0, denormal, infinite or NaN is rescued whatever min_accepted is.
+ * used_double (may be NULL): 1 per rescued pair.  n_rescued (may be NULL, host form only).
+ * The device forms stay asynchronous on the stream when max_read_len / max_hap_len are set:
+ * the rescue list and its length stay on the device. */
+int gasalx_pairhmm_log10_device(gasalx_engine *eng, const gasalx_hmm_batch *dev_batch, float min_accepted,
+                                double *dev_log10, uint8_t *dev_used_double, void *stream);
+int gasalx_pairhmm_log10_host(gasalx_engine *eng, const gasalx_hmm_batch *host_batch, float min_accepted,
+                              double *host_log10, uint8_t *host_used_double, uint32_t *n_rescued);
+int gasalx_pairhmm_quals_log10_device(gasalx_engine *eng, const gasalx_hmm_qual_batch *dev_batch, float min_accepted,
+                                      double *dev_log10, uint8_t *dev_used_double, void *stream);
+int gasalx_pairhmm_quals_log10_host(gasalx_engine *eng, const gasalx_hmm_qual_batch *host_batch, float min_accepted,
+                                    double *host_log10, uint8_t *host_used_double, uint32_t *n_rescued);
+
 /* Reader of the reference's PairHMM input files: groups of `size` pairs, each pair
  * = read length, read bases, then read-length base / insertion / deletion / gcp
  * qualities, haplotype length, haplotype bases (whitespace-separated, fscanf

@@ -1,7 +1,7 @@
 // pairhmm_prog.cpp — command-line driver of the PairHMM path with the reference
 // drivers' contract, as a client of the flat C-ABI only (include/gasalx.h, -lgasal).
 //
-//   pairhmm_prog [-fakesize N] [-print all|first|last|none] input.txt
+//   pairhmm_prog [-fakesize N] [-print all|first|last|none] [-log10] input.txt
 //
 // * input.txt: the reference's input format (groups of `size` pairs; read, base /
 //   insertion / deletion / gcp qualities, haplotype), parsed by gasalx_hmm_file_read
@@ -17,6 +17,10 @@
 //   which (default first).  Then the timing line and "GCUPS: %lf" computed as the
 //   reference does, from the last pair's read and haplotype lengths times the batch
 //   size (tile_1.cu:552-553).
+// * -log10: the batch runs through gasalx_pairhmm_quals_log10_host instead and the result
+//   lines carry log10(likelihood) as "%.9g" (the form the reference's real-data drivers
+//   print, improved_warp_based.cu:196,418, with pairs the fp32 pass cannot represent
+//   recomputed in float64); a last line reads "rescued: K of N".
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -41,15 +45,17 @@ static int die(const char *what, int rc) {
 int main(int argc, char **argv) {
     long fakesize = 0;
     std::string print = "first";
+    bool log10_out = false;
     const char *path = nullptr;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "-fakesize") && i + 1 < argc) fakesize = atol(argv[++i]);
         else if (!strcmp(argv[i], "-print") && i + 1 < argc) print = argv[++i];
+        else if (!strcmp(argv[i], "-log10")) log10_out = true;
         else if (argv[i][0] == '-') { fprintf(stderr, "unknown option %s\n", argv[i]); return 1; }
         else path = argv[i];
     }
     if (!path) {
-        fprintf(stderr, "usage: pairhmm_prog [-fakesize N] [-print all|first|last|none] input.txt\n");
+        fprintf(stderr, "usage: pairhmm_prog [-fakesize N] [-print all|first|last|none] [-log10] input.txt\n");
         return 1;
     }
     double t0 = now();
@@ -61,7 +67,7 @@ int main(int argc, char **argv) {
     if ((rc = gasalx_engine_create(0, &eng))) return die("gasalx_engine_create", rc);
 
     double compute = 0, read_read = 0, hap_hap = 0;
-    uint64_t last_batch = 0;
+    uint64_t last_batch = 0, rescued = 0, total = 0;
     uint32_t first = 0;
     for (uint32_t g = 0; g < f->n_groups; g++) {
         const uint32_t size = f->group_sizes[g];
@@ -85,14 +91,26 @@ int main(int argc, char **argv) {
         b.base_quals = f->base_quals; b.ins_quals = f->ins_quals; b.del_quals = f->del_quals;
         b.haps = f->haps; b.hap_offsets = ho.data(); b.hap_lens = hl.data();
         b.read_bytes = f->read_bytes; b.hap_bytes = f->hap_bytes;
-        std::vector<float> res(b.n_pairs);
+        std::vector<float> res(log10_out ? 0 : b.n_pairs);
+        std::vector<double> lres(log10_out ? b.n_pairs : 0);
         const double t1 = now();
-        if ((rc = gasalx_pairhmm_quals_host(eng, &b, res.data()))) return die("gasalx_pairhmm_quals_host", rc);
+        if (log10_out) {
+            uint32_t k = 0;
+            if ((rc = gasalx_pairhmm_quals_log10_host(eng, &b, 0.f, lres.data(), nullptr, &k)))
+                return die("gasalx_pairhmm_quals_log10_host", rc);
+            rescued += k;
+            total += b.n_pairs;
+        } else if ((rc = gasalx_pairhmm_quals_host(eng, &b, res.data()))) return die("gasalx_pairhmm_quals_host", rc);
         compute += now() - t1;
         read_read = rl.back();
         hap_hap = hl.back();
         last_batch = b.n_pairs;
-        if (print == "all")
+        if (log10_out) {
+            if (print == "all")
+                for (uint32_t i = 0; i < b.n_pairs; i++) printf("  i=%u  %.9g\n", i, lres[i]);
+            else if (print == "first") printf("  i=%d  %.9g\n", 0, lres[0]);
+            else if (print == "last") printf("  i=%u  %.9g\n", b.n_pairs - 1, lres[b.n_pairs - 1]);
+        } else if (print == "all")
             for (uint32_t i = 0; i < b.n_pairs; i++) printf("  i=%u  %e\n", i, res[i]);
         else if (print == "first") printf("  i=%d  %e\n", 0, res[0]);
         else if (print == "last") printf("  i=%u  %e\n", b.n_pairs - 1, res[b.n_pairs - 1]);
@@ -101,6 +119,7 @@ int main(int argc, char **argv) {
     printf("read_time=%e  initial_time=%e  computation_time= %e total_time=%e\n", read_time, 0.0, compute,
            now() - t0);
     printf("GCUPS: %lf \n", compute > 0 ? (double)last_batch * read_read * hap_hap / compute / 1e9 : 0.0);
+    if (log10_out) printf("rescued: %llu of %llu\n", (unsigned long long)rescued, (unsigned long long)total);
     gasalx_engine_destroy(eng);
     gasalx_hmm_file_free(f);
     return 0;
