@@ -64,8 +64,7 @@ size_t nv16_lds(bool shared, uint32_t max_t, int G) {
 // score magnitude) inside the 16-bit f16 window.  GASALX_NV16=0: int32 only.
 bool nv16_ok(int aligner, int type, int32_t match, int32_t mismatch, int32_t go, int32_t ge, int32_t del, int32_t ins,
              bool shared_text, uint32_t text_bits, uint32_t max_p, uint32_t max_t, uint32_t *base) {
-    const char *env = std::getenv("GASALX_NV16");
-    if (env && std::atoi(env) == 0) return false;
+    if (!env_flag("GASALX_NV16", true)) return false;
     (void)shared_text;
     if (text_bits != 2) return false;
     if (match < mismatch || match - mismatch > 255) return false;
@@ -259,8 +258,7 @@ NvBand16Fn nv_band16_lookup_t(int type, uint32_t band) {
 // window (as nv16_ok); GASALX_NVB16=0: int32 only
 bool nvb16_ok(int32_t match, int32_t mismatch, int32_t go, int32_t ge, int32_t del, int32_t ins, uint32_t text_bits,
               uint32_t max_p, uint32_t band, uint32_t *base) {
-    const char *env = std::getenv("GASALX_NVB16");
-    if (env && std::atoi(env) == 0) return false;
+    if (!env_flag("GASALX_NVB16", true)) return false;
     if (text_bits != 2) return false;
     if (match < mismatch || match - mismatch > 255) return false;
     if (go > 0 || ge > 0 || del > 0 || ins > 0) return false;

@@ -44,34 +44,27 @@ void Workspace::release_all() {
 }
 
 // ----------------------------------------------------------------------------
-// (G lanes per pair, R rows per lane) shapes: query rows covered = G*R.
+// the planner's shape lists, smallest first (wavefront16.hpp GX_SHAPES_R4 / GX_SHAPES_PK)
 struct Shape { int G, R; };
-static const Shape kShapes[] = {{8, 8}, {8, 12}, {8, 16}, {8, 20}, {16, 16}, {16, 20}, {32, 20}, {64, 20}};
-// packed kernels (register axis = query for LOCAL/GLOBAL, target for SEMI):
-// R = 19 fits 150 bp (152 padded) and R = 23 fits 182 bp (184 padded) exactly
-// G = 16/32/64 shapes with few rows per lane serve small batches (make_plan)
-static const Shape kShapes16[] = {{8, 8},   {8, 12},  {8, 16},  {8, 19},  {8, 20},  {8, 23},  {16, 10}, {16, 12},
-                                  {16, 16}, {16, 20}, {32, 5},  {32, 6},  {32, 9},  {32, 20}, {64, 3},  {64, 5},
-                                  {64, 20}};
+#define GX_SHAPE(g, r) {g, r},
+static const Shape kShapes[] = {GX_SHAPES_R4(GX_SHAPE)};
+static const Shape kShapes16[] = {GX_SHAPES_PK(GX_SHAPE)};
+#undef GX_SHAPE
 
 using WfFn = void (*)(WfArgs);
 
+// the int32 kernel's instances (STOP: the SEMI TAIL=TARGET reverse pass, start.hpp)
+template <int ALGO, bool KEYS, bool TB, bool STOP = false>
+struct WfK {
+    template <int G, int R> static WfFn fn() { return &wf_kernel<ALGO, KEYS, TB, G, R, STOP>; }
+};
 template <int ALGO, bool KEYS, bool TB>
-static WfFn wf_pick(int G, int R) {
-#define GX_CASE(g, r) if (G == g && R == r) return &wf_kernel<ALGO, KEYS, TB, g, r>;
-    GX_CASE(8, 8) GX_CASE(8, 12) GX_CASE(8, 16) GX_CASE(8, 20)
-    GX_CASE(16, 16) GX_CASE(16, 20) GX_CASE(32, 20) GX_CASE(64, 20)
-#undef GX_CASE
-    return nullptr;
-}
-
-static WfFn wf_pick_stop(int G, int R) {   // SEMI TAIL=TARGET reverse pass (start.hpp)
-#define GX_CASE(g, r) if (G == g && R == r) return &wf_kernel<WF_SEMI, true, false, g, r, true>;
-    GX_CASE(8, 8) GX_CASE(8, 12) GX_CASE(8, 16) GX_CASE(8, 20)
-    GX_CASE(16, 16) GX_CASE(16, 20) GX_CASE(32, 20) GX_CASE(64, 20)
-#undef GX_CASE
-    return nullptr;
-}
+static WfFn wf_pick(int G, int R) { return pick_instance<WfK<ALGO, KEYS, TB>, SHAPES_R4>(G, R); }
+template <int ALGO>
+static WfFn wf16_pick(int G, int R) { return pick_instance<Wf16K<ALGO>, SHAPES_PK>(G, R); }
+// R % 4 == 0 shapes: the packed kernels that store in groups of 4 rows (traceback flags, band windows)
+template <int ALGO>
+static WfFn wf16_pick_r4(int G, int R) { return pick_instance<Wf16K<ALGO>, SHAPES_R4>(G, R); }
 
 static WfFn wf_lookup(int algo, bool keys, bool tb, int G, int R) {
     if (algo == WF_LOCAL) return tb ? wf_pick<WF_LOCAL, true, true>(G, R) : wf_pick<WF_LOCAL, true, false>(G, R);
@@ -79,56 +72,17 @@ static WfFn wf_lookup(int algo, bool keys, bool tb, int G, int R) {
     return keys ? wf_pick<WF_SEMI, true, false>(G, R) : wf_pick<WF_SEMI, false, false>(G, R);
 }
 
-template <int ALGO>
-static WfFn wf16_pick(int G, int R) {
-#define GX_CASE(g, r) if (G == g && R == r) return &wf16_kernel<ALGO, g, r>;
-    GX_CASE(8, 8) GX_CASE(8, 12) GX_CASE(8, 16) GX_CASE(8, 19) GX_CASE(8, 20) GX_CASE(8, 23)
-    GX_CASE(16, 10) GX_CASE(16, 12) GX_CASE(16, 16) GX_CASE(16, 20) GX_CASE(32, 5) GX_CASE(32, 6) GX_CASE(32, 9)
-    GX_CASE(32, 20) GX_CASE(64, 3) GX_CASE(64, 5) GX_CASE(64, 20)
-#undef GX_CASE
-    return nullptr;
-}
-
-static WfFn wf16_pick_tb(int G, int R) {   // R % 4 == 0 shapes (wavefront16.hpp store groups)
-#define GX_CASE(g, r) if (G == g && R == r) return &wf16_kernel<WF16_GLOBAL_TB, g, r>;
-    GX_CASE(8, 8) GX_CASE(8, 12) GX_CASE(8, 16) GX_CASE(8, 20)
-    GX_CASE(16, 16) GX_CASE(16, 20) GX_CASE(32, 20) GX_CASE(64, 20)
-#undef GX_CASE
-    return nullptr;
-}
-
-template <int ALGO>
-static WfFn wf16_pick_r4(int G, int R) {   // R % 4 == 0 shapes (band recomputation)
-#define GX_CASE(g, r) if (G == g && R == r) return &wf16_kernel<ALGO, g, r>;
-    GX_CASE(8, 8) GX_CASE(8, 12) GX_CASE(8, 16) GX_CASE(8, 20)
-    GX_CASE(16, 16) GX_CASE(16, 20) GX_CASE(32, 20) GX_CASE(64, 20)
-#undef GX_CASE
-    return nullptr;
-}
-
-static WfFn wf16_pick_local_tb(int G, int R) {   // R % 4 == 0 shapes
-#define GX_CASE(g, r) if (G == g && R == r) return &wf16_kernel<WF16_LOCAL_TB, g, r>;
-    GX_CASE(8, 8) GX_CASE(8, 12) GX_CASE(8, 16) GX_CASE(8, 20)
-    GX_CASE(16, 16) GX_CASE(16, 20) GX_CASE(32, 20) GX_CASE(64, 20)
-#undef GX_CASE
-    return nullptr;
-}
-
 static WfFn wf16_lookup(int algo, bool tb, int G, int R, bool key2 = false, bool stop = false, bool ku16 = false,
                         bool lrs = false, bool kseg = false, bool tbd = false) {
-    if (algo == WF_LOCAL) return tb ? (tbd ? (G == 16 && R == 12 ? &wf16_kernel<WF16_LOCAL_TBD, 16, 12>
-                                                                  : wf16_pick_r4<WF16_LOCAL_TBD>(G, R))
-                                           : wf16_pick_local_tb(G, R))
+    if (algo == WF_LOCAL) return tb ? (tbd ? wf16_pick_r4<WF16_LOCAL_TBD>(G, R) : wf16_pick_r4<WF16_LOCAL_TB>(G, R))
                                     : key2 ? wf16_pick<WF16_LOCAL_K2>(G, R)
                                                                : (ku16 || lrs || kseg) ? wf16_local_lookup(G, R, ku16, lrs, kseg)
                                                                                : wf16_pick<WF_LOCAL>(G, R);
-    if (algo == WF_GLOBAL) return tb ? wf16_pick_tb(G, R) : wf16_pick<WF_GLOBAL>(G, R);
+    if (algo == WF_GLOBAL) return tb ? wf16_pick_r4<WF16_GLOBAL_TB>(G, R) : wf16_pick<WF_GLOBAL>(G, R);
     return stop ? wf16_pick<WF16_SEMI_STOP>(G, R) : wf16_pick<WF_SEMI>(G, R);
 }
 
 static inline uint32_t pad8(uint32_t x) { return (x + 7u) & ~7u; }
-
-static bool env_flag(const char *name, bool dflt);
 
 // packed LOCAL with the round-2 keys H*256 + (255 - column): H <= 255, 512 columns (two key
 // sets above 256), 256 with traceback
@@ -222,23 +176,12 @@ static bool int16_safe(const gasalx_params &p, uint32_t mq, uint32_t mt) {
     return std::abs((int64_t)p.gap_open) + L * step < 30000;
 }
 
-// A/B switch: the environment variable, read as an integer, or `dflt` when unset
-static bool env_flag(const char *name, bool dflt) {
-    const char *e = std::getenv(name);
-    return e ? std::atoi(e) != 0 : dflt;
-}
-static int env_int(const char *name, int dflt) {
-    const char *e = std::getenv(name);
-    return e ? std::atoi(e) : dflt;
-}
-
 // Packed banded kernel (banded16.hpp): stored values B + [0, Hmax] and keys
 // H*8 + 7 + 0x400 inside [0x0400, 0x7BFF]; pads score -b, which needs an N score
 // <= 0.  GASALX_BAND16=0 keeps every pair on the int32 kernel (A/B runs).
 static uint32_t band16_base(const gasalx_params &p) { return 0x400u + (uint32_t)(p.gap_open + p.gap_extend + p.mismatch); }
 static bool band16_ok(const gasalx_params &p, uint32_t q8, uint32_t t8) {
-    const char *env = std::getenv("GASALX_BAND16");
-    if (env && std::atoi(env) == 0) return false;
+    if (!env_flag("GASALX_BAND16", true)) return false;
     if (p.match < 0 || p.mismatch < 0 || p.gap_open < 0 || p.gap_extend < 0) return false;
     if (p.match + p.mismatch > 255 || p.gap_open + p.gap_extend > 4096) return false;
     if (p.has_n_penalty && p.n_penalty < 0) return false;
@@ -255,8 +198,7 @@ static int32_t local16_sn(const gasalx_params &p) { return p.has_n_penalty ? -p.
 static uint32_t local16_k(const gasalx_params &p) { return (uint32_t)std::max({0, p.mismatch, -local16_sn(p)}); }
 static uint32_t local16_base(const gasalx_params &p) { return 0x400u + (uint32_t)(p.gap_open + p.gap_extend) + local16_k(p); }
 static bool local16_ok(const gasalx_params &p, uint32_t q8, uint32_t t8) {
-    const char *env = std::getenv("GASALX_LOCAL16");
-    if (env && std::atoi(env) == 0) return false;
+    if (!env_flag("GASALX_LOCAL16", true)) return false;
     if (p.match < 0 || p.gap_open < 0 || p.gap_extend < 0 || p.gap_open + p.gap_extend > 4096) return false;
     const int64_t k = local16_k(p), sn = local16_sn(p);
     if (p.match + k > 255 || k - p.mismatch > 255 || sn + k > 255) return false;
@@ -311,8 +253,7 @@ Plan make_plan(const gasalx_params &p, const BatchShape &s, bool has_ops) {
         pl.need_pack = has_ops;
         // GASALX_PACKED16=0: every block on the int32 kernel (A/B runs, the int32 probe of
         // bench.py --force-int32); read per call
-        const char *pk_env = std::getenv("GASALX_PACKED16");
-        pl.packed16 = !(pk_env && std::atoi(pk_env) == 0) && packed16_ok(p, wf_algo, s.max_q, s.max_t, &pl.vmin);
+        pl.packed16 = env_flag("GASALX_PACKED16", true) && packed16_ok(p, wf_algo, s.max_q, s.max_t, &pl.vmin);
         if (pl.packed16) {
             const uint32_t x8 = (wf_algo == WF_SEMI) ? t8 : q8, y8 = (wf_algo == WF_SEMI) ? q8 : t8;
             pl.G16 = 0;
@@ -320,21 +261,17 @@ Plan make_plan(const gasalx_params &p, const BatchShape &s, bool has_ops) {
             // waves per SIMD (128/G pairs per wave, 1024 SIMDs); traceback keeps G = 8 up
             // GASALX_GMIN: fixed minimum G (A/B runs, parity sweeps); read per call so a
             // test process can sweep it
-            const char *gmin_env = std::getenv("GASALX_GMIN");
-            const int gforce = gmin_env ? std::atoi(gmin_env) : 0;
+            const int gforce = env_int("GASALX_GMIN", 0);
             uint32_t gmin = 8;
             if (s.n && !pl.tb)
                 while (gmin < 64 && (uint64_t)s.n * gmin < 2048ull * 128) gmin *= 2;
             if (gforce > 0) gmin = (uint32_t)gforce;
             // traceback kernels store flags in groups of 4 rows and keep >= 16 rows per
-            // lane (their instances, wf16_pick_tb): the other shapes are never taken,
-            // forced or not -- except LOCAL+TB's G16R12 (3 waves per SIMD),
-            // taken under GASALX_LTBD_G16=1 for the A/B against the 2-wave G8R20
-            const bool ltbd16 = pl.tb && wf_algo == WF_LOCAL && env_flag("GASALX_LTBD_G16", false);
-            if (ltbd16) gmin = std::max<uint32_t>(gmin, 16);
+            // lane (their instances, wf16_pick_r4): the other shapes are never taken,
+            // forced or not
             for (const Shape &sh : kShapes16)
                 if ((uint32_t)sh.G >= gmin && (uint32_t)(sh.G * sh.R) >= x8 &&
-                    !(pl.tb && (sh.R % 4 || (sh.G > 8 && sh.R < 16)) && !(ltbd16 && sh.G == 16 && sh.R == 12))) {
+                    !(pl.tb && (sh.R % 4 || (sh.G > 8 && sh.R < 16)))) {
                     pl.G16 = sh.G; pl.R16 = sh.R;
                     break;
                 }
@@ -366,15 +303,14 @@ Plan make_plan(const gasalx_params &p, const BatchShape &s, bool has_ops) {
                 const bool frame = base + hmax + e * span + a + k + 64 <= 0x7BFF && base - 2 * e >= 0x400;
                 // past both, f16 keys by step segments of M = 2^m columns (WF16_LOCAL_SEG): (Hmax +
                 // 1) * M <= 0x7800 for any target length.  GASALX_KSEG=0: never, 2: before u16 keys
-                const char *ks = std::getenv("GASALX_KSEG");
-                const int kseg_mode = ks ? std::atoi(ks) : 1;
+                const int kseg_mode = env_int("GASALX_KSEG", 1);
                 uint32_t mseg = 0;
                 while ((hmax + 1) * (int64_t)(2u << mseg) <= 0x7800 && mseg < 12) ++mseg;   // M = 2^mseg
                 const bool seg_ok = frame && kseg_mode > 0 && mseg >= 2 && y8 <= 0xFFFF;
                 // key range: steps C + G (wavefront16.hpp step_local_dr: keys rank steps)
                 const int64_t kc = (int64_t)y8 + pl.G16;
-                // (GX_LOCAL_KA0: row k's keys carry e*k more, taken off after the sweep)
-                const int64_t hk = hmax + (GX_LOCAL_KA0 && (!pl.tb || GX_LTB_KA0) ? e * (pl.R16 - 1) : 0);
+                // (wf16_body.inc KA0: row k's keys carry e*k more, taken off after the sweep)
+                const int64_t hk = hmax + e * (pl.R16 - 1);
                 if (frame && (hk + 1) * kc <= 0x7800) {
                     pl.kf16 = y8;
                 } else if (pl.tb) {
@@ -391,8 +327,6 @@ Plan make_plan(const gasalx_params &p, const BatchShape &s, bool has_ops) {
                 }
                 if (pl.kf16) pl.key2 = false;
             }
-            // (LOCAL+TB's G16R12, GASALX_LTBD_G16: an e-drift instance only)
-            if (wf_algo == WF_LOCAL && pl.tb && pl.G16 == 16 && pl.R16 == 12 && !pl.kf16) pl.packed16 = false;
             // outside both frames the round-2 keys must hold (packed16_ok admitted the drift case)
             if (wf_algo == WF_LOCAL && !pl.kf16 && !local_key16_ok(p, s.max_q, s.max_t)) pl.packed16 = false;
             pl.semi_tq = pl.semi_tq && pl.packed16;
@@ -402,13 +336,12 @@ Plan make_plan(const gasalx_params &p, const BatchShape &s, bool has_ops) {
             // GASALX_TB_BAND=0: the full-matrix flags kernel (A/B); GASALX_TB_BAND_W: the
             // band's half width w (window of lane lg: columns [max(lg*R - w, 0), + R + 2w))
             if (pl.packed16 && pl.tb && wf_algo == WF_GLOBAL && pl.R16 % 4 == 0 && env_flag("GASALX_TB_BAND", true)) {
-                const char *bw = std::getenv("GASALX_TB_BAND_W");
                 // w = 22: config 3's paths stray up to 20 cells from the diagonal, and any pair
                 // that leaves its band costs the chain a full-matrix sweep and a second walk,
                 // latency floors however few pairs they hold; w = 10 -> 22 took config 3 from
                 // 2,953 to 3,647 GCUPS on one engine and 4,240 to 4,450-4,560 on three, though
                 // the band pass grows by 60 % (profiles/r05/n_band_width.md)
-                const int w = bw ? std::max(0, std::atoi(bw)) : 22;
+                const int w = std::max(0, env_int("GASALX_TB_BAND_W", 22));
                 pl.tb_band = true;
                 pl.band_w = (uint32_t)w;
                 pl.band_wd = ((uint32_t)(pl.R16 + 2 * w) + 3u) & ~3u;
@@ -501,8 +434,7 @@ static TailShape tail_shape(const Plan &pl, const gasalx_params &p, const WfArgs
     TailShape t;
     // (read per call, so a test process can compare both)
     const bool on = env_flag("GASALX_TAIL", true);
-    const char *ke = std::getenv("GASALX_TAIL_K");
-    const int kextra = ke ? std::atoi(ke) : 0;
+    const int kextra = env_int("GASALX_TAIL_K", 0);
     if (!on || !pl.packed16 || (pl.tb && !pl.tb_band) || pl.key2 || pl.ku16 || pl.kseg_shift || pl.semi_tq ||
         A.rev || A.n_dev || A.stop || A.lstop)
         return t;
@@ -530,7 +462,7 @@ static TailShape tail_shape(const Plan &pl, const gasalx_params &p, const WfArgs
         const int64_t a = std::max(p.match, 0), e = p.gap_extend, oe = (int64_t)p.gap_open + e;
         const int64_t k = std::max<int64_t>(p.mismatch, p.has_n_penalty ? p.n_penalty : 0);
         const int64_t hmax = a * std::min(q8, y8), base = 0x400 + oe + k + 16;
-        const int64_t hk2 = hmax + (GX_LOCAL_KA0 ? e * (R2 - 1) : 0);   // (KA0 key offsets)
+        const int64_t hk2 = hmax + e * (R2 - 1);   // (KA0 key offsets)
         if (!(base + hmax + e * span2 + a + k + 64 <= 0x7BFF && (hk2 + 1) * (y8 + G2) <= 0x7800)) return t;
         t.vmin = pl.vmin;
     } else {
@@ -637,7 +569,8 @@ static int launch_wavefront(Workspace &ws, const Plan &pl, const gasalx_params &
     }
     // (the band path's int32 launch aligns its declined blocks without direction words: the walk sends
     // those pairs to the fallback list, whose launch writes them into the capped buffer)
-    WfFn fn = A.stop ? wf_pick_stop(pl.G, pl.R) : wf_lookup(pl.wf_algo, pl.keys, pl.tb && !pl.tb_band, pl.G, pl.R);
+    WfFn fn = A.stop ? pick_instance<WfK<WF_SEMI, true, false, true>, SHAPES_R4>(pl.G, pl.R)
+                     : wf_lookup(pl.wf_algo, pl.keys, pl.tb && !pl.tb_band, pl.G, pl.R);
     if (!fn) { set_error("no wavefront instance"); return GASALX_EUNSUPPORTED; }
     if (pl.lds_bytes > 64 * 1024)
         HIPCHK(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes));
@@ -794,10 +727,7 @@ static int start_reverse(Workspace &ws, int mode, const gasalx_params &p, const 
 
 // GASALX_SORT=0/1 overrides the caller's BatchShape::sort (A/B and probes)
 static bool sort_wanted(const BatchShape &s) {
-    static const int force = [] {
-        const char *e = std::getenv("GASALX_SORT");
-        return e ? std::atoi(e) : -1;
-    }();
+    static const int force = env_int("GASALX_SORT", -1);
     return force < 0 ? s.sort : force != 0;
 }
 
@@ -1097,8 +1027,7 @@ static int align_body(Workspace &ws, const gasalx_params &p, const Plan &pl, con
                 // per SIMD, and larger batches run faster on the global array with its
                 // higher occupancy (200 K config-2 pairs: 806 -> 890 GCUPS; 1 M: 1,320
                 // global, 1,146 LDS).  GASALX_KSW_LDS=0/1 forces either (A/B)
-                const char *kl = std::getenv("GASALX_KSW_LDS");
-                const bool lds_on = kl ? std::atoi(kl) != 0 : n <= 4u * 1024u * 64u;
+                const bool lds_on = env_flag("GASALX_KSW_LDS", n <= 4u * 1024u * 64u);
                 uint32_t tpb = 0;
                 size_t lds = 0;
                 if (lds_on)

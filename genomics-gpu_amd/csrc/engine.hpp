@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -176,5 +177,13 @@ hipStream_t engine_stream(gasalx_engine *e);
 
 void set_error(const std::string &msg);
 const char *last_error();
+
+// An environment switch (A/B runs, the tests' cross-checks): the variable read as an integer, or
+// `dflt` when unset.  Read at every call, so one process can sweep a switch.
+inline int env_int(const char *name, int dflt) {
+    const char *e = std::getenv(name);
+    return e ? std::atoi(e) : dflt;
+}
+inline bool env_flag(const char *name, bool dflt) { return env_int(name, dflt ? 1 : 0) != 0; }
 
 }  // namespace gx

@@ -80,37 +80,6 @@ __device__ __forceinline__ uint32_t pk_max3(uint32_t a, uint32_t b, uint32_t c) 
 }
 
 constexpr int kW16_TB_WAVES = 2;   // GLOBAL + traceback kernel
-#ifndef GX_LOCAL_FENCE
-#define GX_LOCAL_FENCE 0   // A/B: scheduling fences after the LOCAL sweep's table reads
-#endif
-#ifndef GX_LOCAL_IL2
-#define GX_LOCAL_IL2 1     // the LOCAL sweep's rows in interleaved pairs (+1.0 %, profiles/r06/ab)
-#endif
-#ifndef GX_SEMI_IL2
-#define GX_SEMI_IL2 0      // A/B: the SEMI sweep's rows in interleaved pairs (-1.3 % on config 4)
-#endif
-#ifndef GX_GLOBAL_IL2
-#define GX_GLOBAL_IL2 1    // the GLOBAL sweep's rows in interleaved pairs (NW +1.4 %, config 3 +2-4 %)
-#endif
-#ifndef GX_TB_IL2
-#define GX_TB_IL2 1        // the traceback sweeps' rows in interleaved pairs (LOCAL+TB +0.7 %)
-#endif
-#ifndef GX_CP_ST16
-#define GX_CP_ST16 0       // A/B: the config-3 sweep's checkpoint and stream stores 16 bytes wide
-#endif
-#ifndef GX_SEMI_PH4
-#define GX_SEMI_PH4 1      // the SEMI sweep's reset code only in its first G steps (+1.0 %)
-#endif
-#ifndef GX_LTB_KA0
-#define GX_LTB_KA0 1      // GX_LOCAL_KA0 in the LOCAL+TB kernel (step_local_tb_dr): 2,964 -> 3,144 GCUPS
-                          // (its two waves per SIMD issued the two scalar addend subtracts per row)
-#endif
-#ifndef GX_LOCAL_KA0
-#define GX_LOCAL_KA0 1     // one key addend for every row (keys offset by e*k*M, taken off after the sweep): +0.6 %
-#endif
-#ifndef GX_LOCAL_ATIE
-#define GX_LOCAL_ATIE 1    // the LOCAL keys' scalar addends kept as a chain (with IL2: +2.4 %, profiles/r06/ab)
-#endif
 #ifndef GX_WF16_WAVES
 #define GX_WF16_WAVES 3   // waves per SIMD the register allocator must allow
 #endif
@@ -237,9 +206,9 @@ __device__ __forceinline__ void step_local_dr(const uint2 T, const uint32_t diag
     // row 0's addends (invp / invn: the candidates' bases), then one scalar subtract per row
     const uint32_t g20 = (FL[0] - EXT2) & 0xFFFFu, EM = (EXT2 >> 1 & 0xFFFFu) * MK16;   // e * M
     uint32_t a1 = invp - g20 * MK16, a2 = invn - g20 * MK16;
-#if GX_LOCAL_IL2
-    // A/B: two rows' independent parts interleaved (table byte, diagonal add, the two offsets), pinned
+    // two rows' independent parts interleaved (table byte, diagonal add, the two offsets), pinned
     // stage by stage with empty asm ties, so that no instruction waits on the one just before it
+    // (+1.0 %, profiles/r06/ab/README.md); the single-row loop below takes an odd last row
     constexpr int R2 = R & ~1;
 #pragma unroll
     for (int k = 0; k < R2; k += 2) {
@@ -272,9 +241,7 @@ __device__ __forceinline__ void step_local_dr(const uint2 T, const uint32_t diag
             if (!KA0) {
                 a1 -= EM;
                 a2 -= EM;
-#if GX_LOCAL_ATIE
-                asm volatile("" : "+s"(a1), "+s"(a2));
-#endif
+                asm volatile("" : "+s"(a1), "+s"(a2));   // (the addends as a chain: see the single-row loop)
             }
         }
         FL[k] = pk_addnc(FL[k], EXT);
@@ -285,10 +252,6 @@ __device__ __forceinline__ void step_local_dr(const uint2 T, const uint32_t diag
     }
 #pragma unroll
     for (int k = R2; k < R; ++k) {
-#else
-#pragma unroll
-    for (int k = 0; k < R; ++k) {
-#endif
         const uint32_t v = __builtin_amdgcn_perm(T.y, T.x, xs[k]);
         const uint32_t t1 = pk_addnc(diag, v);
         const uint32_t tmp = pk_subnb(t1, KX);
@@ -306,11 +269,10 @@ __device__ __forceinline__ void step_local_dr(const uint2 T, const uint32_t diag
             if (!KA0) {
                 a1 -= EM;   // row k + 1: FL one e higher
                 a2 -= EM;
-#if GX_LOCAL_ATIE
                 // keep the addends a chain of one subtract per row: left alone, the compiler rebuilt each
-                // row's from FL[k] (a subtract, a multiply and an add: 3 SALU per row instead of 1)
+                // row's from FL[k] (a subtract, a multiply and an add: 3 SALU per row instead of 1;
+                // +2.4 % with the interleaved pairs, profiles/r06/ab/README.md)
                 asm volatile("" : "+s"(a1), "+s"(a2));
-#endif
             }
         }
         FL[k] = pk_addnc(FL[k], EXT);
@@ -339,7 +301,7 @@ __device__ __forceinline__ void step_global(const uint2 T, const uint32_t diag_t
                                             uint32_t (&Ek)[R], uint32_t &f_out, const uint32_t KX,
                                             const uint32_t OEX, const uint32_t NN) {
     uint32_t diag = diag_top, f = f_top;
-#if GX_GLOBAL_IL2
+    // rows in interleaved pairs, as step_local_dr (NW +1.4 %, config 3 +2-4 %, profiles/r06/ab/README.md)
     constexpr int R2 = R & ~1;
 #pragma unroll
     for (int k = 0; k < R2; k += 2) {
@@ -362,10 +324,6 @@ __device__ __forceinline__ void step_global(const uint2 T, const uint32_t diag_t
     }
 #pragma unroll
     for (int k = R2; k < R; ++k) {
-#else
-#pragma unroll
-    for (int k = 0; k < R; ++k) {
-#endif
         const uint32_t v = __builtin_amdgcn_perm(T.y, T.x, xs[k]);
         const uint32_t t1 = pk_addnc(diag, v);
         const uint32_t tmp = pk_subnb(t1, KX);
@@ -443,14 +401,15 @@ __device__ __forceinline__ void step_local_tb_dr(const uint2 T, const uint32_t d
                 a2 -= EM;
             }
         }
-        flk = pk_addnc(flk, EXT);
+        flk = pk_addnc(flk, EXT);   // row k + 1: one e higher
         Ek[k] = En;
         f = Fn;
         Hout[k] = H;
+        // row by row, the scalar chains too (the scheduler otherwise spills, VGPRs and SGPRs)
         if (KEYS && !KA0) asm volatile("" : "+v"(dw[k]), "+v"(f), "+s"(a1), "+s"(a2), "+s"(flk));
         else asm volatile("" : "+v"(dw[k]), "+v"(f), "+s"(flk));
     };
-#if GX_TB_IL2
+    // rows in interleaved pairs, as step_local_dr (LOCAL+TB +0.7 %, profiles/r06/ab/README.md)
     constexpr int R2 = R & ~1;
 #pragma unroll
     for (int k = 0; k < R2; k += 2) {
@@ -469,35 +428,6 @@ __device__ __forceinline__ void step_local_tb_dr(const uint2 T, const uint32_t d
         const uint32_t t1 = pk_addnc(diag, __builtin_amdgcn_perm(T.y, T.x, xs[k]));
         cell(k, pk_subnb(t1, KX), pk_subnb(t1, OEX));
     }
-#else
-#pragma unroll
-    for (int k = 0; k < R; ++k) {
-        const uint32_t v = __builtin_amdgcn_perm(T.y, T.x, xs[k]);
-        const uint32_t t1 = pk_addnc(diag, v);
-        const uint32_t tmp = pk_subnb(t1, KX);
-        const uint32_t toe = pk_subnb(t1, OEX);
-        const uint32_t H = pk_max3(tmp, f, Ek[k]);
-        const uint32_t En = pk_max3(toe, Ek[k], flk);
-        const uint32_t Fn = pk_max_u16(toe, f);
-        const uint32_t fu = tb_flag(H, tmp), fw = tb_flag(H, f), fx = tb_flag(toe, Ek[k]), fy = tb_flag(toe, f);
-        const uint32_t m1 = __builtin_amdgcn_perm(fx, fu, 0x0B090A08u);
-        const uint32_t m2 = __builtin_amdgcn_perm(fy, fw, 0x0B090A08u);
-        dw[k] = and_or(m2, M2, j == 0 ? (m1 & M1) : and_or(m1, M1, dw[k]));
-        if (KEYS) {
-            key[k] = pk_max3(key[k], pk_mad_u16_lo(Hin[k], KMUL, a1), pk_mad_u16_lo(H, KMUL, a2));
-            a1 -= EM;
-            a2 -= EM;
-        }
-        flk = pk_addnc(flk, EXT);   // row k + 1: one e higher
-        Ek[k] = En;
-        f = Fn;
-        diag = Hin[k];
-        Hout[k] = H;
-        // row by row, the scalar chains too (the scheduler otherwise spills, VGPRs and SGPRs)
-        if (KEYS) asm volatile("" : "+v"(dw[k]), "+v"(f), "+s"(a1), "+s"(a2), "+s"(flk));
-        else asm volatile("" : "+v"(dw[k]), "+v"(f), "+s"(flk));
-    }
-#endif
     FL0 = pk_addnc(FL0, EXT);   // the next step
     f_out = f;
 }
@@ -510,21 +440,25 @@ __device__ __forceinline__ void step_global_tb(const uint2 T, const uint32_t dia
                                                const uint32_t NN, const int j) {
     const uint32_t M1 = 0x01010101u << j, M2 = 0x10101010u << j;
     uint32_t diag = diag_top, f = f_top, tx = T.x, ty = T.y;
-#if GX_TB_IL2
+    // one cell from tmp = diag + v - KX and toe = diag + v - OEX (drift e: see step_global)
     auto cell = [&](const int k, const uint32_t tmp, const uint32_t toe) __attribute__((always_inline)) {
         const uint32_t H = pk_max3(tmp, f, Ek[k]);
-        const uint32_t em = Ek[k], fm = f;
+        const uint32_t em = Ek[k], fm = f;               // E - e and F - e, in the frame
         const uint32_t En = pk_max3(toe, em, NN);
         const uint32_t Fn = pk_max3(toe, fm, NN);
         const uint32_t fu = tb_flag(H, tmp), fw = tb_flag(H, f), fx = tb_flag(toe, em), fy = tb_flag(toe, fm);
+        // bytes: [u, x] per half and [w, y] per half, 0x00 / 0xFF
         const uint32_t m1 = __builtin_amdgcn_perm(fx, fu, 0x0B090A08u);
         const uint32_t m2 = __builtin_amdgcn_perm(fy, fw, 0x0B090A08u);
         dw[k] = and_or(m2, M2, j == 0 ? (m1 & M1) : and_or(m1, M1, dw[k]));
         Ek[k] = En;
         f = Fn;
         Hout[k] = H;
+        // SYNC: each row's flags before the next row (the band pass deferred them all to the
+        // window's store otherwise: 345 spilled VGPRs; 120 VGPRs with it)
         if (SYNC) asm volatile("" : "+v"(dw[k]), "+v"(f));
     };
+    // rows in interleaved pairs, as step_local_dr
     constexpr int R2 = R & ~1;
 #pragma unroll
     for (int k = 0; k < R2; k += 2) {
@@ -543,31 +477,6 @@ __device__ __forceinline__ void step_global_tb(const uint2 T, const uint32_t dia
         const uint32_t t1 = pk_addnc(diag, __builtin_amdgcn_perm(ty, tx, xs[k]));
         cell(k, pk_subnb(t1, KX), pk_subnb(t1, OEX));
     }
-#else
-#pragma unroll
-    for (int k = 0; k < R; ++k) {
-        const uint32_t v = __builtin_amdgcn_perm(ty, tx, xs[k]);
-        const uint32_t t1 = pk_addnc(diag, v);           // drift e: see step_global
-        const uint32_t tmp = pk_subnb(t1, KX);
-        const uint32_t toe = pk_subnb(t1, OEX);
-        const uint32_t H = pk_max3(tmp, f, Ek[k]);
-        const uint32_t em = Ek[k], fm = f;               // E - e and F - e, in the frame
-        const uint32_t En = pk_max3(toe, em, NN);
-        const uint32_t Fn = pk_max3(toe, fm, NN);
-        const uint32_t fu = tb_flag(H, tmp), fw = tb_flag(H, f), fx = tb_flag(toe, em), fy = tb_flag(toe, fm);
-        // bytes: [u, x] per half and [w, y] per half, 0x00 / 0xFF
-        const uint32_t m1 = __builtin_amdgcn_perm(fx, fu, 0x0B090A08u);
-        const uint32_t m2 = __builtin_amdgcn_perm(fy, fw, 0x0B090A08u);
-        dw[k] = and_or(m2, M2, j == 0 ? (m1 & M1) : and_or(m1, M1, dw[k]));
-        Ek[k] = En;
-        f = Fn;
-        diag = Hin[k];
-        Hout[k] = H;
-        // SYNC: each row's flags before the next row (the band pass deferred them all to the
-        // window's store otherwise: 345 spilled VGPRs; 120 VGPRs with it)
-        if (SYNC) asm volatile("" : "+v"(dw[k]), "+v"(f));
-    }
-#endif
     f_out = f;
 }
 
@@ -631,33 +540,10 @@ __device__ __forceinline__ void step_semi(const uint2 T, const uint32_t diag_top
                                           const uint32_t (&xs)[R], const uint32_t (&Hin)[R], uint32_t (&Hout)[R],
                                           uint32_t (&Fk)[R], const uint32_t GO, const uint32_t *pv = nullptr) {
     uint32_t diag = diag_top, h = hl, e = el;
-#if GX_SEMI_IL2
-    constexpr int R2 = R & ~1;
-#pragma unroll
-    for (int k = 0; k < R2; k += 2) {
-        uint32_t v0 = __builtin_amdgcn_perm(T.y, T.x, xs[k]), v1 = __builtin_amdgcn_perm(T.y, T.x, xs[k + 1]);
-        if (PV > 0 && k >= R - PV) v0 = pk_addnc(v0, pv[k - (R - PV)]);
-        if (PV > 0 && k + 1 >= R - PV) v1 = pk_addnc(v1, pv[k + 1 - (R - PV)]);
-        asm volatile("" : "+v"(v0), "+v"(v1));
-        uint32_t t0 = pk_addnc(diag, v0), t1 = pk_addnc(Hin[k], v1);
-        uint32_t F0 = pk_max_u16(Hin[k], Fk[k]), F1 = pk_max_u16(Hin[k + 1], Fk[k + 1]);
-        asm volatile("" : "+v"(t0), "+v"(t1), "+v"(F0), "+v"(F1));
-        e = pk_max_u16(h, e);
-        h = pk_subnb(pk_max3(t0, F0, e), GO);
-        Hout[k] = h;
-        e = pk_max_u16(h, e);
-        h = pk_subnb(pk_max3(t1, F1, e), GO);
-        Hout[k + 1] = h;
-        Fk[k] = F0;
-        Fk[k + 1] = F1;
-        diag = Hin[k + 1];
-    }
-#pragma unroll
-    for (int k = R2; k < R; ++k) {
-#else
+    // (row by row: interleaved pairs, as the other sweeps have them, measured -1.3 % here,
+    // profiles/r06/ab/README.md)
 #pragma unroll
     for (int k = 0; k < R; ++k) {
-#endif
         uint32_t v = __builtin_amdgcn_perm(T.y, T.x, xs[k]);
         if (PV > 0 && k >= R - PV) v = pk_addnc(v, pv[k - (R - PV)]);
         const uint32_t tmp = pk_addnc(diag, v);                     // H(r-1,c-1) + s
@@ -751,7 +637,6 @@ constexpr int WF16_LOCAL_U16_RS = 12; // the same with u16 keys (local_rs.hip in
 // row the first segment holding its maximum (later columns win only when strictly higher)
 constexpr int WF16_LOCAL_SEG = 13;
 constexpr int WF16_LOCAL_TBD = 14;    // LOCAL + traceback in the e-drift frame (step_local_tb_dr)
-constexpr int WF16_LOCAL_SEGR = 15;   // WF16_LOCAL_SEG with the finished segments' best per row in registers
 constexpr int kW16_LTBD_WAVES = 2;
 constexpr int kW16_TQ_WAVES = 3;
 constexpr int kW16_TQ_BIG_WAVES = 3;   // R > 20: 3 waves spill (R = 23: 20 VGPRs) and still beat 2 (profiles/r03_semi_tq_waves_ab.md)
@@ -761,8 +646,7 @@ constexpr int kW16_CP_WAVES = 3;    // GLOBAL score sweep with band checkpoints,
 __host__ __device__ constexpr int wf16_waves(int algo, int R) {
     return algo == WF16_GLOBAL_TB ? kW16_TB_WAVES
            : algo == WF16_LOCAL_TB ? kW16_LTB_WAVES
-           : algo == WF16_LOCAL_TBD ? (R <= 12 ? 3 : kW16_LTBD_WAVES)   // G16R12: the 3-wave A/B shape
-           : algo == WF16_LOCAL_SEGR ? 2                                 // 2R more VGPRs than WF16_LOCAL_SEG
+           : algo == WF16_LOCAL_TBD ? kW16_LTBD_WAVES
            : algo == WF16_LOCAL_K2 ? kW16_K2_WAVES
            : algo == WF16_SEMI_TQ ? (R > 20 ? kW16_TQ_BIG_WAVES : kW16_TQ_WAVES)
            : algo == WF16_GLOBAL_CP ? kW16_CP_WAVES
@@ -796,9 +680,39 @@ __global__ __launch_bounds__(kBlock, wf16_waves(ALGO_, R1)) void wf16_mix_kernel
     }
 }
 
+// ---------------------------------------------------------------------------
+// (G lanes per pair, R rows per lane) shapes: register-axis positions covered = G*R.  Each list
+// is written once, here: the planner's arrays (dispatch.hip kShapes / kShapes16) and every table
+// of instances (pick_instance) come from them.
+//  * GX_SHAPES_R4: the int32 kernels (wavefront.hpp) and the packed kernels that store in groups
+//    of 4 rows (traceback flags, band windows), R % 4 == 0;
+//  * GX_SHAPES_PK: the packed score kernels (register axis = query for LOCAL/GLOBAL, target for
+//    SEMI): R = 19 fits 150 bp (152 padded) and R = 23 fits 182 bp (184 padded) exactly; the
+//    G = 16/32/64 shapes with few rows per lane serve small batches (make_plan).
+// ---------------------------------------------------------------------------
+#define GX_SHAPES_R4(X) X(8, 8) X(8, 12) X(8, 16) X(8, 20) X(16, 16) X(16, 20) X(32, 20) X(64, 20)
+#define GX_SHAPES_PK(X)                                                                               \
+    X(8, 8) X(8, 12) X(8, 16) X(8, 19) X(8, 20) X(8, 23) X(16, 10) X(16, 12) X(16, 16) X(16, 20)      \
+    X(32, 5) X(32, 6) X(32, 9) X(32, 20) X(64, 3) X(64, 5) X(64, 20)
+enum ShapeSet { SHAPES_R4, SHAPES_PK };
+
+// the instance K::fn<G, R>() of kernel family K for a shape of list L, nullptr for any other shape
+template <class K, ShapeSet L>
+auto pick_instance(int G, int R) -> decltype(K::template fn<8, 8>()) {
+#define GX_CASE(g, r) if (G == g && R == r) return K::template fn<g, r>();
+    if constexpr (L == SHAPES_R4) { GX_SHAPES_R4(GX_CASE) } else { GX_SHAPES_PK(GX_CASE) }
+#undef GX_CASE
+    return nullptr;
+}
+
+using Wf16Fn = void (*)(WfArgs);
+template <int ALGO>
+struct Wf16K {
+    template <int G, int R> static Wf16Fn fn() { return &wf16_kernel<ALGO, G, R>; }
+};
+
 // SEMI TAIL=QUERY/BOTH instances, G = 8, R = 1..32 (semi_tq.hip; one per padded target
 // length 8R): NULL outside that range
-using Wf16Fn = void (*)(WfArgs);
 Wf16Fn wf16_tq_lookup(int R);
 // LOCAL e-drift instances with u16 keys and/or the reverse pass's early stop (local_rs.hip):
 // NULL for shapes outside kShapes16

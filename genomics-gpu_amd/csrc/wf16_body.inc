@@ -15,10 +15,7 @@
     constexpr bool K2 = ALGO_ == WF16_LOCAL_K2;
     constexpr bool KU16 = ALGO_ == WF16_LOCAL_U16 || ALGO_ == WF16_LOCAL_U16_RS;
     constexpr bool LRS = ALGO_ == WF16_LOCAL_RS || ALGO_ == WF16_LOCAL_U16_RS;   // (the check costs VGPRs)
-    // KSEGR: the segment keys merged into a per-row running best in registers instead of saved to
-    // A.kseg (the A/B of VERDICT r05 item 6; 2R more VGPRs, two waves per SIMD)
-    constexpr bool KSEGR = ALGO_ == WF16_LOCAL_SEGR;
-    constexpr bool KSEG = ALGO_ == WF16_LOCAL_SEG || KSEGR;
+    constexpr bool KSEG = ALGO_ == WF16_LOCAL_SEG;
     constexpr bool LTBD = ALGO_ == WF16_LOCAL_TBD;
     // TQ: one launch per class of equal padded target length G*R (dispatch.hip), so the
     // last padded column is always register R - 1 of lane G - 1
@@ -250,10 +247,6 @@
         const uint32_t bshift = ((uint32_t)P.base << 8) & 0xFFFFu;
         uint32_t HA[R], HB[R], Ek[R], key[R], key2[K2 ? R : 1];
         uint32_t jseg = 0;   // KSEG: segments saved to A.kseg (the live one is segment jseg)
-        // KSEGR: per row, the best finished segment's key (packed halves) and that segment's index
-        uint32_t sbest[KSEGR ? R : 1], sseg[KSEGR ? R : 1];
-#pragma unroll
-        for (int k = 0; k < (KSEGR ? R : 1); ++k) { sbest[k] = 0x04000400u; sseg[k] = 0; }
 #pragma unroll
         for (int k = 0; k < R; ++k) { HA[k] = BB; HB[k] = BB; Ek[k] = BB; key[k] = 0; }
 #pragma unroll
@@ -355,15 +348,13 @@
                 // KA0: every row's key candidates take row 0's addend, so row k's keys sit e*k*M higher
                 // (H + e*k in place of H; the planner's key range allows for it) and lose it after
                 // the sweep: one subtract per row per wave instead of two scalar ones per row per step
-                constexpr bool KA0 = GX_LOCAL_KA0 && !LRS && !KSEG && !KU16 && !LTBD;
-                constexpr bool KA0T = GX_LOCAL_KA0 && GX_LTB_KA0 && LTBD;   // the same in the LOCAL+TB kernel
+                // (+0.6 %; LOCAL+TB, whose two waves per SIMD issued the scalar subtracts: +6 %,
+                // profiles/r06/ab/README.md)
+                constexpr bool KA0 = !LRS && !KSEG && !KU16 && !LTBD;
+                constexpr bool KA0T = LTBD;   // the same in the LOCAL+TB kernel
                 const uint32_t ADJ = pk_bcast(ge * (R - 1));
-#if GX_DPP_FUSE
                 uint32_t ADJV = ADJ;
                 asm volatile("" : "+v"(ADJV));   // a VGPR operand: the hand-off's subtract folds into its DPP move
-#else
-                const uint32_t ADJV = ADJ;
-#endif
                 // the diagonals of the first two steps, which no upper-lane step hands over
                 // (lane 1's upper lane has no garbage column -1): H = 0 at k = -1, s - 1
                 prevRecvH = (uint32_t)(pbv - 2 * ge) * 0x10001u;
@@ -412,35 +403,15 @@
                 }
                 for (; !LTBD && s < nsteps; s += 2, c += 2) {
                     if (KSEG && s == segend && jseg < A.kseg_n) {   // wave-uniform: a segment ends
-                        if constexpr (KSEGR) {
-                            // a later segment replaces the best only with a strictly higher H: key >=
-                            // ((best >> m) + 1) << m, per half (borrow-free 16-bit subtract, sign
-                            // bit as the keep mask; values in [0x0400, 0x7BFF])
-                            const uint32_t lowm = ((MK - 1u) & 0xFFFFu) * 0x10001u, js = jseg * 0x10001u;
-                            const pk_u2 one = {1, 1}, sh15 = {15, 15};
+                        // [wave][segment][lane][R]: one base address, immediate offsets
+                        uint32_t *dst = A.kseg + (((size_t)wv * A.kseg_n + jseg) * 64 + lane) * R;
 #pragma unroll
-                            for (int k = 0; k < R; ++k) {
-                                const uint32_t thr = GX_AS(uint32_t, GX_AS(pk_u2, sbest[k] | lowm) + one);
-                                const uint32_t d = GX_AS(uint32_t, GX_AS(pk_u2, key[k]) - GX_AS(pk_u2, thr));
-                                const uint32_t keep = GX_AS(uint32_t, GX_AS(pk_u2, d) >> sh15) * 0xFFFFu;
-                                sbest[k] = __builtin_amdgcn_bitop3_b32(sbest[k], keep, key[k], 0xE2);   // keep ? best : key
-                                sseg[k] = __builtin_amdgcn_bitop3_b32(sseg[k], keep, js, 0xE2);
-                                key[k] = KOFS * 0x10001u;
-                            }
-                        } else {
-                            // [wave][segment][lane][R]: one base address, immediate offsets
-                            uint32_t *dst = A.kseg + (((size_t)wv * A.kseg_n + jseg) * 64 + lane) * R;
-#pragma unroll
-                            for (int k = 0; k < R; ++k) { dst[k] = key[k]; key[k] = KOFS * 0x10001u; }
-                        }
+                        for (int k = 0; k < R; ++k) { dst[k] = key[k]; key[k] = KOFS * 0x10001u; }
                         ++jseg;
                         segend += MK;
                     }
                     uint2 T = tnext;
                     tnext = tcol[c + 1 + G];
-#if GX_LOCAL_FENCE
-                    __builtin_amdgcn_sched_barrier(0);   // the next step's table read issued a step ahead
-#endif
                     const uint32_t dt0 = (uint32_t)(pbv + ge * (c - 2)) * 0x10001u;   // lane 0: H^(-1, c - 1)
                     step_local_dr<R, false, KU16>(T, top ? dt0 : prevRecvH, top ? BB : recvF, xs, HA, HB, Ek, key, FL, f,
                                             KXD, OEXD, EXT, KMC, 0u, 0u, EXT2);
@@ -449,9 +420,6 @@
                     recvF = pk_subnb((uint32_t)shr_lane((int32_t)f), ADJV);
                     T = tnext;
                     tnext = tcol[c + 2 + G];
-#if GX_LOCAL_FENCE
-                    __builtin_amdgcn_sched_barrier(0);
-#endif
                     const uint32_t dt1 = (uint32_t)(pbv + ge * (c - 1)) * 0x10001u;
                     step_local_dr<R, true, KU16, KA0>(T, top ? dt1 : prevRecvH, top ? BB : recvF, xs, HB, HA, Ek, key, FL,
                                                     f, KXD, OEXD, EXT, KMV, inv(s, 0), inv(s + 1, (uint32_t)(-ge)), EXT2, MK);
@@ -553,12 +521,8 @@
                         const uint32_t Hj = x >> ms, t = x & ((1u << ms) - 1u);
                         if (Hj > H) { H = Hj; col = ((j + 1) << ms) - 1u - t - lg; }
                     };
-                    if constexpr (KSEGR) {
-                        if (jseg > 0) seg((sseg[k] >> (16 * h)) & 0xFFFFu, sbest[k]);
-                    } else {
-                        const uint32_t *src = A.kseg + ((size_t)wv * A.kseg_n * 64 + lane) * R + k;
-                        for (uint32_t j = 0; j < jseg; ++j) seg(j, src[(size_t)j * (64 * R)]);
-                    }
+                    const uint32_t *src = A.kseg + ((size_t)wv * A.kseg_n * 64 + lane) * R + k;
+                    for (uint32_t j = 0; j < jseg; ++j) seg(j, src[(size_t)j * (64 * R)]);
                     seg(jseg, key[k]);
                 }
                 if constexpr (K2) {   // columns 256..511: later, so they win only when strictly higher
@@ -628,9 +592,6 @@
         uint32_t *cpw = GCP ? bcp + ((size_t)wv * 64 + lane) * (2 * R) : nullptr;   // [wave][lane][2R]
         uint2 *stw = GCP ? bstm + ((size_t)wv * 64 + lane) * band_stream_words(BWD) : nullptr;   // [wave][lane][SW]
         uint2 tnext = tcol[c + G];
-#if GX_CP_ST16
-        uint2 sthold = make_uint2(0u, 0u);   // GCP: the even stream entry, stored with the odd one
-#endif
         // Capture window: the steps at which some lane of the wave holds a cell to capture --
         // row xl - 1 at column yl - 1 (the score, global.h:98-103,299) and, for traceback, row
         // xl at column yl (the start cell, tb_kernel) -- so that the steps outside it carry no
@@ -699,23 +660,6 @@
                 }
             }
             if constexpr (GCP) {
-#if GX_CP_ST16
-                // 16-byte stores only (an 8-byte store from each of a few lanes 480 bytes apart wrote
-                // partial lines): the checkpoint in quads, the stream entries in pairs
-                if (cp_on && cc == cs_own) {
-#pragma unroll
-                    for (int k = 0; k < R; k += 4) {
-                        *reinterpret_cast<uint4 *>(cpw + k) = make_uint4(Hout[k], Hout[k + 1], Hout[k + 2], Hout[k + 3]);
-                        *reinterpret_cast<uint4 *>(cpw + R + k) = make_uint4(Ek[k], Ek[k + 1], Ek[k + 2], Ek[k + 3]);
-                    }
-                }
-                const uint32_t t = (uint32_t)(cc - cs_dn);
-                if (st_on && t <= BWD) {
-                    if (t & 1u) *reinterpret_cast<uint4 *>(stw + t - 1) = make_uint4(sthold.x, sthold.y, Hout[R - 1], f);
-                    else if (t == BWD) stw[t] = make_uint2(Hout[R - 1], f);
-                    else sthold = make_uint2(Hout[R - 1], f);
-                }
-#else
                 if (cp_on && cc == cs_own) {
 #pragma unroll
                     for (int k = 0; k < R; k += 2) {
@@ -725,7 +669,6 @@
                 }
                 const uint32_t t = (uint32_t)(cc - cs_dn);
                 if (st_on && t <= BWD) stw[t] = make_uint2(Hout[R - 1], f);
-#endif
             }
             prevRecvH = recvH;
             recvH = (uint32_t)shr_lane((int32_t)Hout[R - 1]);
@@ -910,7 +853,6 @@
                 half_step(flg, c + 1, HB, HA);
             }
         };
-#if GX_SEMI_PH4
         // the first G steps with the resets at row -1 (lane lg's at step lg - 1), the captures only
         // from the capture window on, and no reset code after step G (its branch and exec-mask
         // bookkeeping ran on every step of the sweep).  Only in the plain SEMI kernel (the one
@@ -926,12 +868,6 @@
             run(std::integral_constant<int, 0>{}, min(nsteps, cw));
             run(std::integral_constant<int, 2>{}, nsteps);
         }
-#else
-        // the steps before the capture window (the resets at row -1, step lg - 1, included), then
-        // the rest with the captures
-        run(std::integral_constant<int, 1>{}, min(nsteps, cap_lo & ~1u));
-        run(std::integral_constant<int, 3>{}, nsteps);
-#endif
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             uint32_t b = best[h];

@@ -1437,24 +1437,22 @@ def test_tail_shape_declined_blocks(engine, monkeypatch, k_extra):
         assert np.array_equal(g[f], o[f]), f
 
 
-def test_local_traceback_three_wave_shape(engine, monkeypatch):
-    """LOCAL+TB on the 3-wave G16R12 instance (GASALX_LTBD_G16=1, the A/B of VERDICT r05 item 4):
-    CIGAR bytes, n_ops, starts and ends as the oracle, config-2 data and ragged pairs."""
-    monkeypatch.setenv("GASALX_LTBD_G16", "1")
+def test_local_traceback_drift_kernel(engine):
+    """LOCAL+TB on the plan's own e-drift instance (G8R20 at 150 x 150): CIGAR bytes, n_ops, starts
+    and ends as the oracle, config-2 data and ragged pairs with N."""
     kw = dict(algo=G.LOCAL, start_pos=G.WITH_TB)
-    assert G.describe_plan(G.make_params(**kw), 150, 150).endswith("_G16R12")
+    assert G.describe_plan(G.make_params(**kw), 150, 150) == "wavefront16_local_tb_dr_G8R20"
     check(engine, no_cigar_overflow(G.Batch.synth(2, 20000, 0x5EED0002), **kw), cigar=True, **kw)
     rng = np.random.default_rng(0x16C12)
-    # (lengths inside the e-drift kernel's f16 key range, (Hmax + 1) * (C + 16) <= 0x7800)
+    # (lengths inside the e-drift kernel's f16 key range)
     qs, ts = helpers.random_pairs(rng, 900, 1, 150, 1, 180, alphabet=b"ACGTACGTN", related=0.6)
     check(engine, no_cigar_overflow(G.Batch.from_pairs(qs, ts), **kw), cigar=True, **kw)
 
 
-def test_local_segments_in_registers(engine, monkeypatch):
-    """LOCAL keys by step segments with the finished segments' best per row in registers
-    (GASALX_KSEG_REG=1, WF16_LOCAL_SEGR, the A/B of VERDICT r05 item 6) on 300 x 300 pairs,
-    including maxima tied across segment boundaries (a later segment wins only when higher)."""
-    monkeypatch.setenv("GASALX_KSEG_REG", "1")
+def test_local_segment_keys_ties_across_segments(engine):
+    """LOCAL keys by step segments (WF16_LOCAL_SEG, the finished segments' keys saved per wave) on
+    300 x 300 pairs, including maxima tied across segment boundaries (a later segment wins only
+    when higher)."""
     kw = dict(algo=G.LOCAL)
     assert G.describe_plan(G.make_params(**kw), 300, 300) == "wavefront16_local_seg64_G16R20"
     check(engine, G.Batch.synth(3, 30000, 0x5EED0003), **kw)
