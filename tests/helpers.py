@@ -182,3 +182,138 @@ def random_pairs(rng, n, qmin, qmax, tmin, tmax, related=0.7, alphabet=b"ACGT"):
             t = random_seq(rng, int(rng.integers(tmin, tmax + 1)), alphabet)
         qs.append(q); ts.append(t)
     return qs, ts
+
+
+# ------------------------------------------------------------------ KSW ----
+def _unlike(rng, n, avoid):
+    """n bases that never equal the base at the same position of `avoid` (cycled)."""
+    out = bytearray()
+    for k in range(n):
+        c = avoid[k % len(avoid)] if avoid else 0
+        out.append(random_seq(rng, 1, bytes(x for x in b"ACGT" if x != c))[0])
+    return bytes(out)
+
+
+def ksw_rule_batches(seed=0x155):
+    """Constructed KSW batches, one per control-flow rule of ksw_kernel_template.h (rules K1-K3
+    of tests/independent.py, the clip rule :188, seed 0, length 1).  name -> (queries, targets,
+    seeds, scores).  Whether a rule fired is for the caller to assert, from independent.ksw's
+    state=True counts."""
+    rng = np.random.default_rng(seed)
+    out = {}
+    # K1 (:155): qlen a multiple of 8, a seed that dies after a few matching columns against an
+    # unrelated tail, so rows are trimmed short of qlen.  The row's last cell is then an F
+    # tail of the diagonal (diagonal - (o + e) - ...), which passes the clip rule only when
+    # o + e < PEN_CLIP5: gap scores (2, 1), with (6, 1) pairs beside them
+    qs, ts, sd = [], [], []
+    for k in range(240):
+        ql = 8 * int(rng.integers(1, 6))
+        q = random_seq(rng, ql)
+        p = int(rng.integers(1, 7))
+        t = q[:p] + _unlike(rng, int(rng.integers(0, 12)), q[p:] + b"A")
+        qs.append(q); ts.append(t); sd.append(int(rng.integers(1, 9)))
+    out["line155"] = (qs, ts, sd, (1, 4, 2, 1))
+    out["line155_oe7"] = (qs, ts, sd, (1, 4, 6, 1))
+    # K2 (:159): a first target word of T against a query without T kills the seed inside the
+    # word (m == 0 in row 1..3); the first-column value left in eh[0] revives the pair at row 8,
+    # where the target goes on as the query itself and outgrows the seed
+    qs, ts, sd = [], [], []
+    for k in range(160):
+        q = random_seq(rng, int(rng.integers(12, 41)), b"ACG")
+        lead = 8 * int(rng.integers(1, 3))
+        qs.append(q); ts.append(b"T" * lead + q[: int(rng.integers(1, len(q) + 1))]); sd.append(int(rng.integers(8, 22)))
+    for k in range(40):                                       # and plain unrelated first words
+        q = random_seq(rng, int(rng.integers(4, 30)))
+        qs.append(q); ts.append(_unlike(rng, 8, q) + q); sd.append(int(rng.integers(0, 16)))
+    out["tile_break"] = (qs, ts, sd, (1, 4, 6, 1))
+    # K3 (:140): the main diagonal with two mismatches (-10) ties the diagonal four columns to
+    # the right, entered through the first row's insertion of four (-(6 + 4)): q = XX + R[2:4] + R,
+    # t = R with R of period 4; a query tail keeps the end of the query out of reach
+    qs, ts, sd = [], [], []
+    for k in range(120):
+        unit = bytes(rng.permutation(np.frombuffer(b"ACGT", np.uint8)))
+        R = unit * int(rng.integers(3, 8))
+        xx = _unlike(rng, 2, unit)
+        tail = bytes([b"ACGT"[(b"ACGT".index(unit[0]) + 1) % 4]]) * int(rng.integers(6, 14))
+        qs.append(xx + unit[2:] + R + tail); ts.append(R); sd.append(int(rng.integers(11, 40)))
+    out["tie"] = (qs, ts, sd, (1, 4, 6, 1))
+    # the clip rule (:188): the best cell, then mismatches and matches down to the query's end:
+    # max - gscore = 4 * x - y for x mismatches followed by y matches; 4, 5 and 6 among them
+    qs, ts, sd = [], [], []
+    for k in range(160):
+        P = random_seq(rng, int(rng.integers(4, 24)))
+        x, y = [(1, 0), (2, 3), (2, 2), (1, 0), (2, 3), (3, 7), (2, 4), (3, 6)][k % 8]
+        mm = random_seq(rng, x)
+        tailq = random_seq(rng, y)
+        qs.append(P + mm + tailq); ts.append(P + _unlike(rng, x, mm) + tailq + random_seq(rng, int(rng.integers(0, 4))))
+        sd.append(int(rng.integers(8, 30)))
+    out["clip"] = (qs, ts, sd, (1, 4, 6, 1))
+    # seed 0: every entry stays 0 (M = M ? M + s : 0), every word's first row ends its word
+    qs, ts = random_pairs(rng, 80, 1, 40, 1, 40, related=1.0)
+    out["seed0"] = (qs, ts, [0] * 80, (1, 4, 6, 1))
+    # a single base on either side, on both, every seed around o + e
+    qs, ts, sd = [], [], []
+    for k in range(120):
+        one = random_seq(rng, 1)
+        other = random_seq(rng, int(rng.integers(1, 20)))
+        if k % 3 == 0:
+            other = one + other
+        q, t = [(one, other), (other, one), (one, random_seq(rng, 1))][k % 3]
+        qs.append(q); ts.append(t); sd.append(k % 20)
+    out["length1"] = (qs, ts, sd, (1, 4, 6, 1))
+    return out
+
+
+def ksw_routing(qs, ts, seed, scores=(1, 4, 6, 1), env=None, npen=None):
+    """Which KSW kernel form the dispatcher's documented rule (dispatch.hip, KSW branch;
+    ksw16.hpp header; gen_ksw_kernel) sends every pair of a batch to, from the inputs alone.
+    Returns dict(taken: pairs ksw16 takes, level: the entry level 0/1/2 of the others' (and,
+    for the taken ones, the level they would run), inst: the ksw16 instance 64 / 96 / 160 /
+    0 = global entries / None = ksw16 off for the batch, tpb: threads per block of the LDS
+    level 0, 0 = global entries, bound).  The tests assert on this so that a change of the
+    rule fails them instead of moving them onto another kernel without notice."""
+    env = env or {}
+    a, b, o, e = scores
+    ql = np.array([len(q) for q in qs], np.int64); tl = np.array([len(t) for t in ts], np.int64)
+    seed = np.asarray(seed, np.int64)
+    n = len(ql)
+    step = max(a, -b, 0) if npen is None else max(a, -b, -npen, 0)
+    bound = seed + step * np.minimum(ql, tl)
+    if o < 0 or e < 0:
+        bound = np.full(n, 1 << 62, np.int64)           # the negative-gap rule: int2 entries
+    max_q = int(ql.max())
+    k16 = env.get("GASALX_KSW16", "1") != "0" and o >= 0 and e >= 0 and o + e <= 0x300 and max_q <= 254
+    ok = (bound <= 255) & (ql <= 254) & np.array([all(c in b"ACGT" for c in q) for q in qs])
+    lane_ok = ok.copy()
+    lane_ok[0:n - n % 2:2] &= ok[1:n:2]
+    lane_ok[1:n:2] &= ok[0:n - n % 2:2]
+    cols = (max_q + 3) & ~1
+    inst = next((c for c in (64, 96, 160) if cols <= c), 0) if k16 else None
+    lds_on = env.get("GASALX_KSW_LDS", "1" if n <= 4 * 1024 * 64 else "0") != "0"
+    tpb = next((t for t in (256, 128, 64) if 2 * t * (max_q + 2) * 2 <= 160 * 1024), 0) if lds_on else 0
+    return dict(taken=lane_ok & k16, level=np.where(bound <= 255, 0, np.where(bound <= 65535, 1, 2)),
+                inst=inst, tpb=tpb, bound=bound, max_q=max_q)
+
+
+def ksw_rule_fired(name, b, seed, r):
+    """Whether the rule a constructed batch is named for decided at least one pair's answer,
+    from the inputs and independent.ksw's own state (never from the oracle or the GPU)."""
+    ql, tl = b.q_lens.astype(np.int64), b.t_lens.astype(np.int64)
+    at_end = r["q_end"] == ql                           # the gscore branch was reported
+    if name == "line155":
+        # a row trimmed short of qlen took the gscore update and the answer is a gscore
+        return int(((r["k1_rows"] > 0) & at_end & (ql % 8 == 0) & (r["score"] > 0)).sum())
+    if name == "line155_oe7":
+        return int(((r["k1_rows"] > 0) & (ql % 8 == 0)).sum())
+    if name == "tile_break":
+        # rows after the dead word were computed and carried the maximum past the seed
+        return int(((r["k2_resumed"] > 0) & (r["score"] > seed) & (r["t_end"] > 8)).sum())
+    if name == "tie":
+        return int(((r["k3_ties"] > 0) & ~at_end).sum())
+    if name == "clip":
+        return min(int((r["margin"] == 5).sum()), int((r["margin"] == 4).sum()), int((r["margin"] == 6).sum()))
+    if name == "seed0":
+        return int(((seed == 0) & (r["score"] == 0) & (r["k2_resumed"] > 0)).sum())
+    if name == "length1":
+        return min(int((ql == 1).sum()), int((tl == 1).sum()), int(((ql == 1) & (tl == 1)).sum()))
+    raise KeyError(name)

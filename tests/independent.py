@@ -26,6 +26,7 @@ Beyond the score kernels this module also restates, each in a form of its own:
   local_start()     the WITH_START reverse pass (local_kernel_template.h:441-511), see below.
   pairhmm64()       the PairHMM forward model in float64, along anti-diagonals
                     (PairHMM/inter_task/Synthetic_data/tile_1/tile_1.cu:95-175).
+  ksw()             gasal_ksw_kernel (ksw_kernel_template.h:47-199), see below.
   replay_cigar()    walks a forward CIGAR over the two sequences: consumed lengths, M/X
                     labels against the bases, the affine score of the path.
   global_textbook() plain affine global DP without any reference quirk, for rectangle checks.
@@ -46,7 +47,40 @@ cell where the running maximum reaches the forward score (:469,479,482).  So
 The oracle and the HIP start pass (start.hpp) both read it this way; local_start() below
 restates it by running local() on the reversed prefixes and mapping the end it finds back.
 
-KSW is out of scope here: its only pin stays the Q16 hand KATs (tests/test_hand_kats.py).
+KSW (ksw(), ksw_kernel_template.h:47-199).  BWA's ksw_extend walks the
+target row by row over one array eh[0..qlen] of (h, e) entries and trims the column range
+[beg, end) after every row.  GASAL2 wrapped both loops in tiles of 8 packed bases, and three
+of its control-flow rules follow from the tiling alone.  ksw() states them as closed forms:
+  K1 `if (j == qlen)` (:155) tests the j that the tiled column loops (:113-152) left behind.
+     There are regs = (qlen >> 3) + 1 query words (:56), so the last word starts at column
+     L = (qlen >> 3) * 8, with L <= qlen <= L + 7.  `continue` (j < beg, :120) and `break`
+     (j >= end, :122) leave only the inner loop: every word before the last one ends with
+     j >= end or at its eighth base and the outer loop goes on.  In the last word j runs
+     L, L+1, ..; beg <= end (the scans :178-183 keep it so), so every j < beg is also < end
+     and the first j >= end breaks: j = max(L, end), which exists since end <= qlen <= L + 7.
+     Hence j == qlen  <=>  end == qlen or L == qlen:
+         reached_end = (end == qlen) | (qlen % 8 == 0)
+     A query whose length is a multiple of 8 takes the gscore update in *every* row it
+     computes, whatever end is, with h1 = H(i, end - 1), the last cell the row computed (or
+     the row's first-column value when beg == end and no cell was computed).
+  K2 `if (m == 0) break;` (:159) leaves the loop over the 8 bases of the current target word
+     (:93), not the loop over the words (:89).  The rows left in that word are not computed;
+     row 8 * (word + 1) starts again with beg, end and eh as the dead row left them: the
+     trimming scans were skipped, eh[beg+1..end].h hold the dead row's H, eh[end] = (h1, 0)
+     (:153-154 come before the break, and so does K1's update).  As state per pair:
+         skipping |= (m == 0);   skipping = False where i % 8 == 0;   a row runs iff
+         i < tlen and not skipping
+     (`i >= tlen` (:98) is the same break, but every later word starts past tlen too.)
+  K3 `mj = m > h ? mj : j` (:140): with m starting at 0 every cell with h >= m moves mj, so
+     mj is the *last* column of [beg, end) that holds the row's maximum; max_j takes it
+     only when m > max strictly (:161), so among rows the *first* one wins.
+The trimming scans (:178-183) as a closed form: with Z = {j in [beg, end] : eh[j] != (0, 0)},
+beg' = min(Z) and end' = min(max(Z) + 2, qlen); Z empty: beg' = end, end' = min(end + 1, qlen).
+Entries right of end keep whatever an earlier row (or the first row, :78-81) left there and
+are read again when end grows, so the whole eh array is kept.  Query pads are never read
+(j < end <= qlen), target pad rows are skipped (:98), N scores by the LOCAL rule (Q6).
+Cost: rows x columns numpy steps, so ksw() is meant for max(ql), max(tl) <= 256; longer
+shapes (the LDS block sizes of the 8-bit level) are checked against the oracle only.
 """
 from __future__ import annotations
 
@@ -278,6 +312,92 @@ def banded(batch, k_band, a=1, b=4, o=6, e=1, n_code=0x4E, npen=None):
             maxX = np.where(ok & (prev < maxHH), r, maxX)
             prev = np.where(ok, np.maximum(maxHH, prev), prev)
     return {"score": maxHH, "q_end": maxX, "t_end": maxY}
+
+
+def ksw(batch, seed, a=1, b=4, o=6, e=1, n_code=0x4E, npen=None, state=False):
+    """gasal_ksw_kernel<B> (ksw_kernel_template.h:47-199), rules K1-K3 of the module docstring.
+    All pairs advance one target row together; eh is kept as H[j], E[j] vectors over the pairs,
+    beg / end / skipping as arrays.  seed: the h0 of every pair (uint32; compared unsigned with
+    o + e at :79).  state=True adds, per pair, how often each rule decided something:
+      k1_rows    rows that took the gscore update with end < qlen (qlen % 8 == 0 only)
+      k2_resumed rows with m == 0 that were followed by a computed row (of a later word)
+      k3_ties    rows whose maximum set max_j while it stood in two or more columns
+      margin     max - gscore at the end (the clip rule :188 compares it with PEN_CLIP5 = 5)"""
+    q, _ = _codes(batch.q_data, batch.q_offsets, batch.q_lens, n_code)
+    t, _ = _codes(batch.t_data, batch.t_offsets, batch.t_lens, n_code)
+    ql, tl = batch.q_lens.astype(np.int64), batch.t_lens.astype(np.int64)
+    n = len(ql)
+    h0 = np.asarray(seed, np.uint32).astype(np.int64) if seed is not None else np.zeros(n, np.int64)
+    nval, oe = n_code & 15, o + e
+    Q = int(ql.max(initial=1))
+    pn = np.arange(n)
+    H = np.zeros((Q + 2, n), np.int64)
+    E = np.zeros((Q + 2, n), np.int64)
+    H[0] = h0                                                   # :78-81
+    H[1] = np.where(h0 > (oe & 0xFFFFFFFF), h0 - oe, 0)
+    going = np.ones(n, bool)
+    for j in range(2, Q + 1):
+        going &= (j <= ql) & (H[j - 1] > e)
+        H[j] = np.where(going, H[j - 1] - e, 0)
+    mx = h0.copy()
+    mx_i = np.full(n, -1, np.int64); mx_j = mx_i.copy(); mx_ie = mx_i.copy(); gs = mx_i.copy()
+    beg = np.zeros(n, np.int64); end = ql.copy()
+    skipping = np.zeros(n, bool)
+    k1 = np.zeros(n, np.int64); k2 = k1.copy(); k3 = k1.copy(); pending = np.zeros(n, bool)
+    cols = np.arange(Q + 2)[:, None]
+    for i in range(int(tl.max(initial=0))):
+        if i % 8 == 0:
+            skipping[:] = False                                 # K2
+        act = (i < tl) & ~skipping
+        if not act.any():
+            continue
+        k2 += pending & act
+        pending &= ~act
+        gb = t[:, i]
+        h1 = np.where(beg == 0, np.maximum(h0 - (o + e * (i + 1)), 0), 0)      # :105-110
+        f = np.zeros(n, np.int64); m = f.copy(); mj = np.full(n, -1, np.int64); cnt = f.copy()
+        for j in range(int(beg[act].min()), int(end[act].max())):
+            on = act & (beg <= j) & (j < end)
+            M = H[j]
+            M = np.where(M != 0, M + _sub(q[:, j], gb, a, b, nval, npen, True), 0)   # :136
+            h = np.maximum(np.maximum(M, E[j]), f)
+            H[j] = np.where(on, h1, H[j])                       # H(i, j-1) for the next row
+            h1 = np.where(on, h, h1)
+            cnt = np.where(on & (h > m), 1, cnt + (on & (h == m)))
+            keep = m > h                                        # K3: >= moves mj
+            mj = np.where(on & ~keep, j, mj)
+            m = np.where(on & ~keep, h, m)
+            open_ = np.maximum(M - oe, 0)
+            E[j] = np.where(on, np.maximum(E[j] - e, open_), E[j])
+            f = np.where(on, np.maximum(f - e, open_), f)
+        a_idx = pn[act]
+        H[end[act], a_idx] = h1[act]; E[end[act], a_idx] = 0    # :153-154
+        reached = act & ((end == ql) | (ql % 8 == 0))           # K1
+        k1 += reached & (end != ql)
+        upd = reached & ~(gs > h1)
+        mx_ie = np.where(upd, i, mx_ie)
+        gs = np.where(upd, h1, gs)
+        dead = act & (m == 0)
+        skipping |= dead                                        # K2
+        pending |= dead
+        live = act & ~dead
+        up = live & (m > mx)
+        k3 += up & (cnt >= 2)
+        mx_i = np.where(up, i, mx_i); mx_j = np.where(up, mj, mx_j); mx = np.where(up, m, mx)
+        # :178-183: the first and last entry of [beg, end] other than (0, 0)
+        nz = ((H != 0) | (E != 0)) & (cols >= beg) & (cols <= end)
+        some = nz.any(axis=0)
+        first = np.where(some, nz.argmax(axis=0), end)
+        last = np.where(some, Q + 1 - nz[::-1].argmax(axis=0), end - 1)
+        beg = np.where(live, first, beg)
+        end = np.where(live, np.minimum(last + 2, ql), end)
+    local_end = (gs <= 0) | (gs <= mx - 5)                      # :188, PEN_CLIP5
+    out = {"score": np.where(local_end, mx, gs).astype(np.int32),
+           "q_end": np.where(local_end, mx_j + 1, ql).astype(np.int32),
+           "t_end": np.where(local_end, mx_i + 1, mx_ie + 1).astype(np.int32)}
+    if state:
+        out.update(k1_rows=k1, k2_resumed=k2, k3_ties=k3, margin=mx - gs)
+    return out
 
 
 class _Pairs:

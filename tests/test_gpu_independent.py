@@ -258,3 +258,82 @@ def test_pairhmm_underflow_class(engine):
     print(f"denormal range: {int(den.sum())} pairs, gpu returns 0 for {int((g[den] == 0).sum())}, "
           f"oracle for {int((O.pairhmm(*args)[den] == 0).sum())}")
     assert np.all(np.abs(g[den] - f[den]) <= FLT_MIN)
+
+
+# ---------------------------------------------------------------------- KSW ----
+# (query length range, seed range, environment, gap_open override, the form meant)
+KSW_FORMS = {
+    "ksw16_64": ((1, 40), (0, 41), {}, None),
+    "ksw16_96": ((60, 90), (0, 41), {}, None),
+    "ksw16_160": ((140, 158), (0, 41), {}, None),
+    "ksw16_global": ((160, 254), (0, 2), {}, None),
+    "level0_lds": ((1, 40), (0, 41), {"GASALX_KSW16": "0"}, None),
+    "level0_global": ((1, 40), (0, 41), {"GASALX_KSW16": "0", "GASALX_KSW_LDS": "0"}, None),
+    "level1": ((100, 200), (300, 60001), {}, None),
+    "level2": ((100, 200), (65000, 66001), {}, None),
+    "level2_negative_gap": ((100, 200), (0, 41), {}, -1),
+}
+KSW16_FORMS = ("ksw16_64", "ksw16_96", "ksw16_160", "ksw16_global")
+_KSW_REF = {}
+
+
+def _ksw_case(form, sc, alphabet):
+    """The batch of one form and its independent.ksw() answer, computed once.  Queries are
+    A/C/G/T only; an ACGTN case puts N into a third of the targets.  ksw16 takes a pair when
+    seed + match * min(ql, tl) <= 255, so at match = 2 the targets of the long ksw16 forms
+    are cut to (255 - largest seed) // 2 bases: the instance follows the queries alone."""
+    key = (form, sc, alphabet)
+    if key not in _KSW_REF:
+        (qlo, qhi), srange, env, o_neg = KSW_FORMS[form]
+        a, bb, o, e = sc
+        if o_neg is not None:
+            o = o_neg
+        rng = np.random.default_rng(zlib.crc32(repr(key).encode()) & 0xFFFF)
+        tlo, thi = qlo, qhi
+        if form in KSW16_FORMS:
+            thi = min(thi, (255 - (srange[1] - 1)) // a)
+            tlo = min(tlo, max(1, thi - 30))
+        qs, ts = helpers.random_pairs(rng, 301, qlo, qhi, tlo, thi, related=0.6)
+        if alphabet == b"ACGTN":
+            ts = [bytes(ord("N") if (k % 3 == 0 and rng.random() < 0.1) else c for c in t) for k, t in enumerate(ts)]
+            assert sum(b"N" in t for t in ts) >= 20
+        b = G.Batch.from_pairs(qs, ts)
+        seed = rng.integers(*srange, b.n).astype(np.uint32)
+        _KSW_REF[key] = (qs, ts, b, seed, (a, bb, o, e), env, I.ksw(b, seed, a, bb, o, e))
+    return _KSW_REF[key]
+
+
+@pytest.mark.parametrize("sc", SCORES)
+@pytest.mark.parametrize("form,alphabet", [(f, b"ACGT") for f in KSW_FORMS] + [(f, b"ACGTN") for f in KSW16_FORMS])
+def test_ksw(engine, monkeypatch, form, alphabet, sc):
+    """Every KSW kernel form against independent.ksw() directly.  describe_plan names the
+    family only, so the form is asserted from the inputs by the dispatcher's documented rule
+    (helpers.ksw_routing): the ksw16 instance from cols = (max_q + 3) & ~1, the entry level
+    from every pair's bound seed + step * min(ql, tl) against 255 and 65535."""
+    qs, ts, b, seed, sc, env, ref = _ksw_case(form, sc, alphabet)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    kw = dict(algo=G.KSW, **_kw(sc))
+    assert G.describe_plan(G.make_params(**kw), int(b.q_lens.max()), int(b.t_lens.max())) == "generic_ksw"
+    r = helpers.ksw_routing(qs, ts, seed, sc, env)
+    cols = (r["max_q"] + 3) & ~1
+    if form in KSW16_FORMS:
+        assert r["taken"].all(), (form, int((~r["taken"]).sum()), int(r["bound"].max()))
+        want = {"ksw16_64": 64, "ksw16_96": 96, "ksw16_160": 160, "ksw16_global": 0}[form]
+        assert r["inst"] == want, (form, r["max_q"], cols)
+        assert {"ksw16_64": cols <= 64, "ksw16_96": 64 < cols <= 96, "ksw16_160": 96 < cols <= 160,
+                "ksw16_global": cols > 160 and r["max_q"] <= 254}[form]
+    else:
+        assert not r["taken"].any()
+        if form.startswith("level0"):
+            assert (r["level"] == 0).all() and r["inst"] is None
+            assert r["tpb"] == (256 if form == "level0_lds" else 0)
+        elif form == "level1":
+            assert (r["level"] == 1).all() and r["bound"].min() > 255 and r["bound"].max() <= 65535
+        elif form == "level2":
+            # the seed range straddles 65535: no pair fits 8 bits, most need the int2 entries
+            assert r["bound"].min() > 255 and (r["level"] == 2).sum() >= b.n // 2
+        else:
+            assert sc[2] < 0 and (r["level"] == 2).all()
+    _exact(engine.align_host(b, G.make_params(**kw), seed_scores=seed), ref, ("score", "q_end", "t_end"),
+           f"KSW {form} {sc} {alphabet}")

@@ -17,6 +17,7 @@ import pytest
 
 import gasal_ffi as G
 import helpers
+import independent as I
 import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -259,3 +260,161 @@ def test_semiglobal_short_pairs_every_head(engine, head):
     b = edge_batch(_seed("short", head), 900, 150, 182)
     assert plan(kw, 150, 182).startswith("wavefront16_semi")
     check(engine, b, kw)
+
+
+# ------------------------------------------------------------------ KSW ----
+# Edges of the KSW kernel forms (dispatch.hip, KSW branch): the ksw16 instances by query
+# length, its 8-bit value window, the lane-partner rule and a last lane of one pair, the
+# entry levels at 255 / 65535, the LDS block sizes, and the reference's trimming rules.
+# Every batch covers more than one 256-thread block of ksw16 lanes and ends in a partial
+# lane (515 pairs); helpers.ksw_routing restates the dispatcher's rule, and each test asserts
+# from its inputs the form it means to reach.
+KSW_FIELDS = ("score", "q_end", "t_end")
+KSW16_OFF = {"GASALX_KSW16": "0"}
+
+
+def ksw_check(engine, monkeypatch, qs, ts, seed, scores=(1, 4, 6, 1), envs=({},), ref=True):
+    """GPU == oracle (== independent.ksw when every length is <= 256) under every environment."""
+    a, bb, o, e = scores
+    kw = dict(algo=G.KSW, match=a, mismatch=bb, gap_open=o, gap_extend=e)
+    b = G.Batch.from_pairs(qs, ts)
+    seed = np.asarray(seed, np.uint32)
+    assert plan(kw, int(b.q_lens.max()), int(b.t_lens.max())) == "generic_ksw"
+    refs = {"oracle": O.align(b, O.make_params(**kw), seed_scores=seed)}
+    if ref and max(int(b.q_lens.max()), int(b.t_lens.max())) <= 256:
+        refs["independent"] = I.ksw(b, seed, a, bb, o, e, state=True)
+    for env in envs:
+        with monkeypatch.context() as m:
+            for k, v in env.items():
+                m.setenv(k, v)
+            g = engine.align_host(b, G.make_params(**kw), seed_scores=seed)
+        for name, r in refs.items():
+            for f in KSW_FIELDS:
+                bad = np.nonzero(g[f] != r[f])[0]
+                assert bad.size == 0, (f"{f} {env}: {bad.size}/{b.n} differ from {name}; first #{bad[0]}: gpu={g[f][bad[0]]} "
+                                       f"{name}={r[f][bad[0]]} q={qs[bad[0]]} t={ts[bad[0]]} seed={seed[bad[0]]}")
+    return b, seed, refs
+
+
+def _ksw_len_batch(rng, n, max_q, spread, tlo, thi):
+    """n related pairs; pair 0 and a few more have the longest query, the rest are shorter."""
+    qs, ts = [], []
+    for k in range(n):
+        ql = max_q if k % 97 == 0 else int(rng.integers(max(1, max_q - spread), max_q + 1))
+        q = helpers.random_seq(rng, ql)
+        tl = int(rng.integers(max(1, tlo), thi + 1))
+        t = (helpers.mutate(rng, q) + helpers.random_seq(rng, tl))[:tl] if k % 4 else helpers.random_seq(rng, tl)
+        qs.append(q); ts.append(t)
+    return qs, ts
+
+
+@pytest.mark.parametrize("max_q,inst", [(61, 64), (62, 64), (63, 96), (94, 96), (95, 160), (158, 160), (159, 0),
+                                        (254, 0), (255, None)])
+def test_ksw16_instance_boundaries(engine, monkeypatch, max_q, inst):
+    # cols = (max_q + 3) & ~1 picks ksw16<64> / <96> / <160> / the global array; 254 is the
+    # longest query ksw16 takes, one query of 255 turns it off for the whole batch
+    rng = np.random.default_rng(_seed("ksw16 inst", max_q))
+    qs, ts = _ksw_len_batch(rng, 515, max_q, 30, max_q - 10, max_q + 10)
+    seed = rng.integers(0, max(1, min(41, 256 - max_q)), len(qs))
+    r = helpers.ksw_routing(qs, ts, seed)
+    assert r["max_q"] == max_q and r["inst"] == inst
+    assert sum(len(q) == max_q for q in qs) >= 1 and sum(len(q) < max_q for q in qs) > 400
+    if inst is None:
+        assert not r["taken"].any() and (r["level"] == 0).sum() > 100
+    else:
+        assert r["taken"].all(), int(r["bound"].max())
+    ksw_check(engine, monkeypatch, qs, ts, seed, envs=({}, KSW16_OFF))
+
+
+def _identical_at_bound(rng, n, a, top):
+    """Identical pairs of length L with seed = top - a * L (lanes 0, 2, ..: bound and reached
+    score both exactly top) or one more (lanes 1, 3, ..); the two pairs of a lane are of one
+    kind, so that a declined pair does not pull a taken one with it."""
+    qs, sd, over = [], [], []
+    for k in range(n):
+        L = int(rng.integers(1, (254 // a if top < 256 else 128) + 1))
+        qs.append(helpers.random_seq(rng, L))
+        over.append((k // 2) % 2)
+        sd.append(top - a * L + over[-1])
+    return qs, np.array(sd, np.int64), np.array(over, bool)
+
+
+@pytest.mark.parametrize("a", [1, 2])
+def test_ksw_value_window_edge_255(engine, monkeypatch, a):
+    # the 8-bit entries (ksw16's biased f16 halves, then level 0 in LDS and in the global
+    # array) holding 255, the largest value they can, beside pairs one past it (level 1) in
+    # the same waves
+    sc = (a, 4, 6, 1)
+    qs, seed, over = _identical_at_bound(np.random.default_rng(_seed("ksw 255", a)), 515, a, 255)
+    envs = ({}, KSW16_OFF, {"GASALX_KSW16": "0", "GASALX_KSW_LDS": "0"})
+    assert over.any() and (~over).any()
+    for env in envs:
+        r = helpers.ksw_routing(qs, qs, seed, sc, env)
+        assert np.array_equal(r["bound"], 255 + over) and np.array_equal(r["level"], over.astype(int))
+        if env:
+            assert not r["taken"].any()
+            assert r["tpb"] == (0 if "GASALX_KSW_LDS" in env else 256 if r["max_q"] <= 158 else 128)
+        else:
+            assert np.array_equal(r["taken"], ~over) and r["inst"] == (0 if a == 1 else 160)
+    b, _, refs = ksw_check(engine, monkeypatch, qs, qs, seed, sc, envs=envs)
+    # the reached score is the bound itself, reported at the end of the query
+    assert np.array_equal(refs["independent"]["score"], 255 + over)
+
+
+@pytest.mark.parametrize("a", [1, 2])
+def test_ksw_level_edge_65535(engine, monkeypatch, a):
+    # 16-bit entries holding 65535 (level 1) beside pairs one past it (level 2, int2 entries)
+    sc = (a, 4, 6, 1)
+    qs, seed, over = _identical_at_bound(np.random.default_rng(_seed("ksw 65535", a)), 515, a, 65535)
+    r = helpers.ksw_routing(qs, qs, seed, sc)
+    assert not r["taken"].any() and np.array_equal(r["level"], 1 + over) and over.any() and (~over).any()
+    b, _, refs = ksw_check(engine, monkeypatch, qs, qs, seed, sc)
+    assert np.array_equal(refs["independent"]["score"], 65535 + over)
+
+
+@pytest.mark.parametrize("n", [1, 2, 3, 129, 513, 515])
+def test_ksw16_lane_partner_and_last_lane(engine, monkeypatch, n):
+    # one non-ACGT query sends both pairs of its lane to the levels; an N in the target does
+    # not.  Odd n: the last lane holds one pair
+    rng = np.random.default_rng(_seed("ksw16 lane", n))
+    qs, ts = helpers.random_pairs(rng, n, 2, 40, 2, 40, related=0.7)
+    seed = rng.integers(0, 41, n)
+    with_n = lambda s: s[: len(s) // 2] + b"N" + s[len(s) // 2 + 1:]
+    qn = [with_n(q) if k % 2 == 0 else q for k, q in enumerate(qs)]
+    tn = [with_n(t) if k % 2 == 0 else t for k, t in enumerate(ts)]
+    r = helpers.ksw_routing(qn, ts, seed)
+    assert r["inst"] == 64 and not r["taken"].any() and (r["level"] == 0).all()
+    ksw_check(engine, monkeypatch, qn, ts, seed)
+    r = helpers.ksw_routing(qs, tn, seed)
+    assert r["inst"] == 64 and r["taken"].all()
+    ksw_check(engine, monkeypatch, qs, tn, seed, envs=({}, KSW16_OFF))
+    if n >= 129:
+        # N in the odd pairs' queries only from lane 32 on: taken and declined lanes in one batch
+        qm = [q if k < 64 else x for k, (q, x) in enumerate(zip(qs, qn))]
+        r = helpers.ksw_routing(qm, ts, seed)
+        assert r["taken"][:64].all() and not r["taken"][64:].any()
+        ksw_check(engine, monkeypatch, qm, ts, seed)
+
+
+@pytest.mark.parametrize("max_q,tpb", [(158, 256), (159, 128), (318, 128), (319, 64), (638, 64), (639, 0)])
+def test_ksw_level0_lds_block_sizes(engine, monkeypatch, max_q, tpb):
+    # 8-bit entries in LDS: two blocks of 256 / 128 / 64 threads x (max_q + 2) entries must fit
+    # 160 KiB, past 638 the global array.  Short targets and small seeds keep every bound
+    # <= 255 so that level 0 really runs the long queries.  Oracle only (lengths > 256).
+    rng = np.random.default_rng(_seed("ksw lds", max_q))
+    qs, ts = _ksw_len_batch(rng, 130, max_q, 40, 100, 200)
+    seed = rng.integers(0, 41, len(qs))
+    r = helpers.ksw_routing(qs, ts, seed, env=KSW16_OFF)
+    assert r["max_q"] == max_q and r["tpb"] == tpb and (r["level"] == 0).all() and not r["taken"].any()
+    ksw_check(engine, monkeypatch, qs, ts, seed, envs=(KSW16_OFF,), ref=max_q <= 256)
+
+
+@pytest.mark.parametrize("name", sorted(helpers.ksw_rule_batches()))
+def test_ksw_trimming_rules(engine, monkeypatch, name):
+    # the constructed batches of test_independent.test_ksw_constructed_rules (rules K1-K3 of
+    # independent.py, the clip rule, seed 0, length 1) through ksw16 and through the levels
+    qs, ts, sd, sc = helpers.ksw_rule_batches()[name]
+    r = helpers.ksw_routing(qs, ts, sd, sc)
+    assert r["taken"].sum() > len(qs) // 2 and r["inst"] == 64, (int(r["taken"].sum()), r["inst"])
+    b, seed, refs = ksw_check(engine, monkeypatch, qs, ts, sd, sc, envs=({}, KSW16_OFF))
+    assert helpers.ksw_rule_fired(name, b, seed, refs["independent"]) >= 10

@@ -1,6 +1,6 @@
 """Hand-derived known answers (tests/golden/hand_kats.json) for the paths the survey's
 KATs do not cover: LOCAL WITH_START (Q8), semi-global end conventions (Q3, Q10, Q11),
-local second-best (Q13), KSW (Q16), banded and the reverse / complement pre-op.  Each
+local second-best (Q13), KSW (Q16, Q23 and the clip rule), banded and the reverse / complement pre-op.  Each
 case's derivation is written out in the fixture from the cited reference lines, so it
 checks the oracle and the HIP kernels without trusting either (the oracle and the
 thread-per-pair kernels are close restatements of each other)."""

@@ -247,3 +247,69 @@ def test_banded(k_band, lens):
             # the whole matrix is inside the band; H-based and diag-based E/F (Q4) agree
             # while mismatch < open + 2*extend (an I next to a D never beats an X)
             _same(I.local(b, a, bb, o, e), ref, ("score", "q_end", "t_end"))
+
+
+# --------------------------------------------------------------------- KSW ----
+KSW_FIELDS = ("score", "q_end", "t_end")
+
+
+def _ksw_both(qs, ts, seed, sc, npen=None):
+    a, bb, o, e = sc
+    b = G.Batch.from_pairs(qs, ts)
+    seed = np.asarray(seed, np.uint32)
+    kw = dict(match=a, mismatch=bb, gap_open=o, gap_extend=e)
+    if npen is not None:
+        kw["n_penalty"] = npen
+    ref = O.align(b, O.make_params(algo=O.KSW, **kw), seed_scores=seed)
+    r = I.ksw(b, seed, a, bb, o, e, npen=npen, state=True)
+    _same(r, ref, KSW_FIELDS)
+    return b, seed, r
+
+
+@pytest.mark.parametrize("seeds", [(0, 5), (0, 60), (200, 300)])
+@pytest.mark.parametrize("lens", [(1, 40), (100, 160)])
+@pytest.mark.parametrize("alphabet", [b"ACGT", b"ACGTN"])
+def test_ksw_random(alphabet, lens, seeds):
+    """The oracle's k_ksw against independent.ksw() (rules K1-K3 as closed forms) on the
+    shapes of test_gpu_parity.test_ksw_trimming, both score sets and an N penalty."""
+    rng = np.random.default_rng(lens[0] * 7 + seeds[1] + len(alphabet))
+    qs, ts = helpers.random_pairs(rng, 200, *lens, *lens, related=0.6, alphabet=alphabet)
+    seed = rng.integers(*seeds, len(qs)).astype(np.uint32)
+    for sc in SCORES[:2]:
+        _ksw_both(qs, ts, seed, sc)
+    if alphabet == b"ACGTN":
+        _ksw_both(qs, ts, seed, SCORES[0], npen=2)
+
+
+def test_ksw_every_length_residue():
+    """Every query length 1..33 against every target length 1..33: all residues mod 8 on
+    both axes (regs = (len >> 3) + 1 words, K1's extra word at the multiples of 8)."""
+    rng = np.random.default_rng(0x3333)
+    qs, ts = [], []
+    for ql in range(1, 34):
+        for tl in range(1, 34):
+            q = helpers.random_seq(rng, ql)
+            t = (helpers.mutate(rng, q) + helpers.random_seq(rng, tl))[:tl] if (ql + tl) % 3 else helpers.random_seq(rng, tl)
+            qs.append(q); ts.append(t)
+    seed = rng.integers(0, 30, len(qs)).astype(np.uint32)
+    for sc in SCORES[:2] + [(1, 4, 2, 1)]:
+        b, _, r = _ksw_both(qs, ts, seed, sc)
+    assert set(b.q_lens) == set(range(1, 34)) and set(b.t_lens) == set(range(1, 34))
+
+
+KSW_RULES = helpers.ksw_rule_batches()
+
+
+@pytest.mark.parametrize("name", sorted(KSW_RULES))
+def test_ksw_constructed_rules(name):
+    qs, ts, sd, sc = KSW_RULES[name]
+    b, seed, r = _ksw_both(qs, ts, sd, sc)
+    fired = helpers.ksw_rule_fired(name, b, seed, r)
+    print(f"{name}: rule decided {fired} of {b.n} pairs")
+    assert fired >= 10, (name, fired)
+    if name == "clip":
+        # gscore == max - 5 reports the local end, max - 4 the end of the query (:188)
+        assert np.all(r["q_end"][r["margin"] == 5] != b.q_lens[r["margin"] == 5])
+        assert np.all(r["q_end"][(r["margin"] == 4) & (r["score"] > 4)] == b.q_lens[(r["margin"] == 4) & (r["score"] > 4)])
+    if name == "seed0":
+        assert not r["score"].any() and not r["q_end"].any() and not r["t_end"].any()
