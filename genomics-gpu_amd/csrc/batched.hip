@@ -181,14 +181,8 @@ int nv_score_device(const gasalx_nv_aligner &al, uint32_t n, const gasalx_nv_str
             D.lds_cols = nv16_cols(shared, shared ? A.tlen0 : max_t, sh->G);
             const size_t lds16 = nv16_lds(shared, shared ? A.tlen0 : max_t, sh->G);
             if (lds16 <= 160 * 1024) {
-                if (lds16 > 64 * 1024) {
-                    hipError_t e = hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                       (int)lds16);
-                    if (e != hipSuccess) { set_error(hipGetErrorString(e)); return GASALX_EDEVICE; }
-                }
                 const uint32_t per_block = 8 * (64 / sh->G);   // two pairs per lane group
-                hipLaunchKernelGGL(fn, dim3((n + per_block - 1) / per_block), dim3(256), lds16, st, D);
-                hipError_t e = hipGetLastError();
+                hipError_t e = launch_lds(fn, dim3((n + per_block - 1) / per_block), dim3(256), lds16, st, D);
                 if (e != hipSuccess) { set_error(hipGetErrorString(e)); return GASALX_EDEVICE; }
                 return GASALX_OK;
             }
@@ -197,13 +191,8 @@ int nv_score_device(const gasalx_nv_aligner &al, uint32_t n, const gasalx_nv_str
     NvFn fn = sh ? nv_lookup(gotoh, al.type, mask, sh->G, sh->R) : nullptr;
     if (fn) {
         A.lds_stride = stride;
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) { set_error(hipGetErrorString(e)); return GASALX_EDEVICE; }
-        }
         const uint32_t per_block = 4 * (64 / sh->G);
-        hipLaunchKernelGGL(fn, dim3((n + per_block - 1) / per_block), dim3(256), lds, st, A);
-        hipError_t e = hipGetLastError();
+        hipError_t e = launch_lds(fn, dim3((n + per_block - 1) / per_block), dim3(256), lds, st, A);
         if (e != hipSuccess) { set_error(hipGetErrorString(e)); return GASALX_EDEVICE; }
         return GASALX_OK;
     }

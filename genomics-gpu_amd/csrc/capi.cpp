@@ -192,8 +192,6 @@ int gasalx_align_device(gasalx_engine *eng, const gasalx_params *params, const g
 
 namespace {
 
-uint32_t pad8u(uint32_t x) { return (x + 7u) & ~7u; }
-
 
 // Sequences laid out back to back from offset 0 (what gasal_host_batch_fill
 // produces): chunks of pairs then own contiguous byte ranges.
@@ -201,7 +199,7 @@ bool contiguous(const uint32_t *off, const uint32_t *len, uint32_t n, uint32_t b
     uint64_t at = 0;
     for (uint32_t i = 0; i < n; i++) {
         if (off[i] != at) return false;
-        at += pad8u(len[i]);
+        at += gx::pad8(len[i]);
     }
     return at == bytes;
 }
@@ -257,8 +255,8 @@ int align_host_pipelined(gasalx_engine *eng, const gasalx_params *params, const 
         const uint32_t i1 = std::min(n, i0 + chunk), m = i1 - i0;
         HostSlot &s = eng->slot[k];
         if ((rc = drain(k))) return rc;
-        const uint64_t qlo = hb->q_offsets[i0], qhi = (uint64_t)hb->q_offsets[i1 - 1] + pad8u(hb->q_lens[i1 - 1]);
-        const uint64_t tlo = hb->t_offsets[i0], thi = (uint64_t)hb->t_offsets[i1 - 1] + pad8u(hb->t_lens[i1 - 1]);
+        const uint64_t qlo = hb->q_offsets[i0], qhi = (uint64_t)hb->q_offsets[i1 - 1] + gx::pad8(hb->q_lens[i1 - 1]);
+        const uint64_t tlo = hb->t_offsets[i0], thi = (uint64_t)hb->t_offsets[i1 - 1] + gx::pad8(hb->t_lens[i1 - 1]);
         // host image of the per-pair region
         size_t at = 0;
         const size_t a_qo = at; at += col(m);

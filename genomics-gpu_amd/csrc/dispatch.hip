@@ -72,17 +72,42 @@ static WfFn wf_lookup(int algo, bool keys, bool tb, int G, int R) {
     return keys ? wf_pick<WF_SEMI, true, false>(G, R) : wf_pick<WF_SEMI, false, false>(G, R);
 }
 
-static WfFn wf16_lookup(int algo, bool tb, int G, int R, bool key2 = false, bool stop = false, bool ku16 = false,
-                        bool lrs = false, bool kseg = false, bool tbd = false) {
-    if (algo == WF_LOCAL) return tb ? (tbd ? wf16_pick_r4<WF16_LOCAL_TBD>(G, R) : wf16_pick_r4<WF16_LOCAL_TB>(G, R))
-                                    : key2 ? wf16_pick<WF16_LOCAL_K2>(G, R)
-                                                               : (ku16 || lrs || kseg) ? wf16_local_lookup(G, R, ku16, lrs, kseg)
-                                                                               : wf16_pick<WF_LOCAL>(G, R);
-    if (algo == WF_GLOBAL) return tb ? wf16_pick_r4<WF16_GLOBAL_TB>(G, R) : wf16_pick<WF_GLOBAL>(G, R);
-    return stop ? wf16_pick<WF16_SEMI_STOP>(G, R) : wf16_pick<WF_SEMI>(G, R);
+// which packed kernel of an algo a launch takes
+struct Wf16Variant {
+    bool tb = false;     // traceback flags
+    bool tbd = false;    // LOCAL + traceback in the e-drift frame (WF16_LOCAL_TBD)
+    bool key2 = false;   // LOCAL: second key set (WF16_LOCAL_K2)
+    bool ku16 = false;   // LOCAL e-drift: u16 keys
+    bool lrs = false;    // LOCAL e-drift: the WITH_START reverse pass (lstop)
+    bool kseg = false;   // LOCAL e-drift: keys by step segments
+    bool stop = false;   // SEMI TAIL=TARGET reverse pass
+};
+static WfFn wf16_lookup(int algo, int G, int R, const Wf16Variant &v) {
+    if (algo == WF_LOCAL) return v.tb ? (v.tbd ? wf16_pick_r4<WF16_LOCAL_TBD>(G, R) : wf16_pick_r4<WF16_LOCAL_TB>(G, R))
+                               : v.key2 ? wf16_pick<WF16_LOCAL_K2>(G, R)
+                               : (v.ku16 || v.lrs || v.kseg) ? wf16_local_lookup(G, R, v.ku16, v.lrs, v.kseg)
+                                                             : wf16_pick<WF_LOCAL>(G, R);
+    if (algo == WF_GLOBAL) return v.tb ? wf16_pick_r4<WF16_GLOBAL_TB>(G, R) : wf16_pick<WF_GLOBAL>(G, R);
+    return v.stop ? wf16_pick<WF16_SEMI_STOP>(G, R) : wf16_pick<WF_SEMI>(G, R);
 }
 
-static inline uint32_t pad8(uint32_t x) { return (x + 7u) & ~7u; }
+// ----------------------------------------------------------------------------
+// The packed kernels' launch arithmetic, each formula written once: the planner, the tail shape,
+// the launch and the walk must agree on them, or a packed kernel overflows silently.
+// two pairs per group of G lanes
+static inline uint32_t pairs_per_wave(int G) { return 2 * (64 / G); }
+static inline uint32_t pairs_per_block(int G) { return kWavesPerBlock * (64 / G) * 2; }
+// largest row + column of any cell a G x R launch computes over y8 step-axis positions (packed16_ok)
+static inline int64_t packed_span(int G, int R, int64_t y8) { return (int64_t)G * R + y8 + 2 * G + 8; }
+// LDS per pair slot: uint2 per position, with the odd-step tail and the prefetch; and per block
+static inline uint32_t packed_lds_stride(uint32_t y8, int G) { return ((y8 + 2 * G + 4 + 3) & ~3u) * 8; }
+static inline size_t packed_lds_bytes(uint32_t y8, int G) {
+    return (size_t)kWavesPerBlock * (64 / std::max(G, 1)) * packed_lds_stride(y8, G);
+}
+// band traceback: the window of a lane with R rows and half width w, columns [max(lg*R - w, 0), + R + 2w)
+static inline uint32_t band_window(int R, uint32_t w) { return ((uint32_t)(R + 2 * w) + 3u) & ~3u; }
+// ceil(2^32 / R): the walk's division by R (generic.hpp TbArgs::pk_rmagic)
+static inline uint32_t rmagic(int R) { return (uint32_t)((0x100000000ull + R - 1) / R); }
 
 // packed LOCAL with the round-2 keys H*256 + (255 - column): H <= 255, 512 columns (two key
 // sets above 256), 256 with traceback
@@ -92,6 +117,30 @@ static bool local_key16_ok(const gasalx_params &p, uint32_t mq, uint32_t mt) {
     const int64_t t8 = pad8(mt);
     if (a * std::min(mq, mt) > 255 || t8 > (p.start_pos == 2 ? 256 : 512)) return false;
     return 0x400 + oe + k + 16 + 255 + a + k + 64 <= 0x7BFF;
+}
+
+// LOCAL in the e-drift frame (wavefront16.hpp step_local_dr) for a shape G x R over q8 rows and y8
+// target columns: values B + H + e(r + c) over the shape's span stay in the window (`window`), the
+// top lane's first diagonal B - 2e stays above 0x0400 (`floor`), and the keys H*C + (C-1-c), which
+// rank kc = C + G steps (row k's carry e*k more, wf16_body.inc KA0, taken off after the sweep), fit
+// f16 patterns (`f16`)
+struct LocalDrift {
+    int64_t hmax, kc;
+    bool window, floor, f16;
+};
+static LocalDrift local_drift_frame(const gasalx_params &p, int64_t q8, int64_t y8, int G, int R) {
+    const int64_t a = std::max(p.match, 0), e = p.gap_extend, oe = (int64_t)p.gap_open + e;
+    const int64_t k = std::max<int64_t>(p.mismatch, p.has_n_penalty ? p.n_penalty : 0);
+    const int64_t hmax = a * std::min(q8, y8), base = 0x400 + oe + k + 16;
+    const int64_t span = packed_span(G, R, y8);
+    LocalDrift d;
+    d.hmax = hmax;
+    d.kc = y8 + G;
+    d.window = base + hmax + e * span + a + k + 64 <= 0x7BFF;
+    d.floor = base - 2 * e >= 0x400;
+    const int64_t hk = hmax + e * (R - 1);
+    d.f16 = (hk + 1) * d.kc <= 0x7800;
+    return d;
 }
 
 // The packed kernels (wavefront16.hpp) are exact when every stored value stays
@@ -279,13 +328,11 @@ Plan make_plan(const gasalx_params &p, const BatchShape &s, bool has_ops) {
             // last padded column at register R - 1 of lane 7); the plan names the largest
             pl.semi_tq = pl.packed16 && wf_algo == WF_SEMI && p.tail != 2;
             if (pl.semi_tq) { pl.G16 = 8; pl.R16 = (int)(x8 / 8); }
-            const uint32_t words = (y8 + 2 * pl.G16 + 4 + 3) & ~3u;   // odd-step tail + prefetch
-            pl.lds16_stride = words * 8;                               // uint2 per position
-            pl.lds16_bytes = (size_t)kWavesPerBlock * (64 / std::max(pl.G16, 1)) * pl.lds16_stride;
+            pl.lds16_stride = packed_lds_stride(y8, pl.G16);
+            pl.lds16_bytes = packed_lds_bytes(y8, pl.G16);
             if (pl.G16 == 0 || pl.lds16_bytes > 160 * 1024) pl.packed16 = false;
             if (pl.packed16 && wf_algo != WF_LOCAL)   // the value window over the chosen shape's cells
-                pl.packed16 = packed16_ok(p, wf_algo, s.max_q, s.max_t, &pl.vmin,
-                                          (int64_t)pl.G16 * pl.R16 + y8 + 2 * pl.G16 + 8);
+                pl.packed16 = packed16_ok(p, wf_algo, s.max_q, s.max_t, &pl.vmin, packed_span(pl.G16, pl.R16, y8));
             pl.key2 = wf_algo == WF_LOCAL && y8 > 256;
             // LOCAL score kernels in the e-drift frame (wavefront16.hpp step_local_dr): keys
             // H*C + (C-1-c) with C = the padded target length, as f16 patterns 0x0400 + key
@@ -296,22 +343,17 @@ Plan make_plan(const gasalx_params &p, const BatchShape &s, bool has_ops) {
             // keeps the round-2 kernel (the tests' cross-check of both key forms)
             // LOCAL + traceback takes the e-drift kernel with f16 keys (WF16_LOCAL_TBD) when they fit
             if (wf_algo == WF_LOCAL && env_flag("GASALX_KF16", true)) {
-                const int64_t a = std::max(p.match, 0), e = p.gap_extend, oe = (int64_t)p.gap_open + e;
-                const int64_t k = std::max<int64_t>(p.mismatch, p.has_n_penalty ? p.n_penalty : 0);
-                const int64_t hmax = a * std::min(q8, t8), base = 0x400 + oe + k + 16;
-                const int64_t span = (int64_t)pl.G16 * pl.R16 + y8 + 2 * pl.G16 + 8;
-                const bool frame = base + hmax + e * span + a + k + 64 <= 0x7BFF && base - 2 * e >= 0x400;
+                const LocalDrift d = local_drift_frame(p, q8, y8, pl.G16, pl.R16);
+                const int64_t hmax = d.hmax;
+                const bool frame = d.window && d.floor;
                 // past both, f16 keys by step segments of M = 2^m columns (WF16_LOCAL_SEG): (Hmax +
                 // 1) * M <= 0x7800 for any target length.  GASALX_KSEG=0: never, 2: before u16 keys
                 const int kseg_mode = env_int("GASALX_KSEG", 1);
                 uint32_t mseg = 0;
                 while ((hmax + 1) * (int64_t)(2u << mseg) <= 0x7800 && mseg < 12) ++mseg;   // M = 2^mseg
                 const bool seg_ok = frame && kseg_mode > 0 && mseg >= 2 && y8 <= 0xFFFF;
-                // key range: steps C + G (wavefront16.hpp step_local_dr: keys rank steps)
-                const int64_t kc = (int64_t)y8 + pl.G16;
-                // (wf16_body.inc KA0: row k's keys carry e*k more, taken off after the sweep)
-                const int64_t hk = hmax + e * (pl.R16 - 1);
-                if (frame && (hk + 1) * kc <= 0x7800) {
+                const int64_t kc = d.kc;
+                if (frame && d.f16) {
                     pl.kf16 = y8;
                 } else if (pl.tb) {
                     // (the traceback kernel has f16 keys only)
@@ -344,7 +386,7 @@ Plan make_plan(const gasalx_params &p, const BatchShape &s, bool has_ops) {
                 const int w = std::max(0, env_int("GASALX_TB_BAND_W", 22));
                 pl.tb_band = true;
                 pl.band_w = (uint32_t)w;
-                pl.band_wd = ((uint32_t)(pl.R16 + 2 * w) + 3u) & ~3u;
+                pl.band_wd = band_window(pl.R16, (uint32_t)w);
             }
         }
         const char *an = wf_algo == WF_LOCAL ? (p.start_pos == 1 ? "local_start" : "local")
@@ -430,13 +472,25 @@ struct TailShape {
     size_t lds_bytes = 0;
     int32_t vmin = 0;   // GLOBAL: the value-window bound for the larger span of the two shapes
 };
-static TailShape tail_shape(const Plan &pl, const gasalx_params &p, const WfArgs &A, uint32_t n) {
+// launches that are one shape whatever the plan: the WITH_START reverse passes and the band
+// traceback's fallback launches (their device-side count excludes the tail)
+static bool one_shape_only(const WfArgs &A) { return A.rev || A.n_dev || A.stop || A.lstop; }
+
+// the CU count of the workspace's device, asked once per workspace (256 when the query fails)
+static int device_cus(Workspace &ws) {
+    if (!ws.cus) (void)hipDeviceGetAttribute(&ws.cus, hipDeviceAttributeMultiprocessorCount, ws.device);
+    return ws.cus > 0 ? ws.cus : 256;
+}
+
+// Evaluated once per call, for the main launch A over n pairs (run_wavefront): the launch, the band
+// buffers and the walk all take this one answer.
+static TailShape tail_shape(Workspace &ws, const Plan &pl, const gasalx_params &p, const WfArgs &A, uint32_t n) {
     TailShape t;
     // (read per call, so a test process can compare both)
     const bool on = env_flag("GASALX_TAIL", true);
     const int kextra = env_int("GASALX_TAIL_K", 0);
     if (!on || !pl.packed16 || (pl.tb && !pl.tb_band) || pl.key2 || pl.ku16 || pl.kseg_shift || pl.semi_tq ||
-        A.rev || A.n_dev || A.stop || A.lstop)
+        one_shape_only(A))
         return t;
     int G2 = 0, R2 = 0;
     WfFn fn = nullptr;
@@ -457,25 +511,20 @@ static TailShape tail_shape(const Plan &pl, const gasalx_params &p, const WfArgs
     }
     const int64_t q8 = pad8(pl.max_q), y8 = pad8(pl.max_t);   // LOCAL / GLOBAL: the target is the step axis
     // the second shape's span and keys must fit the value window too (make_plan checked the first's)
-    const int64_t span2 = (int64_t)G2 * R2 + y8 + 2 * G2 + 8;
     if (pl.wf_algo == WF_LOCAL) {
-        const int64_t a = std::max(p.match, 0), e = p.gap_extend, oe = (int64_t)p.gap_open + e;
-        const int64_t k = std::max<int64_t>(p.mismatch, p.has_n_penalty ? p.n_penalty : 0);
-        const int64_t hmax = a * std::min(q8, y8), base = 0x400 + oe + k + 16;
-        const int64_t hk2 = hmax + e * (R2 - 1);   // (KA0 key offsets)
-        if (!(base + hmax + e * span2 + a + k + 64 <= 0x7BFF && (hk2 + 1) * (y8 + G2) <= 0x7800)) return t;
+        const LocalDrift d = local_drift_frame(p, q8, y8, G2, R2);
+        if (!(d.window && d.f16)) return t;
         t.vmin = pl.vmin;
     } else {
         // the window offset for the larger span serves both shapes: their values then sit higher
         // in the same window, whose top packed16_ok checked for that span
-        if (!packed16_ok(p, WF_GLOBAL, pl.max_q, pl.max_t, &t.vmin, std::max<int64_t>(span2, (int64_t)pl.G16 * pl.R16 + y8 + 2 * pl.G16 + 8)))
+        if (!packed16_ok(p, WF_GLOBAL, pl.max_q, pl.max_t, &t.vmin,
+                         std::max(packed_span(G2, R2, y8), packed_span(pl.G16, pl.R16, y8))))
             return t;
         t.vmin = std::max(t.vmin, pl.vmin);
     }
-    static int cus = 0;
-    if (!cus) { int d = 0; (void)hipGetDevice(&d); (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, d); }
-    const uint64_t slots = (uint64_t)wf16_waves(pl.wf_algo, pl.R16) * 4 * (cus > 0 ? cus : 256);
-    const uint32_t ppw = 2 * (64 / pl.G16), ppb = kWavesPerBlock * ppw;
+    const uint64_t slots = (uint64_t)wf16_waves(pl.wf_algo, pl.R16) * 4 * device_cus(ws);
+    const uint32_t ppw = pairs_per_wave(pl.G16), ppb = pairs_per_block(pl.G16);
     const uint64_t waves = (n + ppw - 1) / ppw;
     const uint64_t rounds = waves / slots;
     if (rounds < 2 + (uint64_t)std::max(kextra, 0)) return t;
@@ -483,30 +532,47 @@ static TailShape tail_shape(const Plan &pl, const gasalx_params &p, const WfArgs
     t.b0 = (uint32_t)(long_waves / kWavesPerBlock);
     t.p0 = t.b0 * ppb;
     if (t.p0 >= n) return TailShape();
-    t.ppb = kWavesPerBlock * 2 * (64 / G2);
-    const uint32_t words = ((uint32_t)y8 + 2 * G2 + 4 + 3) & ~3u;   // as make_plan's, for G2
-    t.lds_stride = words * 8;
-    t.lds_bytes = (size_t)kWavesPerBlock * (64 / G2) * t.lds_stride;
+    t.ppb = pairs_per_block(G2);
+    t.lds_stride = packed_lds_stride((uint32_t)y8, G2);
+    t.lds_bytes = packed_lds_bytes((uint32_t)y8, G2);
     t.fn = fn;
     t.G2 = G2;
     t.R2 = R2;
     return t;
 }
 
-// Launch the wavefront kernel(s) of plan `pl` over one device batch: the packed
-// kernel first when the plan has one (it flags the blocks it aligned), then the
-// int32 kernel, which aligns exactly the pairs of the declined blocks.
-static int launch_wavefront(Workspace &ws, const Plan &pl, const gasalx_params &p, const WfArgs &base,
-                            hipStream_t st) {
-    WfArgs A = base;
-    const uint32_t n = A.n;
+// the scoring fields every argument struct of the DP kernels and the walk shares
+template <class Args>
+static void fill_scoring(Args &A, const gasalx_params &p) {
     A.a = p.match; A.b = p.mismatch; A.o = p.gap_open; A.e = p.gap_extend;
     A.nval = p.n_code & 0xF;
     A.has_npen = p.has_n_penalty; A.npen = p.n_penalty;
+}
+// what the wavefront launches of one plan share (the int32 kernel's; the packed copy overrides its own)
+static void wf_common(WfArgs &A, const gasalx_params &p, const Plan &pl) {
+    fill_scoring(A, p);
     A.head = p.head; A.tail = p.tail;
     A.lds_stride = pl.lds_stride;
     A.force_exact = (p.mismatch <= 0 || (p.has_n_penalty && p.n_penalty < 0)) ? 1 : 0;
     A.one = 0x00010001u;
+}
+
+// the int32 kernel over the blocks the packed launches declined (A.skip), or over every pair
+static int launch_int32(const Plan &pl, WfFn fn, const WfArgs &A, hipStream_t st) {
+    if (!fn) { set_error("no wavefront instance"); return GASALX_EUNSUPPORTED; }
+    HIPCHK(launch_lds(fn, dim3(wf_grid(A.n, pl.G, A.skip != nullptr)), dim3(kBlock), pl.lds_bytes, st, A));
+    return GASALX_OK;
+}
+
+// Launch the wavefront kernel(s) of plan `pl` over one device batch: the packed
+// kernel first when the plan has one (it flags the blocks it aligned), then the
+// int32 kernel, which aligns exactly the pairs of the declined blocks.  main_tail: the
+// main launch's second shape (tail_shape), or none.
+static int launch_wavefront(Workspace &ws, const Plan &pl, const gasalx_params &p, const WfArgs &base,
+                            const TailShape &main_tail, hipStream_t st) {
+    WfArgs A = base;
+    const uint32_t n = A.n;
+    wf_common(A, p, pl);
     if (pl.packed16) {
         // packed kernel first; it marks every block it aligned in ws.misc ...
         WfArgs P16 = A;
@@ -514,11 +580,12 @@ static int launch_wavefront(Workspace &ws, const Plan &pl, const gasalx_params &
         P16.fast16 = 1;
         P16.vmin = pl.vmin;
         P16.kf16 = pl.kf16;
-        const uint32_t ppb16 = kWavesPerBlock * (64 / pl.G16) * 2;
+        const uint32_t ppb16 = pairs_per_block(pl.G16);
         uint32_t grid16 = grid_for(n, ppb16);
         // the launch's last slots on a shorter shape (wavefront16.hpp wf16_mix_kernel), so that its
-        // end is not a fraction of a round of long waves running alone
-        const TailShape tail = tail_shape(pl, p, A, n);
+        // end is not a fraction of a round of long waves running alone; never for a reverse pass or
+        // a fallback launch, whoever calls
+        const TailShape tail = one_shape_only(A) ? TailShape() : main_tail;
         size_t lds16 = pl.lds16_bytes;
         if (tail.fn) {
             P16.tail_b0 = tail.b0; P16.tail_p0 = tail.p0; P16.tail_lds = tail.lds_stride;
@@ -534,14 +601,14 @@ static int launch_wavefront(Workspace &ws, const Plan &pl, const gasalx_params &
             HIPCHK(ws.aux.reserve((size_t)n * 4));
             P16.tbfix = ws.aux.as<int32_t>();
         }
-        WfFn f16 = pl.tb_band ? wf16_pick_r4<WF16_GLOBAL_CP>(pl.G16, pl.R16)
-                              : wf16_lookup(pl.wf_algo, pl.tb, pl.G16, pl.R16, pl.key2, A.stop != nullptr, pl.ku16,
-                                            A.lstop != nullptr && pl.kf16 != 0 && !pl.kseg_shift, pl.kseg_shift != 0,
-                                            pl.tb && pl.kf16 != 0);
+        Wf16Variant v;
+        v.tb = pl.tb; v.tbd = pl.tb && pl.kf16 != 0;
+        v.key2 = pl.key2; v.ku16 = pl.ku16; v.kseg = pl.kseg_shift != 0;
+        v.lrs = pl.wf_algo == WF_LOCAL && !pl.tb && !pl.key2 && A.lstop != nullptr && pl.kf16 != 0 && !pl.kseg_shift;
+        v.stop = A.stop != nullptr;
+        WfFn f16 = pl.tb_band ? wf16_pick_r4<WF16_GLOBAL_CP>(pl.G16, pl.R16) : wf16_lookup(pl.wf_algo, pl.G16, pl.R16, v);
         // WITH_START reverse passes: the register axis sized per block (rclass.hip)
-        const bool lrs = pl.wf_algo == WF_LOCAL && !pl.tb && !pl.key2 && A.lstop != nullptr && pl.kf16 != 0 &&
-                         !pl.kseg_shift;
-        if (A.rev && !pl.tb_band && (A.stop != nullptr || lrs)) {
+        if (A.rev && !pl.tb_band && (v.stop || v.lrs)) {
             const int ra = A.stop ? WF16_SEMI_STOP : pl.ku16 ? WF16_LOCAL_U16_RS : WF16_LOCAL_RS;
             if (WfFn rc = wf16_rclass_lookup(ra, pl.G16, pl.R16)) f16 = rc;
         }
@@ -556,10 +623,7 @@ static int launch_wavefront(Workspace &ws, const Plan &pl, const gasalx_params &
         }
         if (tail.fn) f16 = tail.fn;
         if (!f16) { set_error("no packed wavefront instance"); return GASALX_EUNSUPPORTED; }
-        if (lds16 > 64 * 1024)
-            HIPCHK(hipFuncSetAttribute((const void *)f16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16));
-        hipLaunchKernelGGL(f16, dim3(grid16), dim3(kBlock), lds16, st, P16);
-        HIPCHK(hipGetLastError());
+        HIPCHK(launch_lds(f16, dim3(grid16), dim3(kBlock), lds16, st, P16));
         // ... and the int32 kernel aligns the pairs of the blocks it declined
         A.skip = ws.misc.as<uint8_t>();
         A.skip_ppb = ppb16;
@@ -569,13 +633,49 @@ static int launch_wavefront(Workspace &ws, const Plan &pl, const gasalx_params &
     }
     // (the band path's int32 launch aligns its declined blocks without direction words: the walk sends
     // those pairs to the fallback list, whose launch writes them into the capped buffer)
-    WfFn fn = A.stop ? pick_instance<WfK<WF_SEMI, true, false, true>, SHAPES_R4>(pl.G, pl.R)
-                     : wf_lookup(pl.wf_algo, pl.keys, pl.tb && !pl.tb_band, pl.G, pl.R);
-    if (!fn) { set_error("no wavefront instance"); return GASALX_EUNSUPPORTED; }
-    if (pl.lds_bytes > 64 * 1024)
-        HIPCHK(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes));
-    hipLaunchKernelGGL(fn, dim3(wf_grid(n, pl.G, A.skip != nullptr)), dim3(kBlock), pl.lds_bytes, st, A);
+    return launch_int32(pl, A.stop ? pick_instance<WfK<WF_SEMI, true, false, true>, SHAPES_R4>(pl.G, pl.R)
+                                   : wf_lookup(pl.wf_algo, pl.keys, pl.tb && !pl.tb_band, pl.G, pl.R), A, st);
+}
+
+// The counting sort's arrays in ws.sort_meta: perm[n], then (two) a second array of n words -- the
+// inverse permutation, or the caller's keys --, then the histogram and the cursor, nkeys + 1 words
+// each (sh bytes).  Keys are lengths, bucketed by their 8-base words (start.hpp REV_PLAIN: longest first).
+struct SortMeta {
+    uint32_t *perm, *second, *hist, *cursor;
+    size_t sh;
+};
+static int sort_reserve(Workspace &ws, uint32_t n, uint32_t nkeys, bool two, SortMeta *m) {
+    m->sh = (size_t)(nkeys + 1) * 4;
+    HIPCHK(ws.sort_meta.reserve((size_t)n * (two ? 8 : 4) + 2 * m->sh + 64));
+    m->perm = ws.sort_meta.as<uint32_t>();
+    m->second = two ? m->perm + n : nullptr;
+    m->hist = m->perm + (two ? 2 : 1) * (size_t)n;
+    m->cursor = m->hist + nkeys + 1;
+    return GASALX_OK;
+}
+static int sort_histogram(const SortMeta &m, const uint32_t *keys, uint32_t n, uint32_t nkeys, hipStream_t st) {
+    HIPCHK(hipMemsetAsync(m.hist, 0, m.sh, st));
+    rev_hist_kernel<<<sort_grid(n), 256, m.sh, st>>>(REV_PLAIN, keys, nullptr, n, nkeys, m.hist);
     HIPCHK(hipGetLastError());
+    return GASALX_OK;
+}
+static int sort_scatter(const SortMeta &m, const uint32_t *keys, uint32_t n, uint32_t nkeys, uint32_t *inv,
+                        hipStream_t st) {
+    rev_scan_kernel<<<1, 256, 0, st>>>(m.hist, m.cursor, nkeys + 1);
+    rev_scatter_kernel<<<sort_grid(n), 256, 2 * m.sh, st>>>(REV_PLAIN, keys, nullptr, n, nkeys, m.cursor, m.perm, inv);
+    HIPCHK(hipGetLastError());
+    return GASALX_OK;
+}
+// The whole sort of n slots by keys: *perm (slot -> pair) and, when wanted, *inv (pair -> slot).
+static int counting_sort(Workspace &ws, const uint32_t *keys, uint32_t n, uint32_t nkeys, hipStream_t st,
+                         bool want_inv, const uint32_t **perm, const uint32_t **inv) {
+    SortMeta m;
+    int rc = sort_reserve(ws, n, nkeys, want_inv, &m);
+    if (!rc) rc = sort_histogram(m, keys, n, nkeys, st);
+    if (!rc) rc = sort_scatter(m, keys, n, nkeys, m.second, st);
+    if (rc) return rc;
+    *perm = m.perm;
+    if (want_inv) *inv = m.second;
     return GASALX_OK;
 }
 
@@ -588,36 +688,26 @@ static int launch_semi_tq(Workspace &ws, const Plan &pl, const gasalx_params &p,
                           hipStream_t st, bool one_class) {
     WfArgs A = base;
     const uint32_t n = A.n;
-    A.a = p.match; A.b = p.mismatch; A.o = p.gap_open; A.e = p.gap_extend;
-    A.nval = p.n_code & 0xF;
-    A.has_npen = p.has_n_penalty; A.npen = p.n_penalty;
-    A.head = p.head; A.tail = p.tail;
-    A.lds_stride = pl.lds_stride;
-    A.force_exact = (p.mismatch <= 0 || (p.has_n_penalty && p.n_penalty < 0)) ? 1 : 0;
-    A.one = 0x00010001u;
+    wf_common(A, p, pl);
     const uint32_t t8w = (uint32_t)pl.R16;                  // largest class
-    const size_t sh = (size_t)(t8w + 1) * 4;
-    HIPCHK(ws.sort_meta.reserve((size_t)n * 4 + 2 * sh + 64));
-    uint32_t *perm = ws.sort_meta.as<uint32_t>(), *hist = perm + n, *cursor = hist + t8w + 1;
+    SortMeta m;
+    int rc = sort_reserve(ws, n, t8w, false, &m);
+    if (rc) return rc;
     std::vector<uint32_t> h(t8w + 1, 0u);
     if (one_class) {
         h[0] = n;   // every pair in the largest class (host-side lengths, BatchShape::one_t8): no read-back
     } else {
         // the class sizes, read back: one synchronisation of the stream (gasalx.h, max_t_len)
-        HIPCHK(hipMemsetAsync(hist, 0, sh, st));
-        rev_hist_kernel<<<sort_grid(n), 256, sh, st>>>(REV_PLAIN, A.tlen, nullptr, n, t8w, hist);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(h.data(), hist, sh, hipMemcpyDeviceToHost, st));
+        if ((rc = sort_histogram(m, A.tlen, n, t8w, st))) return rc;
+        HIPCHK(hipMemcpyAsync(h.data(), m.hist, m.sh, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
     }
     int classes = 0;
     for (uint32_t b = 0; b <= t8w; b++) classes += h[b] != 0;
     A.perm = nullptr;
     if (classes > 1) {                                       // counting sort: longest targets first
-        rev_scan_kernel<<<1, 256, 0, st>>>(hist, cursor, t8w + 1);
-        rev_scatter_kernel<<<sort_grid(n), 256, 2 * sh, st>>>(REV_PLAIN, A.tlen, nullptr, n, t8w, cursor, perm);
-        HIPCHK(hipGetLastError());
-        A.perm = perm;
+        if ((rc = sort_scatter(m, A.tlen, n, t8w, nullptr, st))) return rc;
+        A.perm = m.perm;
     }
     HIPCHK(ws.misc.reserve(n + 64));
     HIPCHK(hipMemsetAsync(ws.misc.p, 0, n, st));            // slots no class launch covers stay declined
@@ -627,31 +717,21 @@ static int launch_semi_tq(Workspace &ws, const Plan &pl, const gasalx_params &p,
     P16.fast16 = 1;
     P16.vmin = pl.vmin;
     P16.handled = ws.misc.as<uint8_t>();
-    const uint32_t ppb16 = kWavesPerBlock * (64 / 8) * 2;
+    const uint32_t ppb16 = pairs_per_block(8);
     uint32_t slot = 0;
     for (uint32_t b = 0; b <= t8w; slot += h[b], b++) {
         const uint32_t R = t8w - b;                          // bucket b: padded target of 8R
         if (!h[b] || R == 0) continue;
         Wf16Fn fn = wf16_tq_lookup((int)R);
         if (!fn) { set_error("no packed TAIL=QUERY/BOTH instance"); return GASALX_EUNSUPPORTED; }
-        if (pl.lds16_bytes > 64 * 1024)
-            HIPCHK(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)pl.lds16_bytes));
         P16.slot0 = slot;
         P16.n = slot + h[b];
-        hipLaunchKernelGGL(fn, dim3(grid_for(h[b], ppb16)), dim3(kBlock), pl.lds16_bytes, st, P16);
-        HIPCHK(hipGetLastError());
+        HIPCHK(launch_lds(fn, dim3(grid_for(h[b], ppb16)), dim3(kBlock), pl.lds16_bytes, st, P16));
     }
     A.skip = ws.misc.as<uint8_t>();
     A.skip_ppb = 1;
     A.skip_p1 = 0xFFFFFFFFu;
-    WfFn fn = wf_lookup(pl.wf_algo, pl.keys, false, pl.G, pl.R);
-    if (!fn) { set_error("no wavefront instance"); return GASALX_EUNSUPPORTED; }
-    if (pl.lds_bytes > 64 * 1024)
-        HIPCHK(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes));
-    hipLaunchKernelGGL(fn, dim3(wf_grid(n, pl.G, A.skip != nullptr)), dim3(kBlock), pl.lds_bytes, st, A);
-    HIPCHK(hipGetLastError());
-    return GASALX_OK;
+    return launch_int32(pl, wf_lookup(pl.wf_algo, pl.keys, false, pl.G, pl.R), A, st);
 }
 
 // SEMI TAIL=NONE outputs (PLAN_CONST): score MINUS_INF, query_batch_end = maxXY_x =
@@ -717,7 +797,7 @@ static int start_reverse(Workspace &ws, int mode, const gasalx_params &p, const 
     A.lstop = lstop ? score : nullptr;
     A.n = n;
     A.packed = packed;
-    int rc = launch_wavefront(ws, pl, pr, A, st);
+    int rc = launch_wavefront(ws, pl, pr, A, TailShape(), st);
     if (rc) return rc;
     start_map_kernel<<<grid_for(n, 256), 256, 0, st>>>(mode, score, b.q_lens, rqlen, b.t_lens, tend, rscore, rqend,
                                                         rtend, qstart, tstart, n);
@@ -738,26 +818,473 @@ static int geometry_perm(Workspace &ws, const gasalx_batch &b, const BatchShape 
                          const uint32_t **perm_out) {
     *perm_out = nullptr;
     const uint32_t trw = pad8(shape.max_t) / 8, nkeys = (pad8(shape.max_q) / 8) * trw;
-    const size_t sh = (size_t)(nkeys + 1) * 4;
-    if (!(sort_wanted(shape) && n >= 4096 && 2 * sh <= 64 * 1024)) return GASALX_OK;
-    HIPCHK(ws.sort_meta.reserve((size_t)n * 8 + 2 * sh + 64));
-    uint32_t *perm = ws.sort_meta.as<uint32_t>(), *klen = perm + n, *hist = klen + n, *cursor = hist + nkeys + 1;
-    band16_key_kernel<<<grid_for(n, 256), 256, 0, st>>>(b.q_lens, b.t_lens, n, trw, klen);
-    HIPCHK(hipMemsetAsync(hist, 0, sh, st));
-    rev_hist_kernel<<<sort_grid(n), 256, sh, st>>>(REV_PLAIN, klen, nullptr, n, nkeys, hist);
-    rev_scan_kernel<<<1, 256, 0, st>>>(hist, cursor, nkeys + 1);
-    rev_scatter_kernel<<<sort_grid(n), 256, 2 * sh, st>>>(REV_PLAIN, klen, nullptr, n, nkeys, cursor, perm);
-    HIPCHK(hipGetLastError());
-    *perm_out = perm;
+    if (!(sort_wanted(shape) && n >= 4096 && 2 * (size_t)(nkeys + 1) * 4 <= 64 * 1024)) return GASALX_OK;
+    SortMeta m;   // the keys in its second array
+    int rc = sort_reserve(ws, n, nkeys, true, &m);
+    if (rc) return rc;
+    band16_key_kernel<<<grid_for(n, 256), 256, 0, st>>>(b.q_lens, b.t_lens, n, trw, m.second);
+    rc = sort_histogram(m, m.second, n, nkeys, st);
+    if (!rc) rc = sort_scatter(m, m.second, n, nkeys, nullptr, st);
+    if (rc) return rc;
+    *perm_out = m.perm;
     return GASALX_OK;
 }
 
+// ----------------------------------------------------------------------------
+// One align_body call: its inputs, then what each step leaves for the later ones.
+struct Call {
+    Workspace &ws;
+    const gasalx_params &p;
+    const Plan &pl;
+    const gasalx_batch &b;
+    const gasalx_results &out;
+    hipStream_t st;
+    const BatchShape &shape;
+    uint32_t n;
+    bool runs_tb;                 // a traceback walk follows the DP
+    const uint8_t *qsrc, *tsrc;   // pack_inputs: the sequences the kernels read, as bytes or packed words
+    int packed;
+    int32_t *qend, *tend;         // size_traceback: the ends, the caller's or the workspace's;
+    uint64_t tb_words;            //   direction words per pair; pair slots of ws.tb
+    uint32_t n_tb;
+    WfArgs A;                     // run_wavefront: the main launch (the band fallback starts from a copy),
+    TailShape tail;               //   its second shape, if any,
+    const uint32_t *slot_of;      //   pair -> slot when it ran sorted,
+    uint32_t *fb_count;           //   band traceback: the count of pairs handed to the full-matrix fallback
+};
+
+// the packed words of the generic kernels and of reverse-complemented batches (Plan::need_pack)
+static int pack_inputs(Call &c) {
+    Workspace &ws = c.ws;
+    const gasalx_batch &b = c.b;
+    if (!c.pl.need_pack) return GASALX_OK;
+    const uint32_t qw = b.q_bytes / 8, tw = b.t_bytes / 8;
+    HIPCHK(ws.packed_q.reserve((size_t)qw * 4 + 16));
+    HIPCHK(ws.packed_t.reserve((size_t)tw * 4 + 16));
+    if (c.p.is_packed) {
+        HIPCHK(hipMemcpyAsync(ws.packed_q.p, b.q_batch, (size_t)qw * 4, hipMemcpyDeviceToDevice, c.st));
+        HIPCHK(hipMemcpyAsync(ws.packed_t.p, b.t_batch, (size_t)tw * 4, hipMemcpyDeviceToDevice, c.st));
+    } else {
+        pack_kernel<<<std::min(grid_for(qw, 256), 4096), 256, 0, c.st>>>(b.q_batch, ws.packed_q.as<uint32_t>(), qw);
+        pack_kernel<<<std::min(grid_for(tw, 256), 4096), 256, 0, c.st>>>(b.t_batch, ws.packed_t.as<uint32_t>(), tw);
+    }
+    if (b.q_ops && b.t_ops) {
+        revcomp_kernel<<<grid_for(c.n, 256), 256, 0, c.st>>>(ws.packed_q.as<uint32_t>(), ws.packed_t.as<uint32_t>(),
+                                                              b.q_lens, b.t_lens, b.q_offsets, b.t_offsets, b.q_ops,
+                                                              b.t_ops, c.n, c.p.n_code);
+        // with isPacked the reference's packed buffer aliases the unpacked one, so
+        // the reversed words are what the cigar D2H copy sees (ctors.cpp:64-68)
+        if (c.p.start_pos == 2 && c.out.cigar && c.p.is_packed)
+            HIPCHK(hipMemcpyAsync(c.out.cigar, ws.packed_q.p, (size_t)qw * 4, hipMemcpyDeviceToDevice, c.st));
+    }
+    c.qsrc = ws.packed_q.as<uint8_t>();
+    c.tsrc = ws.packed_t.as<uint8_t>();
+    c.packed = 1;
+    return GASALX_OK;
+}
+
+// the direction words and, where the caller gave none, the end arrays
+static int size_traceback(Call &c, bool wf_start) {
+    const Plan &pl = c.pl;
+    // traceback storage: one word per (8-column strip, padded query row); the
+    // packed traceback kernels' skewed uint16 layout needs (t8 + G + 2) / 4 windows
+    // of G*R 16-bit entries instead (wavefront16.hpp)
+    const uint32_t q8 = pad8(c.shape.max_q), t8 = pad8(c.shape.max_t);
+    c.tb_words = (uint64_t)q8 * (t8 / 8);
+    if (pl.packed16 && pl.tb)
+        c.tb_words = std::max<uint64_t>(c.tb_words, (((uint64_t)pl.G16 * pl.R16 * ((t8 + pl.G16 + 2) / 4) / 2 + 3) & ~3ull));
+    // (whole groups of 8 pairs: the packed kernels' interleaved layout, tb_store_window)
+    // the band path's full-matrix direction words serve its fallback list only: GASALX_TB_FBCAP slots
+    // (131,072 by default), the list then aligned in chunks of that many (the rest reserve every pair)
+    const uint32_t fb_cap = std::max(64, env_int("GASALX_TB_FBCAP", 131072));
+    c.n_tb = (pl.kind == PLAN_WAVEFRONT && pl.packed16 && pl.tb_band) ? std::min(c.n, fb_cap) : c.n;
+    if (c.runs_tb) HIPCHK(c.ws.tb.reserve((size_t)((c.n_tb + 7) & ~7u) * c.tb_words * 4 + 64));
+    if ((c.runs_tb || wf_start) && (c.p.algo == 3 || c.p.algo == 2) && (!c.qend || !c.tend)) {
+        HIPCHK(c.ws.ends_q.reserve((size_t)c.n * 4));
+        HIPCHK(c.ws.ends_t.reserve((size_t)c.n * 4));
+        if (!c.qend) c.qend = c.ws.ends_q.as<int32_t>();
+        if (!c.tend) c.tend = c.ws.ends_t.as<int32_t>();
+    }
+    return GASALX_OK;
+}
+
+// uneven lengths: a wave's step count is set by its longest step-axis
+// sequence (target; query for the transposed SEMI kernel), so run the
+// slots in length order (counting sort, longest first)
+// (semi_tq sorts by target class itself; a launch whose waves hold fewer than 8 pairs --
+// the small-batch shapes, G >= 32 -- gains nothing from the order and would pay the three
+// sort launches: a 5,000-pair batch of the reference's sample data, profiles/r06/boundary)
+static int forward_length_sort(Call &c) {
+    const Plan &pl = c.pl;
+    const int gsort = pl.packed16 ? pl.G16 : pl.G;
+    if (!(sort_wanted(c.shape) && c.n >= 4096 && !pl.semi_tq && pairs_per_wave(std::max(gsort, 1)) >= 8)) return GASALX_OK;
+    const uint32_t s8w = pad8(pl.wf_algo == WF_SEMI ? c.shape.max_q : c.shape.max_t) / 8;
+    if (2 * (size_t)(s8w + 1) * 4 > 64 * 1024) return GASALX_OK;
+    return counting_sort(c.ws, pl.wf_algo == WF_SEMI ? c.b.q_lens : c.b.t_lens, c.n, s8w, c.st, true, &c.A.perm,
+                         &c.slot_of);
+}
+
+// band recomputation buffers per wave of the packed launch (wavefront16.hpp); a mixed-
+// shape launch (c.tail) keeps its second region's after the first's
+static int size_band_buffers(Call &c) {
+    Workspace &ws = c.ws;
+    const Plan &pl = c.pl;
+    const TailShape &tail = c.tail;
+    WfArgs &A = c.A;
+    const uint32_t n = c.n, grid1 = grid_for(n, pairs_per_block(pl.G16));
+    const uint64_t waves = (uint64_t)(tail.fn ? tail.b0 : grid1) * kWavesPerBlock;
+    const uint64_t waves2 = tail.fn ? (uint64_t)grid_for(n - tail.p0, tail.ppb) * kWavesPerBlock : 0;
+    const uint32_t wd2 = tail.fn ? band_window(tail.R2, pl.band_w) : 4u;
+    const uint64_t cpw1 = waves * 2 * pl.R16 * 64, cpw2 = waves2 * 2 * tail.R2 * 64;   // words
+    const uint64_t st1 = waves * 64 * band_stream_words(pl.band_wd), st2 = waves2 * 64 * band_stream_words(wd2);
+    const uint64_t fl1 = waves * 64 * (pl.band_wd / 4) * (pl.R16 / 4), fl2 = waves2 * 64 * (wd2 / 4) * (tail.R2 / 4);
+    HIPCHK(ws.band_cp.reserve((cpw1 + cpw2) * 4 + 64));
+    HIPCHK(ws.band_stm.reserve((st1 + st2) * 8 + 64));
+    HIPCHK(ws.band_fl.reserve((fl1 + fl2) * 16 + 64));
+    HIPCHK(ws.band_fb.reserve((size_t)n * 4 + grid1 + 256));
+    A.cp = ws.band_cp.as<uint32_t>();
+    A.stm = ws.band_stm.as<uint2>();
+    A.bflags = ws.band_fl.as<uint4>();
+    A.band_w = pl.band_w;
+    A.band_wd = pl.band_wd;
+    A.cp2 = A.cp + cpw1;
+    A.stm2 = A.stm + st1;
+    A.bflags2 = A.bflags + fl1;
+    A.band_wd2 = wd2;
+    c.fb_count = ws.band_fb.as<uint32_t>();
+    return GASALX_OK;
+}
+
+// PLAN_WAVEFRONT: the main launch, and the reverse pass of WITH_START
+static int run_wavefront(Call &c, bool wf_start) {
+    const gasalx_params &p = c.p;
+    const Plan &pl = c.pl;
+    WfArgs &A = c.A;
+    A.q = c.qsrc; A.t = c.tsrc;
+    A.qoff = c.b.q_offsets; A.toff = c.b.t_offsets; A.qlen = c.b.q_lens; A.tlen = c.b.t_lens;
+    A.score = c.out.aln_score;
+    A.qend = (p.algo == 1) ? nullptr : c.qend;
+    A.tend = (p.algo == 1) ? nullptr : c.tend;
+    A.tb = c.ws.tb.as<uint32_t>();
+    A.tb_pair_words = c.tb_words;
+    A.n = c.n;
+    A.packed = c.packed;
+    int rc = forward_length_sort(c);
+    if (rc) return rc;
+    // unsorted waves hold consecutive pairs: interleave their direction chunks
+    A.tb_q8 = (pl.packed16 && pl.tb && !pl.tb_band && !A.perm) ? 1u : 0u;
+    // the one evaluation of the tail shape: this launch, its band buffers and the walk share it
+    c.tail = tail_shape(c.ws, pl, p, A, c.n);
+    if (pl.tb_band && c.runs_tb && (rc = size_band_buffers(c))) return rc;
+    rc = pl.semi_tq ? launch_semi_tq(c.ws, pl, p, A, c.st, c.shape.one_t8) : launch_wavefront(c.ws, pl, p, A, c.tail, c.st);
+    if (rc || !wf_start) return rc;
+    return start_reverse(c.ws, p.algo == 3 ? REV_LOCAL : REV_SEMI, p, c.qsrc, c.tsrc, c.packed, c.b, c.shape,
+                         c.out.aln_score, c.qend, c.tend, c.out.q_start, c.out.t_start, c.st);
+}
+
+// KSW: 8-bit (h, e) entries, then 16-bit, then int2, each for the pairs whose score
+// bound does not fit the level before
+static int run_ksw(Call &c, const GenArgs &A) {
+    Workspace &ws = c.ws;
+    const gasalx_params &p = c.p;
+    const gasalx_batch &b = c.b;
+    const uint32_t n = c.n, max_q = c.shape.max_q;
+    hipStream_t st = c.st;
+    HIPCHK(ws.rows_h.reserve((size_t)(max_q + 8) * n * 8));
+    HIPCHK(ws.misc.reserve(n));
+    HIPCHK(hipMemsetAsync(ws.misc.p, 0, n, st));
+    uint8_t *todo = ws.misc.as<uint8_t>();
+    // two pairs per lane in 16-bit halves first (ksw16.hpp): the pairs it takes
+    // get todo = 0xFF, the rest run the levels below (GASALX_KSW16=0: levels only)
+    const int32_t nsc = p.has_n_penalty ? -p.n_penalty : 0;
+    const int32_t kofs = std::max({0, p.mismatch, -nsc, -p.match});
+    const bool k16 = env_flag("GASALX_KSW16", true) && p.gap_open >= 0 && p.gap_extend >= 0 &&
+                     p.gap_open + p.gap_extend <= 0x300 && p.match + kofs <= 255 &&
+                     -p.mismatch + kofs <= 255 && nsc + kofs <= 255 && max_q <= 254;
+    if (k16) {
+        Ksw16Args K;
+        std::memset(&K, 0, sizeof(K));
+        K.qw = A.qw; K.tw = A.tw;
+        K.qoff = b.q_offsets; K.toff = b.t_offsets; K.qlen = b.q_lens; K.tlen = b.t_lens;
+        K.seed = b.seed_scores;
+        K.score = c.out.aln_score; K.qend = c.qend; K.tend = c.tend;
+        K.todo = todo;
+        K.n = n; K.n_lanes = (n + 1) / 2; K.cols = (max_q + 3) & ~1u;
+        K.stride = grid_for(K.n_lanes, 256) * 256;
+        fill_scoring(K, p);
+        K.kofs = kofs;
+        // the entry row in registers when the padded query fits an instance
+        // (selector words in LDS: QC / 2 words per lane), else the global array
+        int qc = 0;
+        for (int q : {64, 96, 160})
+            if (K.cols <= (uint32_t)q) { qc = q; break; }
+        if (qc) {
+            void (*fn)(Ksw16Args) = qc == 64 ? &ksw16_kernel<64> : qc == 96 ? &ksw16_kernel<96> : &ksw16_kernel<160>;
+            HIPCHK(launch_lds(fn, dim3(grid_for(K.n_lanes, 256)), dim3(256), (size_t)4 * (qc / 2) * 64 * 4, st, K));
+        } else {
+            const size_t ent_words = (size_t)K.cols * K.stride, sel_words = (size_t)(K.cols / 2) * K.stride;
+            HIPCHK(ws.rows_e.reserve((ent_words + sel_words) * 4 + 64));
+            K.ent = ws.rows_e.as<uint32_t>(); K.sel = K.ent + ent_words;
+            ksw16_kernel<0><<<grid_for(K.n_lanes, 256), 256, 0, st>>>(K);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    // level 0 with the entries in LDS when two blocks of >= 64 threads fit
+    // a CU, for batches of up to 4 waves per SIMD: LDS then holds 2 waves
+    // per SIMD, and larger batches run faster on the global array with its
+    // higher occupancy (200 K config-2 pairs: 806 -> 890 GCUPS; 1 M: 1,320
+    // global, 1,146 LDS).  GASALX_KSW_LDS=0/1 forces either (A/B)
+    const bool lds_on = env_flag("GASALX_KSW_LDS", n <= 4u * 1024u * 64u);
+    uint32_t tpb = 0;
+    size_t lds = 0;
+    if (lds_on)
+        for (uint32_t t : {256u, 128u, 64u}) {
+            lds = (size_t)t * (max_q + 2) * 2;
+            if (2 * lds <= 160 * 1024) { tpb = t; break; }
+        }
+    if (tpb)
+        HIPCHK(launch_lds(&gen_ksw_kernel<0, true>, dim3(grid_for(n, tpb)), dim3(tpb), lds, st, A, ws.rows_h.p, todo));
+    else
+        gen_ksw_kernel<0><<<grid_for(n, 256), 256, 0, st>>>(A, ws.rows_h.p, todo);
+    gen_ksw_kernel<1><<<grid_for(n, 256), 256, 0, st>>>(A, ws.rows_h.p, todo);
+    gen_ksw_kernel<2><<<grid_for(n, 256), 256, 0, st>>>(A, ws.rows_h.p, todo);
+    return GASALX_OK;
+}
+
+// LOCAL second best, two pairs per lane (local16.hpp): *todo marks the pairs left to gen_local_kernel
+static int run_local16_prepass(Call &c, const GenArgs &A, const uint8_t **todo) {
+    Workspace &ws = c.ws;
+    const gasalx_params &p = c.p;
+    const uint32_t n = c.n, q8 = pad8(c.shape.max_q);
+    Local16Args D;
+    std::memset(&D, 0, sizeof(D));
+    D.qw = A.qw; D.tw = A.tw;
+    D.qoff = c.b.q_offsets; D.toff = c.b.t_offsets; D.qlen = c.b.q_lens; D.tlen = c.b.t_lens;
+    D.score = c.out.aln_score; D.qend = c.qend; D.tend = c.tend;
+    D.score2 = c.out.aln_score2; D.qend2 = c.out.q_end2; D.tend2 = c.out.t_end2;
+    D.n = n; D.n_lanes = (n + 1) / 2;
+    D.a = p.match; D.b = p.mismatch; D.oe = p.gap_open + p.gap_extend; D.e = p.gap_extend;
+    D.nval = A.nval; D.sn = local16_sn(p); D.k = local16_k(p); D.base = local16_base(p);
+    HIPCHK(ws.misc.reserve(n));
+    HIPCHK(hipMemsetAsync(ws.misc.p, 0, n, c.st));
+    D.todo = ws.misc.as<uint8_t>();
+    D.rows_cap = q8;
+    HIPCHK(ws.aux.reserve((size_t)q8 * ((D.n_lanes + 63) / 64) * 64 * 8 + 64));
+    D.rows = ws.aux.as<uint2>();
+    const int rc = geometry_perm(ws, c.b, c.shape, n, c.st, &D.perm);
+    if (rc) return rc;
+    // 3 waves per SIMD (162 VGPRs): 2 waves 2 % and 4 waves (spills) 5-15 % slower
+    local2nd16_kernel<3><<<grid_for(D.n_lanes, 256), 256, 0, c.st>>>(D);
+    HIPCHK(hipGetLastError());
+    *todo = D.todo;
+    return GASALX_OK;
+}
+
+// BANDED, two pairs per lane (banded16.hpp): *todo marks the pairs left to gen_banded_kernel
+static int run_band16_prepass(Call &c, const GenArgs &A, const uint8_t **todo) {
+    Workspace &ws = c.ws;
+    const gasalx_params &p = c.p;
+    const uint32_t n = c.n, q8 = pad8(c.shape.max_q);
+    BandArgs D;
+    std::memset(&D, 0, sizeof(D));
+    D.qw = A.qw; D.tw = A.tw;
+    D.qoff = c.b.q_offsets; D.toff = c.b.t_offsets; D.qlen = c.b.q_lens; D.tlen = c.b.t_lens;
+    D.score = c.out.aln_score; D.qend = c.qend; D.tend = c.tend;
+    D.n = n; D.n_lanes = (n + 1) / 2;
+    D.a = p.match; D.b = p.mismatch; D.oe = p.gap_open + p.gap_extend; D.e = p.gap_extend;
+    D.kbw = A.kbw; D.nval = A.nval; D.base = band16_base(p);
+    HIPCHK(ws.misc.reserve(n));
+    HIPCHK(hipMemsetAsync(ws.misc.p, 0, n, c.st));
+    D.todo = ws.misc.as<uint8_t>();
+    HIPCHK(ws.aux.reserve((size_t)q8 * D.n_lanes * 8 + 64));
+    D.rows = ws.aux.as<uint2>();
+    const int rc = geometry_perm(ws, c.b, c.shape, n, c.st, &D.perm);
+    if (rc) return rc;
+    band16_kernel<<<grid_for(D.n_lanes, 256), 256, 0, c.st>>>(D);
+    HIPCHK(hipGetLastError());
+    *todo = D.todo;
+    return GASALX_OK;
+}
+
+// PLAN_GENERIC: a thread per pair over packed words, after the two-pairs-per-lane kernel of the
+// plans that have one
+static int run_generic(Call &c) {
+    Workspace &ws = c.ws;
+    const gasalx_params &p = c.p;
+    const gasalx_batch &b = c.b;
+    const uint32_t n = c.n;
+    hipStream_t st = c.st;
+    GenArgs A;
+    std::memset(&A, 0, sizeof(A));
+    A.qw = ws.packed_q.as<uint32_t>(); A.tw = ws.packed_t.as<uint32_t>();
+    A.qoff = b.q_offsets; A.toff = b.t_offsets; A.qlen = b.q_lens; A.tlen = b.t_lens;
+    A.seed = b.seed_scores;
+    A.score = c.out.aln_score; A.qend = c.qend; A.tend = c.tend; A.qstart = c.out.q_start; A.tstart = c.out.t_start;
+    A.score2 = c.out.aln_score2; A.qend2 = c.out.q_end2; A.tend2 = c.out.t_end2;
+    A.tb = ws.tb.as<uint32_t>(); A.tb_pair_words = c.tb_words;
+    const uint32_t q8 = pad8(c.shape.max_q), t8 = pad8(c.shape.max_t);
+    uint32_t maxq = p.max_query_len > 0 ? (uint32_t)p.max_query_len : std::max(q8, t8);
+    if (maxq < q8) { set_error("max_query_len smaller than a padded query"); return GASALX_ERANGE; }
+    if (p.algo == 2 && p.start_pos == 1 && maxq < t8) {
+        set_error("semi-global WITH_START needs max_query_len >= padded target length");
+        return GASALX_ERANGE;
+    }
+    A.rows_cap = std::max(maxq, q8) + 8;
+    A.maxq = (int32_t)maxq;
+    A.rev_words = maxq / 8 + 1;
+    A.n = n;
+    fill_scoring(A, p);
+    A.start_pos = p.start_pos; A.second = p.second_best; A.head = p.head; A.tail = p.tail;
+    A.kbw = p.k_band >> 3;
+    int rc = GASALX_OK;
+    if (p.algo == 6) {
+        if ((rc = run_ksw(c, A))) return rc;
+    } else {
+        const size_t rows_elems = (size_t)A.rows_cap * n;
+        HIPCHK(ws.rows_h.reserve(rows_elems * 2));
+        HIPCHK(ws.rows_e.reserve(rows_elems * 2));
+        A.rowH = ws.rows_h.as<int16_t>(); A.rowE = ws.rows_e.as<int16_t>();
+        if (p.algo == 3) {
+            if (c.pl.local16 && (rc = run_local16_prepass(c, A, &A.todo))) return rc;
+            gen_local_kernel<<<grid_for(n, 256), 256, 0, st>>>(A);
+        } else if (p.algo == 2) {
+            if (p.start_pos == 1) {
+                HIPCHK(ws.rev.reserve((size_t)2 * A.rev_words * n * 4));
+                A.rev = ws.rev.as<uint32_t>();
+            }
+            gen_semi_kernel<<<grid_for(n, 256), 256, 0, st>>>(A);
+        } else if (p.algo == 5) {
+            if (c.pl.band16 && (rc = run_band16_prepass(c, A, &A.todo))) return rc;
+            gen_banded_kernel<<<grid_for(n, 256), 256, 0, st>>>(A);
+        } else {
+            gen_global_kernel<<<grid_for(n, 256), 256, 0, st>>>(A);
+        }
+    }
+    HIPCHK(hipGetLastError());
+    return GASALX_OK;
+}
+
+// The walk's arguments: every field's default in one place, then what the main launch decided.
+// walk_qseq: align_device's copy of the query codes, or NULL.
+static TbArgs make_tb_args(const Call &c, uint64_t cigar_cap, const uint8_t *walk_qseq) {
+    const gasalx_params &p = c.p;
+    const Plan &pl = c.pl;
+    TbArgs T;
+    std::memset(&T, 0, sizeof(T));
+    T.tb = c.ws.tb.as<uint32_t>(); T.tb_pair_words = c.tb_words;
+    T.qlen = c.b.q_lens; T.tlen = c.b.t_lens; T.qoff = c.b.q_offsets;
+    T.score = c.out.aln_score; T.qend = c.qend; T.tend = c.tend;
+    T.qstart = c.out.q_start; T.tstart = c.out.t_start;
+    T.cigar = c.out.cigar; T.n_ops = c.out.n_cigar_ops; T.n = c.n;
+    T.cigar_cap = cigar_cap ? cigar_cap : c.b.q_bytes;
+    fill_scoring(T, p);
+    T.is_local = p.algo == 3;
+    T.slot_of = c.slot_of;
+    T.sc_nn = p.has_n_penalty ? -p.n_penalty : p.match;   // GLOBAL: N == N is a match unless N_PENALTY
+    T.qseq = walk_qseq ? walk_qseq : c.qsrc; T.tseq = c.tsrc; T.toff = c.b.t_offsets; T.seq_packed = c.packed;
+    // no packed launch, one shape, no band, no fallback list (pointers and offsets: zero)
+    T.pk_ppb = 1; T.pk_R = 1; T.pk_G = 1;
+    T.pk_p1 = 0xFFFFFFFFu; T.pk_ppb2 = 1;
+    T.band_wd = 4; T.pk_ppw = 1;
+    T.band_wd2 = 4; T.pk_R2 = 4; T.pk_G2 = 1; T.pk_ppw2 = 1;
+    if (pl.kind == PLAN_WAVEFRONT && pl.packed16) {
+        T.pk_flags = c.ws.misc.as<uint8_t>();
+        T.pk_ppb = pairs_per_block(pl.G16);
+        T.pk_R = pl.R16;
+        T.pk_G = pl.G16;
+        T.pk_rmagic = rmagic(pl.R16);
+        T.pk_fix = c.ws.aux.as<int32_t>();
+        T.pk_q8 = c.A.tb_q8;
+        if (c.tail.fn) { T.pk_p1 = c.tail.p0; T.pk_b1 = c.tail.b0; T.pk_ppb2 = c.tail.ppb; }   // the launch's flag ranges
+    }
+    if (c.fb_count) {
+        T.band = c.ws.band_fl.as<uint4>();
+        T.band_w = pl.band_w; T.band_wd = pl.band_wd;
+        T.pk_ppw = pairs_per_wave(pl.G16);
+        if (c.tail.fn) {   // the second region of a mixed-shape launch
+            T.band2 = c.A.bflags2;
+            T.band_wd2 = c.A.band_wd2;
+            T.pk_R2 = c.tail.R2; T.pk_G2 = c.tail.G2; T.pk_ppw2 = pairs_per_wave(c.tail.G2);
+            T.pk_rmagic2 = rmagic(c.tail.R2);
+        }
+        T.fb_count = c.fb_count;
+        T.fb_list = c.fb_count + 64;
+    }
+    return T;
+}
+
+// Band traceback, after the walk: pairs whose path left the band (or whose block the packed launch
+// declined): the full-matrix packed traceback kernel over the list (slots = list positions; per-pair
+// flag layout at slot positions of the capped buffer), its int32 kernel for any block it
+// declines, and the walk again -- in chunks of n_tb list positions, each launch reading
+// the device-side count less its chunk's offset (empty chunks exit at once)
+static int run_band_fallback(Call &c, const TbArgs &T, const uint8_t *walk_qseq) {
+    Plan fp = c.pl;
+    fp.tb_band = false;
+    for (uint32_t k0 = 0; k0 < c.n; k0 += c.n_tb) {
+        const uint32_t cn = std::min(c.n_tb, c.n - k0);
+        WfArgs F = c.A;
+        // the band walk has written CIGAR prefixes over the query batch when that is the
+        // CIGAR buffer (get_tb.h:94): the DP reads align_device's copy of the codes then
+        if (walk_qseq) F.q = walk_qseq;
+        F.perm = T.fb_list + k0;
+        F.n = cn;
+        F.n_dev = c.fb_count;
+        F.n_dev_off = k0;
+        F.tb_slot = 1;
+        F.tb_q8 = 0;
+        F.cp = nullptr; F.stm = nullptr; F.bflags = nullptr;
+        int rc = launch_wavefront(c.ws, fp, c.p, F, TailShape(), c.st);
+        if (rc) return rc;
+        TbArgs T2 = T;
+        T2.band = nullptr;
+        T2.list = T.fb_list + k0;
+        T2.n = cn;
+        T2.n_dev = c.fb_count;
+        T2.n_dev_off = k0;
+        T2.tb_slot = 1;
+        T2.slot_of = nullptr;
+        T2.pk_q8 = 0;
+        T2.pk_p1 = 0xFFFFFFFFu;   // the fallback launch is one shape (its n_dev excludes the tail)
+        T2.fb_list = T2.fb_count = nullptr;
+        tb_kernel<<<grid_for(cn, 256), 256, 0, c.st>>>(T2);
+        HIPCHK(hipGetLastError());
+    }
+    return GASALX_OK;
+}
+
+// the traceback walk over every pair, then the band path's fallback
+static int run_walk(Call &c, uint64_t cigar_cap, const uint8_t *walk_qseq) {
+    const TbArgs T = make_tb_args(c, cigar_cap, walk_qseq);
+    if (c.fb_count) HIPCHK(hipMemsetAsync(c.fb_count, 0, 4, c.st));
+    tb_kernel<<<grid_for(c.n, 256), 256, 0, c.st>>>(T);
+    HIPCHK(hipGetLastError());
+    return c.fb_count ? run_band_fallback(c, T, walk_qseq) : GASALX_OK;
+}
+
 // Everything after align_device's prologue, over the pairs of b (a whole batch or one
-// chunk of it).  walk_qseq: the query codes the traceback walk reads when the CIGAR
-// buffer overlays the query batch (copied once by the prologue), else NULL.
+// chunk of it): pack, size, launch, walk.  walk_qseq: the query codes the traceback walk
+// reads when the CIGAR buffer overlays the query batch (copied once by the prologue), else NULL.
 static int align_body(Workspace &ws, const gasalx_params &p, const Plan &pl, const gasalx_batch &b,
                       const gasalx_results &out, hipStream_t st, const BatchShape &shape, uint64_t cigar_cap,
-                      const uint8_t *walk_qseq);
+                      const uint8_t *walk_qseq) {
+    const uint32_t n = b.n_alns;
+    if (pl.kind == PLAN_CONST) {
+        semi_tail_none_kernel<<<grid_for(n, 256), 256, 0, st>>>(out.aln_score, out.q_end, out.t_end, b.q_lens,
+                                                                      b.t_lens, n);
+        HIPCHK(hipGetLastError());
+        return GASALX_OK;
+    }
+    const bool runs_tb = p.start_pos == 2 && (p.algo == 1 || p.algo == 3) && pl.kind != PLAN_NONE;
+    const bool wf_start = pl.kind == PLAN_WAVEFRONT && (p.algo == 3 || p.algo == 2) && p.start_pos == 1 &&
+                          (out.q_start || out.t_start);
+    Call c{ws, p, pl, b, out, st, shape, n, runs_tb, b.q_batch, b.t_batch, p.is_packed ? 1 : 0, out.q_end, out.t_end};
+    int rc = pack_inputs(c);
+    if (!rc) rc = size_traceback(c, wf_start);
+    if (!rc) rc = pl.kind == PLAN_WAVEFRONT ? run_wavefront(c, wf_start) : run_generic(c);
+    if (!rc && runs_tb && out.cigar && out.n_cigar_ops) rc = run_walk(c, cigar_cap, walk_qseq);
+    return rc;
+}
 
 int align_device(Workspace &ws, const gasalx_params &p, const gasalx_batch &b, const gasalx_results &out,
                  hipStream_t st, const BatchShape &shape, uint64_t cigar_cap) {
@@ -807,407 +1334,6 @@ int align_device(Workspace &ws, const gasalx_params &p, const gasalx_batch &b, c
     return align_body(ws, p, pl, b, out, st, sized, cigar_cap, walk_qseq);
 }
 
-static int align_body(Workspace &ws, const gasalx_params &p, const Plan &pl, const gasalx_batch &b,
-                      const gasalx_results &out, hipStream_t st, const BatchShape &shape, uint64_t cigar_cap,
-                      const uint8_t *walk_qseq) {
-    const bool has_ops = b.q_ops && b.t_ops;
-    const uint32_t n = b.n_alns;
-    const bool tb = p.start_pos == 2;
-    const bool runs_tb = tb && (p.algo == 1 || p.algo == 3) && pl.kind != PLAN_NONE;
-    if (pl.kind == PLAN_CONST) {
-        semi_tail_none_kernel<<<grid_for(n, 256), 256, 0, st>>>(out.aln_score, out.q_end, out.t_end, b.q_lens,
-                                                                      b.t_lens, n);
-        HIPCHK(hipGetLastError());
-        return GASALX_OK;
-    }
-
-    const uint8_t *qsrc = b.q_batch, *tsrc = b.t_batch;
-    int packed = p.is_packed ? 1 : 0;
-    if (pl.need_pack) {
-        const uint32_t qw = b.q_bytes / 8, tw = b.t_bytes / 8;
-        HIPCHK(ws.packed_q.reserve((size_t)qw * 4 + 16));
-        HIPCHK(ws.packed_t.reserve((size_t)tw * 4 + 16));
-        if (p.is_packed) {
-            HIPCHK(hipMemcpyAsync(ws.packed_q.p, b.q_batch, (size_t)qw * 4, hipMemcpyDeviceToDevice, st));
-            HIPCHK(hipMemcpyAsync(ws.packed_t.p, b.t_batch, (size_t)tw * 4, hipMemcpyDeviceToDevice, st));
-        } else {
-            pack_kernel<<<std::min(grid_for(qw, 256), 4096), 256, 0, st>>>(b.q_batch, ws.packed_q.as<uint32_t>(), qw);
-            pack_kernel<<<std::min(grid_for(tw, 256), 4096), 256, 0, st>>>(b.t_batch, ws.packed_t.as<uint32_t>(), tw);
-        }
-        if (has_ops) {
-            revcomp_kernel<<<grid_for(n, 256), 256, 0, st>>>(ws.packed_q.as<uint32_t>(), ws.packed_t.as<uint32_t>(),
-                                                             b.q_lens, b.t_lens, b.q_offsets, b.t_offsets, b.q_ops,
-                                                             b.t_ops, n, p.n_code);
-            // with isPacked the reference's packed buffer aliases the unpacked one, so
-            // the reversed words are what the cigar D2H copy sees (ctors.cpp:64-68)
-            if (tb && out.cigar && p.is_packed)
-                HIPCHK(hipMemcpyAsync(out.cigar, ws.packed_q.p, (size_t)qw * 4, hipMemcpyDeviceToDevice, st));
-        }
-        qsrc = ws.packed_q.as<uint8_t>();
-        tsrc = ws.packed_t.as<uint8_t>();
-        packed = 1;
-    }
-
-    // traceback storage: one word per (8-column strip, padded query row); the
-    // packed traceback kernels' skewed uint16 layout needs (t8 + G + 2) / 4 windows
-    // of G*R 16-bit entries instead (wavefront16.hpp)
-    uint64_t tb_words = (uint64_t)pad8(shape.max_q) * (pad8(shape.max_t) / 8);
-    if (pl.packed16 && pl.tb)
-        tb_words = std::max<uint64_t>(tb_words, (((uint64_t)pl.G16 * pl.R16 * ((pad8(shape.max_t) + pl.G16 + 2) / 4) / 2 + 3) & ~3ull));
-    int32_t *qend = out.q_end, *tend = out.t_end;
-    const bool wf_start = pl.kind == PLAN_WAVEFRONT && (p.algo == 3 || p.algo == 2) && p.start_pos == 1 &&
-                          (out.q_start || out.t_start);
-    // (whole groups of 8 pairs: the packed kernels' interleaved layout, tb_store_window)
-    // the band path's full-matrix direction words serve its fallback list only: GASALX_TB_FBCAP slots
-    // (131,072 by default), the list then aligned in chunks of that many (the rest reserve every pair)
-    const uint32_t fb_cap = std::max(64, env_int("GASALX_TB_FBCAP", 131072));
-    const uint32_t n_tb = (pl.kind == PLAN_WAVEFRONT && pl.packed16 && pl.tb_band) ? std::min(n, fb_cap) : n;
-    if (runs_tb) HIPCHK(ws.tb.reserve((size_t)((n_tb + 7) & ~7u) * tb_words * 4 + 64));
-    if (runs_tb || wf_start) {
-        if ((p.algo == 3 || p.algo == 2) && (!qend || !tend)) {
-            HIPCHK(ws.ends_q.reserve((size_t)n * 4));
-            HIPCHK(ws.ends_t.reserve((size_t)n * 4));
-            if (!qend) qend = ws.ends_q.as<int32_t>();
-            if (!tend) tend = ws.ends_t.as<int32_t>();
-        }
-    }
-
-    const uint32_t *slot_of = nullptr;   // pair -> slot when the wavefront launch ran sorted
-    uint32_t tb_q8 = 0;                  // the packed TB kernels' interleaved layout
-    WfArgs A;                            // the wavefront launch (kept for the traceback fallback)
-    std::memset(&A, 0, sizeof(A));
-    uint32_t *fb_count = nullptr;        // band traceback: pairs handed to the full-matrix fallback
-    if (pl.kind == PLAN_WAVEFRONT) {
-        A.q = qsrc; A.t = tsrc;
-        A.qoff = b.q_offsets; A.toff = b.t_offsets; A.qlen = b.q_lens; A.tlen = b.t_lens;
-        A.score = out.aln_score;
-        A.qend = (p.algo == 1) ? nullptr : qend;
-        A.tend = (p.algo == 1) ? nullptr : tend;
-        A.tb = ws.tb.as<uint32_t>();
-        A.tb_pair_words = tb_words;
-        A.n = n;
-        A.packed = packed;
-        // uneven lengths: a wave's step count is set by its longest step-axis
-        // sequence (target; query for the transposed SEMI kernel), so run the
-        // slots in length order (counting sort, longest first)
-        // (semi_tq sorts by target class itself; a launch whose waves hold fewer than 8 pairs --
-        // the small-batch shapes, G >= 32 -- gains nothing from the order and would pay the three
-        // sort launches: a 5,000-pair batch of the reference's sample data, profiles/r06/boundary)
-        const int gsort = pl.packed16 ? pl.G16 : pl.G;
-        if (sort_wanted(shape) && n >= 4096 && !pl.semi_tq && 2 * (64 / std::max(gsort, 1)) >= 8) {
-            const uint32_t s8w = pad8(pl.wf_algo == WF_SEMI ? shape.max_q : shape.max_t) / 8;
-            const uint32_t *slen = pl.wf_algo == WF_SEMI ? b.q_lens : b.t_lens;
-            const size_t sh = (size_t)(s8w + 1) * 4;
-            if (2 * sh <= 64 * 1024) {
-                HIPCHK(ws.sort_meta.reserve((size_t)n * 8 + (size_t)(s8w + 1) * 8 + 64));
-                uint32_t *perm = ws.sort_meta.as<uint32_t>(), *inv = perm + n, *hist = inv + n, *cursor = hist + s8w + 1;
-                HIPCHK(hipMemsetAsync(hist, 0, sh, st));
-                rev_hist_kernel<<<sort_grid(n), 256, sh, st>>>(REV_PLAIN, slen, nullptr, n, s8w, hist);
-                rev_scan_kernel<<<1, 256, 0, st>>>(hist, cursor, s8w + 1);
-                rev_scatter_kernel<<<sort_grid(n), 256, 2 * sh, st>>>(REV_PLAIN, slen, nullptr, n, s8w,
-                                                                          cursor, perm, inv);
-                HIPCHK(hipGetLastError());
-                A.perm = perm;
-                slot_of = inv;
-            }
-        }
-        // unsorted waves hold consecutive pairs: interleave their direction chunks
-        A.tb_q8 = (pl.packed16 && pl.tb && !pl.tb_band && !A.perm) ? 1u : 0u;
-        tb_q8 = A.tb_q8;
-        if (pl.tb_band && runs_tb) {
-            // band recomputation buffers per wave of the packed launch (wavefront16.hpp); a mixed-
-            // shape launch (tail_shape) keeps its second region's after the first's
-            const uint32_t ppb16 = kWavesPerBlock * (64 / pl.G16) * 2;
-            A.n = n;
-            const TailShape tail = tail_shape(pl, p, A, n);
-            const uint64_t waves = (uint64_t)(tail.fn ? tail.b0 : grid_for(n, ppb16)) * kWavesPerBlock;
-            const uint64_t waves2 = tail.fn ? (uint64_t)grid_for(n - tail.p0, tail.ppb) * kWavesPerBlock : 0;
-            const uint32_t wd2 = tail.fn ? (((uint32_t)(tail.R2 + 2 * pl.band_w) + 3u) & ~3u) : 4u;
-            const uint64_t cpw1 = waves * 2 * pl.R16 * 64, cpw2 = waves2 * 2 * tail.R2 * 64;   // words
-            const uint64_t st1 = waves * 64 * band_stream_words(pl.band_wd), st2 = waves2 * 64 * band_stream_words(wd2);
-            const uint64_t fl1 = waves * 64 * (pl.band_wd / 4) * (pl.R16 / 4), fl2 = waves2 * 64 * (wd2 / 4) * (tail.R2 / 4);
-            HIPCHK(ws.band_cp.reserve((cpw1 + cpw2) * 4 + 64));
-            HIPCHK(ws.band_stm.reserve((st1 + st2) * 8 + 64));
-            HIPCHK(ws.band_fl.reserve((fl1 + fl2) * 16 + 64));
-            HIPCHK(ws.band_fb.reserve((size_t)n * 4 + grid_for(n, ppb16) + 256));
-            A.cp = ws.band_cp.as<uint32_t>();
-            A.stm = ws.band_stm.as<uint2>();
-            A.bflags = ws.band_fl.as<uint4>();
-            A.band_w = pl.band_w;
-            A.band_wd = pl.band_wd;
-            A.cp2 = A.cp + cpw1;
-            A.stm2 = A.stm + st1;
-            A.bflags2 = A.bflags + fl1;
-            A.band_wd2 = wd2;
-            fb_count = ws.band_fb.as<uint32_t>();
-        }
-        int rc = pl.semi_tq ? launch_semi_tq(ws, pl, p, A, st, shape.one_t8) : launch_wavefront(ws, pl, p, A, st);
-        if (rc) return rc;
-        if (wf_start) {
-            rc = start_reverse(ws, p.algo == 3 ? REV_LOCAL : REV_SEMI, p, qsrc, tsrc, packed, b, shape, out.aln_score,
-                               qend, tend, out.q_start, out.t_start, st);
-            if (rc) return rc;
-        }
-    } else {
-        GenArgs A;
-        std::memset(&A, 0, sizeof(A));
-        A.qw = ws.packed_q.as<uint32_t>(); A.tw = ws.packed_t.as<uint32_t>();
-        A.qoff = b.q_offsets; A.toff = b.t_offsets; A.qlen = b.q_lens; A.tlen = b.t_lens;
-        A.seed = b.seed_scores;
-        A.score = out.aln_score; A.qend = qend; A.tend = tend; A.qstart = out.q_start; A.tstart = out.t_start;
-        A.score2 = out.aln_score2; A.qend2 = out.q_end2; A.tend2 = out.t_end2;
-        A.tb = ws.tb.as<uint32_t>(); A.tb_pair_words = tb_words;
-        const uint32_t q8 = pad8(shape.max_q), t8 = pad8(shape.max_t);
-        uint32_t maxq = p.max_query_len > 0 ? (uint32_t)p.max_query_len : std::max(q8, t8);
-        if (maxq < q8) { set_error("max_query_len smaller than a padded query"); return GASALX_ERANGE; }
-        if (p.algo == 2 && p.start_pos == 1 && maxq < t8) {
-            set_error("semi-global WITH_START needs max_query_len >= padded target length");
-            return GASALX_ERANGE;
-        }
-        A.rows_cap = std::max(maxq, q8) + 8;
-        A.maxq = (int32_t)maxq;
-        A.rev_words = maxq / 8 + 1;
-        A.n = n;
-        A.a = p.match; A.b = p.mismatch; A.o = p.gap_open; A.e = p.gap_extend;
-        A.nval = p.n_code & 0xF; A.has_npen = p.has_n_penalty; A.npen = p.n_penalty;
-        A.start_pos = p.start_pos; A.second = p.second_best; A.head = p.head; A.tail = p.tail;
-        A.kbw = p.k_band >> 3;
-        const size_t rows_elems = (size_t)A.rows_cap * n;
-        if (p.algo == 6) {
-            const size_t ke = (size_t)(shape.max_q + 8) * n;
-            HIPCHK(ws.rows_h.reserve(ke * 8));
-            // 8-bit (h, e) entries, then 16-bit, then int2, each for the pairs whose score
-            // bound does not fit the level before
-            uint8_t *todo = nullptr;
-            {
-                HIPCHK(ws.misc.reserve(n));
-                HIPCHK(hipMemsetAsync(ws.misc.p, 0, n, st));
-                todo = ws.misc.as<uint8_t>();
-                // two pairs per lane in 16-bit halves first (ksw16.hpp): the pairs it takes
-                // get todo = 0xFF, the rest run the levels below (GASALX_KSW16=0: levels only)
-                const int32_t nsc = p.has_n_penalty ? -p.n_penalty : 0;
-                const int32_t kofs = std::max({0, p.mismatch, -nsc, -p.match});
-                const bool k16 = env_flag("GASALX_KSW16", true) && p.gap_open >= 0 && p.gap_extend >= 0 &&
-                                 p.gap_open + p.gap_extend <= 0x300 && p.match + kofs <= 255 &&
-                                 -p.mismatch + kofs <= 255 && nsc + kofs <= 255 && shape.max_q <= 254;
-                if (k16) {
-                    Ksw16Args K;
-                    std::memset(&K, 0, sizeof(K));
-                    K.qw = A.qw; K.tw = A.tw;
-                    K.qoff = b.q_offsets; K.toff = b.t_offsets; K.qlen = b.q_lens; K.tlen = b.t_lens;
-                    K.seed = b.seed_scores;
-                    K.score = out.aln_score; K.qend = qend; K.tend = tend;
-                    K.todo = todo;
-                    K.n = n; K.n_lanes = (n + 1) / 2; K.cols = (shape.max_q + 3) & ~1u;
-                    K.stride = grid_for(K.n_lanes, 256) * 256;
-                    K.a = p.match; K.b = p.mismatch; K.o = p.gap_open; K.e = p.gap_extend;
-                    K.nval = p.n_code & 0xF; K.has_npen = p.has_n_penalty; K.npen = p.n_penalty;
-                    K.kofs = kofs;
-                    // the entry row in registers when the padded query fits an instance
-                    // (selector words in LDS: QC / 2 words per lane), else the global array
-                    int qc = 0;
-                    for (int c : {64, 96, 160})
-                        if (K.cols <= (uint32_t)c) { qc = c; break; }
-                    if (qc) {
-                        void (*fn)(Ksw16Args) = qc == 64 ? &ksw16_kernel<64> : qc == 96 ? &ksw16_kernel<96> : &ksw16_kernel<160>;
-                        const size_t lds = (size_t)4 * (qc / 2) * 64 * 4;
-                        if (lds > 64 * 1024)
-                            HIPCHK(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                        hipLaunchKernelGGL(fn, dim3(grid_for(K.n_lanes, 256)), dim3(256), lds, st, K);
-                    } else {
-                        const size_t ent_words = (size_t)K.cols * K.stride, sel_words = (size_t)(K.cols / 2) * K.stride;
-                        HIPCHK(ws.rows_e.reserve((ent_words + sel_words) * 4 + 64));
-                        K.ent = ws.rows_e.as<uint32_t>(); K.sel = K.ent + ent_words;
-                        ksw16_kernel<0><<<grid_for(K.n_lanes, 256), 256, 0, st>>>(K);
-                    }
-                    HIPCHK(hipGetLastError());
-                }
-                // level 0 with the entries in LDS when two blocks of >= 64 threads fit
-                // a CU, for batches of up to 4 waves per SIMD: LDS then holds 2 waves
-                // per SIMD, and larger batches run faster on the global array with its
-                // higher occupancy (200 K config-2 pairs: 806 -> 890 GCUPS; 1 M: 1,320
-                // global, 1,146 LDS).  GASALX_KSW_LDS=0/1 forces either (A/B)
-                const bool lds_on = env_flag("GASALX_KSW_LDS", n <= 4u * 1024u * 64u);
-                uint32_t tpb = 0;
-                size_t lds = 0;
-                if (lds_on)
-                    for (uint32_t t : {256u, 128u, 64u}) {
-                        lds = (size_t)t * (shape.max_q + 2) * 2;
-                        if (2 * lds <= 160 * 1024) { tpb = t; break; }
-                    }
-                if (tpb) {
-                    if (lds > 64 * 1024)
-                        HIPCHK(hipFuncSetAttribute((const void *)&gen_ksw_kernel<0, true>,
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    gen_ksw_kernel<0, true><<<grid_for(n, tpb), tpb, lds, st>>>(A, ws.rows_h.p, todo);
-                } else {
-                    gen_ksw_kernel<0><<<grid_for(n, 256), 256, 0, st>>>(A, ws.rows_h.p, todo);
-                }
-                gen_ksw_kernel<1><<<grid_for(n, 256), 256, 0, st>>>(A, ws.rows_h.p, todo);
-            }
-            gen_ksw_kernel<2><<<grid_for(n, 256), 256, 0, st>>>(A, ws.rows_h.p, todo);
-        } else {
-            HIPCHK(ws.rows_h.reserve(rows_elems * 2));
-            HIPCHK(ws.rows_e.reserve(rows_elems * 2));
-            A.rowH = ws.rows_h.as<int16_t>(); A.rowE = ws.rows_e.as<int16_t>();
-            if (p.algo == 3) {
-                if (pl.local16) {
-                    Local16Args D;
-                    std::memset(&D, 0, sizeof(D));
-                    D.qw = A.qw; D.tw = A.tw;
-                    D.qoff = b.q_offsets; D.toff = b.t_offsets; D.qlen = b.q_lens; D.tlen = b.t_lens;
-                    D.score = out.aln_score; D.qend = qend; D.tend = tend;
-                    D.score2 = out.aln_score2; D.qend2 = out.q_end2; D.tend2 = out.t_end2;
-                    D.n = n; D.n_lanes = (n + 1) / 2;
-                    D.a = p.match; D.b = p.mismatch; D.oe = p.gap_open + p.gap_extend; D.e = p.gap_extend;
-                    D.nval = A.nval; D.sn = local16_sn(p); D.k = local16_k(p); D.base = local16_base(p);
-                    HIPCHK(ws.misc.reserve(n));
-                    HIPCHK(hipMemsetAsync(ws.misc.p, 0, n, st));
-                    D.todo = ws.misc.as<uint8_t>();
-                    D.rows_cap = q8;
-                    HIPCHK(ws.aux.reserve((size_t)q8 * ((D.n_lanes + 63) / 64) * 64 * 8 + 64));
-                    D.rows = ws.aux.as<uint2>();
-                    {
-                        const int rc = geometry_perm(ws, b, shape, n, st, &D.perm);
-                        if (rc) return rc;
-                    }
-                    // 3 waves per SIMD (162 VGPRs): 2 waves 2 % and 4 waves (spills) 5-15 % slower
-                    local2nd16_kernel<3><<<grid_for(D.n_lanes, 256), 256, 0, st>>>(D);
-                    HIPCHK(hipGetLastError());
-                    A.todo = D.todo;
-                }
-                gen_local_kernel<<<grid_for(n, 256), 256, 0, st>>>(A);
-            }
-            else if (p.algo == 2) {
-                if (p.start_pos == 1) {
-                    HIPCHK(ws.rev.reserve((size_t)2 * A.rev_words * n * 4));
-                    A.rev = ws.rev.as<uint32_t>();
-                }
-                gen_semi_kernel<<<grid_for(n, 256), 256, 0, st>>>(A);
-            } else if (p.algo == 5) {
-                if (pl.band16) {
-                    BandArgs D;
-                    std::memset(&D, 0, sizeof(D));
-                    D.qw = A.qw; D.tw = A.tw;
-                    D.qoff = b.q_offsets; D.toff = b.t_offsets; D.qlen = b.q_lens; D.tlen = b.t_lens;
-                    D.score = out.aln_score; D.qend = qend; D.tend = tend;
-                    D.n = n; D.n_lanes = (n + 1) / 2;
-                    D.a = p.match; D.b = p.mismatch; D.oe = p.gap_open + p.gap_extend; D.e = p.gap_extend;
-                    D.kbw = A.kbw; D.nval = A.nval; D.base = band16_base(p);
-                    HIPCHK(ws.misc.reserve(n));
-                    HIPCHK(hipMemsetAsync(ws.misc.p, 0, n, st));
-                    D.todo = ws.misc.as<uint8_t>();
-                    HIPCHK(ws.aux.reserve((size_t)q8 * D.n_lanes * 8 + 64));
-                    D.rows = ws.aux.as<uint2>();
-                    {
-                        const int rc = geometry_perm(ws, b, shape, n, st, &D.perm);
-                        if (rc) return rc;
-                    }
-                    band16_kernel<<<grid_for(D.n_lanes, 256), 256, 0, st>>>(D);
-                    HIPCHK(hipGetLastError());
-                    A.todo = D.todo;
-                }
-                gen_banded_kernel<<<grid_for(n, 256), 256, 0, st>>>(A);
-            }
-            else gen_global_kernel<<<grid_for(n, 256), 256, 0, st>>>(A);
-        }
-        HIPCHK(hipGetLastError());
-    }
-
-    if (runs_tb && out.cigar && out.n_cigar_ops) {
-        TbArgs T;
-        T.tb = ws.tb.as<uint32_t>(); T.tb_pair_words = tb_words;
-        T.qlen = b.q_lens; T.tlen = b.t_lens; T.qoff = b.q_offsets;
-        T.score = out.aln_score; T.qend = qend; T.tend = tend;
-        T.qstart = out.q_start; T.tstart = out.t_start;
-        T.cigar = out.cigar; T.n_ops = out.n_cigar_ops; T.n = n;
-        T.cigar_cap = cigar_cap ? cigar_cap : b.q_bytes;
-        T.a = p.match; T.b = p.mismatch; T.o = p.gap_open; T.e = p.gap_extend;
-        T.is_local = p.algo == 3;
-        T.pk_flags = nullptr;
-        T.pk_ppb = 1; T.pk_R = 1; T.pk_G = 1; T.pk_rmagic = 0; T.pk_q8 = 0;
-        T.pk_fix = nullptr;
-        T.pk_p1 = 0xFFFFFFFFu; T.pk_b1 = 0; T.pk_ppb2 = 1;
-        T.band2 = nullptr; T.band_wd2 = 4; T.pk_R2 = 4; T.pk_G2 = 1; T.pk_ppw2 = 1; T.pk_rmagic2 = 0;
-        T.slot_of = slot_of;
-        T.sc_nn = p.has_n_penalty ? -p.n_penalty : p.match;   // GLOBAL: N == N is a match unless N_PENALTY
-        T.qseq = qsrc; T.tseq = tsrc; T.toff = b.t_offsets; T.seq_packed = packed;
-        if (walk_qseq) T.qseq = walk_qseq;   // align_device's copy of the query codes
-        T.nval = p.n_code & 0xF; T.has_npen = p.has_n_penalty; T.npen = p.n_penalty;
-        if (pl.kind == PLAN_WAVEFRONT && pl.packed16) {
-            T.pk_flags = ws.misc.as<uint8_t>();
-            T.pk_ppb = kWavesPerBlock * (64 / pl.G16) * 2;
-            T.pk_R = pl.R16;
-            T.pk_G = pl.G16;
-            T.pk_rmagic = (uint32_t)((0x100000000ull + pl.R16 - 1) / pl.R16);
-            T.pk_fix = ws.aux.as<int32_t>();
-            T.pk_q8 = tb_q8;
-            T.pk_p1 = ws.pk_p1; T.pk_b1 = ws.pk_b1; T.pk_ppb2 = ws.pk_ppb2;   // the launch's flag ranges
-        }
-        T.band = nullptr; T.band_w = 0; T.band_wd = 4; T.pk_ppw = 1;
-        T.fb_list = T.fb_count = nullptr;
-        T.list = T.n_dev = nullptr;
-        T.n_dev_off = 0; T.tb_slot = 0;
-        if (fb_count) {
-            T.band = ws.band_fl.as<uint4>();
-            T.band_w = pl.band_w; T.band_wd = pl.band_wd;
-            T.pk_ppw = 2 * (64 / pl.G16);
-            if (T.pk_p1 != 0xFFFFFFFFu) {   // the second region of a mixed-shape launch (tail_shape)
-                const TailShape tail = tail_shape(pl, p, A, n);
-                if (!tail.fn || tail.p0 != T.pk_p1) { set_error("band traceback: tail shape changed"); return GASALX_EINVAL; }
-                T.band2 = A.bflags2;
-                T.band_wd2 = A.band_wd2;
-                T.pk_R2 = tail.R2; T.pk_G2 = tail.G2; T.pk_ppw2 = 2 * (64 / tail.G2);
-                T.pk_rmagic2 = (uint32_t)((0x100000000ull + tail.R2 - 1) / tail.R2);
-            }
-            T.fb_count = fb_count;
-            T.fb_list = fb_count + 64;
-            HIPCHK(hipMemsetAsync(fb_count, 0, 4, st));
-        }
-        tb_kernel<<<grid_for(n, 256), 256, 0, st>>>(T);
-        HIPCHK(hipGetLastError());
-        if (fb_count) {
-            // pairs whose path left the band (or whose block the packed launch declined): the
-            // full-matrix packed traceback kernel over the list (slots = list positions; per-pair
-            // flag layout at slot positions of the capped buffer), its int32 kernel for any block it
-            // declines, and the walk again -- in chunks of n_tb list positions, each launch reading
-            // the device-side count less its chunk's offset (empty chunks exit at once)
-            Plan fp = pl;
-            fp.tb_band = false;
-            for (uint32_t k0 = 0; k0 < n; k0 += n_tb) {
-                const uint32_t cn = std::min(n_tb, n - k0);
-                WfArgs F = A;
-                // the band walk has written CIGAR prefixes over the query batch when that is the
-                // CIGAR buffer (get_tb.h:94): the DP reads align_device's copy of the codes then
-                if (walk_qseq) F.q = walk_qseq;
-                F.perm = T.fb_list + k0;
-                F.n = cn;
-                F.n_dev = fb_count;
-                F.n_dev_off = k0;
-                F.tb_slot = 1;
-                F.tb_q8 = 0;
-                F.cp = nullptr; F.stm = nullptr; F.bflags = nullptr;
-                int rc = launch_wavefront(ws, fp, p, F, st);
-                if (rc) return rc;
-                TbArgs T2 = T;
-                T2.band = nullptr;
-                T2.list = T.fb_list + k0;
-                T2.n = cn;
-                T2.n_dev = fb_count;
-                T2.n_dev_off = k0;
-                T2.tb_slot = 1;
-                T2.slot_of = nullptr;
-                T2.pk_q8 = 0;
-                T2.pk_p1 = 0xFFFFFFFFu;   // the fallback launch is one shape (its n_dev excludes the tail)
-                T2.fb_list = T2.fb_count = nullptr;
-                tb_kernel<<<grid_for(cn, 256), 256, 0, st>>>(T2);
-                HIPCHK(hipGetLastError());
-            }
-        }
-    }
-    return GASALX_OK;
-}
-
 // ----------------------------------------------------------------------------
 constexpr int kHmmRows = 8;   // read rows per lane
 using HmmFn = void (*)(HmmArgs);
@@ -1250,9 +1376,7 @@ static int pairhmm_launch(HmmArgs A, bool quals, uint32_t max_r, uint32_t slot0,
     if (lds > 160 * 1024) { set_error("PairHMM haplotype too long"); return GASALX_ERANGE; }
     HmmFn fn = quals ? (absorb ? hmm_lookup<true, true>(G) : hmm_lookup<true, false>(G))
                      : (absorb ? hmm_lookup<false, true>(G) : hmm_lookup<false, false>(G));
-    if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(fn, dim3(grid_for(slot1 - slot0, 4 * (64 / G))), dim3(256), lds, st, A);
-    HIPCHK(hipGetLastError());
+    HIPCHK(launch_lds(fn, dim3(grid_for(slot1 - slot0, 4 * (64 / G))), dim3(256), lds, st, A));
     return GASALX_OK;
 }
 

@@ -44,8 +44,27 @@ struct Workspace {
     // a mixed-shape launch (wavefront16.hpp wf16_mix_kernel): flags from pk_b1 on cover pk_ppb2 pairs
     // each, from pair pk_p1 on (pk_p1 = 0xFFFFFFFF: one block size)
     uint32_t pk_p1 = 0xFFFFFFFFu, pk_b1 = 0, pk_ppb2 = 1;
+    int cus = 0;                    // CU count of `device`, asked on first use (0: not yet)
     void release_all();
 };
+
+// a length padded to whole 8-base words
+inline uint32_t pad8(uint32_t x) { return (x + 7u) & ~7u; }
+
+template <class T> struct LaunchArg { using type = T; };
+// Launch kernel fn(args...) with `lds` bytes of dynamic LDS, raising the kernel's limit first when
+// that is past the 64 KB default; the error of either step, or of the launch.
+template <class... P>
+hipError_t launch_lds(void (*fn)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st,
+                      const typename LaunchArg<P>::type &...args) {
+    if (lds > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    void *argv[] = {const_cast<void *>(static_cast<const void *>(&args))...};
+    hipError_t e = hipLaunchKernel((const void *)fn, grid, block, argv, lds, st);
+    return e != hipSuccess ? e : hipGetLastError();
+}
 
 // PLAN_CONST: outputs that do not depend on the DP (SEMI TAIL=NONE, score-only)
 enum PlanKind { PLAN_NONE = 0, PLAN_WAVEFRONT, PLAN_GENERIC, PLAN_CONST };

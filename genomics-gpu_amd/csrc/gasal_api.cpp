@@ -112,8 +112,6 @@ template <class T> size_t block_run(std::initializer_list<T *> a) {
 template <class T> void host_free(T *&p) { if (p && !block_release(p)) CHECKHIPERROR(hipHostFree(p)); p = nullptr; }
 template <class T> void dev_free(T *&p) { if (p && !block_release(p)) CHECKHIPERROR(hipFree(p)); p = nullptr; }
 
-uint32_t pad8(uint32_t x) { return x % 8 ? x + (8 - x % 8) : x; }
-
 }  // namespace
 
 // ============================================================== res.cpp ====
@@ -399,7 +397,7 @@ gasal_gpu_storage_v gasal_init_gpu_storage_v(int n_streams) {
 
 void gasal_init_streams(gasal_gpu_storage_v *vec, int max_query_len, int max_target_len, int max_n_alns,
                         Parameters *params) {
-    const uint32_t q8 = pad8((uint32_t)max_query_len), t8 = pad8((uint32_t)max_target_len);
+    const uint32_t q8 = gx::pad8((uint32_t)max_query_len), t8 = gx::pad8((uint32_t)max_target_len);
     const uint32_t qbytes = (uint32_t)max_n_alns * q8, tbytes = (uint32_t)max_n_alns * t8;   // ctors.cpp:33-38
     for (int i = 0; i < vec->n; i++) {
         gasal_gpu_storage_t *gs = &vec->a[i];

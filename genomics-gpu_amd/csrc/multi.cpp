@@ -36,8 +36,6 @@
 
 namespace {
 
-uint32_t pad8u(uint32_t x) { return (x + 7u) & ~7u; }
-
 // RCCL entry points, resolved once per process
 struct Rccl {
     decltype(&ncclCommInitAll) init_all = nullptr;
@@ -97,7 +95,7 @@ void span(const uint32_t *off, const uint32_t *len, uint32_t s, uint32_t e, bool
     uint64_t a = ~0ull, z = 0;
     for (uint32_t i = s; i < e; i++) {
         a = std::min<uint64_t>(a, off[i]);
-        z = std::max<uint64_t>(z, (uint64_t)off[i] + (pad ? pad8u(len[i]) : len[i]));
+        z = std::max<uint64_t>(z, (uint64_t)off[i] + (pad ? gx::pad8(len[i]) : len[i]));
     }
     *lo = e > s ? a : 0;
     *hi = e > s ? z : 0;

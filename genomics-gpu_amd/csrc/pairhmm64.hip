@@ -102,10 +102,8 @@ static int pairhmm64_launch(Hmm64Args A, bool quals, uint32_t n, uint32_t max_r,
     const size_t lds = ((size_t)4 * (64 / G) * A.lds_stride + 15) & ~(size_t)15;
     if (lds > 160 * 1024) { set_error("PairHMM haplotype too long"); return GASALX_ERANGE; }
     Hmm64Fn fn = quals ? hmm64_lookup<true>(G, rows) : hmm64_lookup<false>(G, rows);
-    if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const uint32_t ppb = 4 * (64 / G);
-    hipLaunchKernelGGL(fn, dim3((n + ppb - 1) / ppb), dim3(256), lds, st, A);
-    HIPCHK(hipGetLastError());
+    HIPCHK(launch_lds(fn, dim3((n + ppb - 1) / ppb), dim3(256), lds, st, A));
     return GASALX_OK;
 }
 

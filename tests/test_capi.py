@@ -85,6 +85,77 @@ def test_plan_selection_cpu_only():
     assert G.describe_plan(G.make_params(algo=G.UNKNOWN), 10, 10) == "none"
 
 
+# ---- the planner over a fixed grid (tests/golden/plan_names.json, written by tools/plan_grid.py
+#      from the build of the commit it names) ----
+PLAN_LENS = (8, 64, 150, 152, 182, 256, 257, 300, 512, 513, 1000, 4000)
+# (match, mismatch, gap_open, gap_extend, n_penalty): match 1, 2, 3; a zero and a negative mismatch;
+# an N penalty below and above the mismatch
+PLAN_SCORES = ((1, 4, 6, 1, None), (2, 4, 6, 1, None), (3, 4, 6, 1, None), (1, 0, 6, 1, None), (2, -1, 4, 2, None),
+               (1, 4, 6, 1, 2), (1, 4, 6, 1, 6))
+PLAN_ENVS = (None, "GASALX_KF16=0", "GASALX_KSEG=0", "GASALX_KSEG=2", "GASALX_TB_BAND=0", "GASALX_PACKED16=0",
+             "GASALX_BAND16=0", "GASALX_LOCAL16=0")
+PLAN_SWITCHES = sorted({e.split("=")[0] for e in PLAN_ENVS if e} | {"GASALX_GMIN"})
+
+
+def plan_length_pairs():
+    """Every length with itself, with each neighbour in the list and with the read length 150, in
+    both orientations."""
+    out = []
+    for i, a in enumerate(PLAN_LENS):
+        for b in {a, PLAN_LENS[max(i - 1, 0)], PLAN_LENS[min(i + 1, len(PLAN_LENS) - 1)], 150}:
+            out += [(a, b), (b, a)]
+    return sorted(set(out))
+
+
+def plan_param_sets():
+    """Every algo x start_pos x second_best x score set, and every tail and head for SEMI (k_band 16
+    for BANDED): one list per set, of its heads."""
+    for algo in range(7):
+        semi = algo == G.SEMI_GLOBAL
+        for start in (0, 1, 2):
+            for second in (0, 1):
+                for tail in (range(4) if semi else (G.TARGET,)):
+                    for m, x, o, e, npen in PLAN_SCORES:
+                        yield [G.make_params(algo=algo, start_pos=start, second_best=second, head=head, tail=tail,
+                                             match=m, mismatch=x, gap_open=o, gap_extend=e, n_penalty=npen,
+                                             k_band=16 if algo == G.BANDED else 0)
+                               for head in (range(4) if semi else (G.TARGET,))]
+
+
+def plan_grid_names(setenv, delenv):
+    """The plan name of every grid row, in the fixture's order: switch, parameter set, length pair, head."""
+    lib, buf = G.lib(), ctypes.create_string_buffer(128)
+    pairs = plan_length_pairs()
+    params = list(plan_param_sets())
+    names = []
+    for env in PLAN_ENVS:
+        for s in PLAN_SWITCHES:
+            delenv(s)
+        if env:
+            setenv(*env.split("="))
+        for heads in params:
+            refs = [ctypes.byref(p) for p in heads]
+            for q, t in pairs:
+                for ref in refs:
+                    assert lib.gasalx_describe_plan(ref, q, t, buf, 128) == 0
+                    names.append(buf.value)
+    return [n.decode() for n in names]
+
+
+def test_plan_names_match_golden_grid(monkeypatch):
+    """make_plan names the same kernel for every row of the grid as the build that wrote the fixture
+    (rows run-length encoded: name index, count, name index, count, ... over plan_grid_names' order)."""
+    import json
+    gold = json.load(open(os.path.join(ROOT, "tests", "golden", "plan_names.json")))
+    assert gold["lens"] == list(PLAN_LENS) and gold["envs"] == list(PLAN_ENVS)
+    assert gold["scores"] == [list(s) for s in PLAN_SCORES]
+    want = [gold["names"][i] for i, c in zip(gold["runs"][0::2], gold["runs"][1::2]) for _ in range(c)]
+    got = plan_grid_names(monkeypatch.setenv, lambda s: monkeypatch.delenv(s, raising=False))
+    assert len(got) == len(want) == gold["rows"]
+    bad = [k for k in range(len(got)) if got[k] != want[k]]
+    assert not bad, (len(bad), bad[:5], [(got[k], want[k]) for k in bad[:5]])
+
+
 def test_synthetic_workloads_deterministic():
     a = G.Batch.synth(2, 64, 0x5EED0002)
     b = G.Batch.synth(2, 64, 0x5EED0002)
