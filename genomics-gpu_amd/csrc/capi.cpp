@@ -4,8 +4,10 @@
 #include <algorithm>
 #include <cerrno>
 #include <cmath>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <string>
 #include <vector>
@@ -15,16 +17,37 @@
 
 // One stage of the host-staged pipeline (gasalx_align_host on large batches):
 // its own stream, workspace and device copies of one chunk of pairs.
+enum SlotBuf { S_Q, S_T, S_META, S_CIG, S_COUNT };
 struct HostSlot {
     hipStream_t st = nullptr;
     gx::Workspace ws;
-    gx::DevBuf q, t, meta, cig;
-    std::vector<uint8_t> hmeta;   // host image of the chunk's per-pair region (meta)
+    gx::DevBuf buf[S_COUNT];
+    std::vector<uint8_t> hmeta;   // host image of the chunk's per-pair region (S_META)
     void release() {
         ws.release_all();
-        for (gx::DevBuf *b : {&q, &t, &meta, &cig}) b->release();
+        for (gx::DevBuf &b : buf) b.release();
         if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); st = nullptr; }
     }
+};
+
+// The engine's device buffers outside its workspaces, by role.  A buffer exists in this list and
+// nowhere else: gasalx_engine::release() walks the array.  No buffer serves two roles: the ones
+// marked "device forms" are still in use on the caller's stream after the call has returned, so a
+// host form's staging must never land in them.
+enum Buf {
+    // gasalx_align_host, single shot: the batch, then the ten result fields in gasalx_results order
+    B_Q, B_T, B_QO, B_TO, B_QL, B_TL, B_QOP, B_TOP, B_SEED, B_OUT, B_OUT_LAST = B_OUT + 9,
+    // PairHMM host forms: the batch in either input form, the slot order, the results
+    B_READS, B_RO, B_RL, B_QM, B_DE, B_XI, B_AL, B_HAPS, B_HO, B_HL, B_BQ, B_IQ, B_DQ, B_PERM,
+    B_RES, B_RES64, B_USED,
+    // PairHMM, device forms too: the ph2pr table, the log10 calls' fp32 results and their rescue
+    // list (its count in the first of four words, then one word per pair)
+    B_PH2PR, B_HM_R32, B_HM_LIST,
+    // nvbio host forms: the two string sets, the outputs
+    B_NV_PW, B_NV_PO, B_NV_TW, B_NV_TO, B_NV_S, B_NV_S16, B_NV_SRC, B_NV_SNK, B_NV_OPS, B_NV_NOPS,
+    // nvbio traceback, device forms too: flags of every cell, one DP row per pair
+    B_NV_DIR, B_NV_ROW,
+    B_COUNT
 };
 
 struct gasalx_engine {
@@ -32,25 +55,11 @@ struct gasalx_engine {
     hipStream_t stream = nullptr;
     gx::Workspace ws;
     HostSlot slot[2];
-    // staging for the host-to-host entry points
-    gx::DevBuf q, t, qo, to, ql, tl, qop, top, seed;
-    gx::DevBuf o_score, o_qe, o_te, o_qs, o_ts, o_s2, o_qe2, o_te2, o_cig, o_nops, lens_max;
-    gx::DevBuf h_reads, h_ro, h_rl, h_qm, h_de, h_xi, h_al, h_haps, h_ho, h_hl, h_res;
-    gx::DevBuf h_bq, h_iq, h_dq, h_perm, ph2pr;   // PairHMM from qualities: staging + the ph2pr table
-    // PairHMM log10 / float64: the fp32 pass's results, the rescue list (its count in the first of
-    // four words, then one word per pair), and the host forms' device outputs
-    gx::DevBuf hm_r32, hm_list, h_res64, h_used;
-    gx::DevBuf nv_pw, nv_po, nv_tw, nv_to, nv_s, nv_s16;   // nvbio front-end staging
-    gx::DevBuf nv_dir, nv_row, nv_src, nv_snk, nv_ops, nv_nops;   // nvbio traceback: workspace + staging
+    gx::DevBuf buf[B_COUNT];
     void release() {
         ws.release_all();
         for (HostSlot &s : slot) s.release();
-        for (gx::DevBuf *b : {&q, &t, &qo, &to, &ql, &tl, &qop, &top, &seed, &o_score, &o_qe, &o_te, &o_qs, &o_ts,
-                              &o_s2, &o_qe2, &o_te2, &o_cig, &o_nops, &lens_max, &h_reads, &h_ro, &h_rl, &h_qm,
-                              &h_de, &h_xi, &h_al, &h_haps, &h_ho, &h_hl, &h_res, &h_bq, &h_iq, &h_dq, &h_perm,
-                              &ph2pr, &hm_r32, &hm_list, &h_res64, &h_used, &nv_pw, &nv_po, &nv_tw, &nv_to, &nv_s, &nv_s16, &nv_dir, &nv_row,
-                              &nv_src, &nv_snk, &nv_ops, &nv_nops})
-            b->release();
+        for (gx::DevBuf &b : buf) b.release();
     }
 };
 
@@ -67,22 +76,65 @@ hipStream_t gx::engine_stream(gasalx_engine *e) { return e->stream; }
 
 namespace {
 
-__attribute__((unused)) uint32_t host_max(const uint32_t *a, uint32_t n) {
+// Every engine call starts here, after its own argument checks: the engine's device becomes
+// current, and the call runs on the caller's stream or, without one (every host form), the engine's.
+int enter(gasalx_engine *eng, void *stream, hipStream_t *st) {
+    CK(hipSetDevice(eng->device));
+    *st = stream ? (hipStream_t)stream : eng->stream;
+    return GASALX_OK;
+}
+
+// Every host form ends here: rc is what its launches returned, back the results to copy out.
+// A host form synchronises on an error too: its staging buffers are reused by the next call, which
+// must not overwrite what this call's queued copies and kernels still read.  The device forms
+// return an error as it is: the caller owns the stream and decides when to wait for it.
+struct Back { void *host; const void *dev; size_t bytes; };
+int host_finish(hipStream_t st, int rc, std::initializer_list<Back> back) {
+    if (rc) { (void)hipStreamSynchronize(st); return rc; }
+    for (const Back &b : back)
+        if (b.host) CK(hipMemcpyAsync(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost, st));
+    CK(hipStreamSynchronize(st));
+    return GASALX_OK;
+}
+
+uint32_t host_max(const uint32_t *a, uint32_t n) {
     uint32_t m = 0;
     for (uint32_t i = 0; i < n; i++) m = std::max(m, a[i]);
     return m;
 }
 
-// Read back max(q_lens), max(t_lens) from device memory (synchronises `st`).
-int device_max_lens(gasalx_engine *eng, const uint32_t *dq, const uint32_t *dt, uint32_t n, hipStream_t st,
-                    uint32_t *mq, uint32_t *mt) {
+// max over i of off[i+1] - off[i]
+uint32_t max_span(const uint32_t *off, uint32_t n) {
+    uint32_t m = 0;
+    for (uint32_t i = 0; i < n; i++) m = std::max(m, off[i + 1] - off[i]);
+    return m;
+}
+
+// The maxima of a device batch's two length arrays where the caller left one of them zero: both
+// read back (synchronises `st`).
+int device_max_lens(const uint32_t *dq, const uint32_t *dt, uint32_t n, hipStream_t st, uint32_t *mq, uint32_t *mt) {
+    if ((*mq && *mt) || !n) return GASALX_OK;
     std::vector<uint32_t> hq(n), ht(n);
     CK(hipMemcpyAsync(hq.data(), dq, n * 4ull, hipMemcpyDeviceToHost, st));
     CK(hipMemcpyAsync(ht.data(), dt, n * 4ull, hipMemcpyDeviceToHost, st));
     CK(hipStreamSynchronize(st));
-    (void)eng;
     *mq = host_max(hq.data(), n);
     *mt = host_max(ht.data(), n);
+    return GASALX_OK;
+}
+
+// The same for device string sets: the offsets read back (synchronises `st`) where *max_p is zero
+// or, with txt (per-pair texts that have a bound to give), *max_t is.
+int device_max_spans(const gasalx_nv_strings *pat, const gasalx_nv_strings *txt, uint32_t n, hipStream_t st,
+                     uint32_t *max_p, uint32_t *max_t) {
+    const bool texts = txt && txt->offsets;
+    if (!n || (*max_p && !(texts && !*max_t))) return GASALX_OK;
+    std::vector<uint32_t> po(n + 1), to(texts ? n + 1 : 0);
+    CK(hipMemcpyAsync(po.data(), pat->offsets, (n + 1) * 4ull, hipMemcpyDeviceToHost, st));
+    if (texts) CK(hipMemcpyAsync(to.data(), txt->offsets, (n + 1) * 4ull, hipMemcpyDeviceToHost, st));
+    CK(hipStreamSynchronize(st));
+    if (!*max_p) *max_p = max_span(po.data(), n);
+    if (texts && !*max_t) *max_t = max_span(to.data(), n);
     return GASALX_OK;
 }
 
@@ -96,26 +148,72 @@ int stage_in(gx::DevBuf &d, const T *h, size_t count, hipStream_t st, T **dptr) 
     return GASALX_OK;
 }
 
-// Stage a host PairHMM batch (parameter form) into the engine's device buffers; db = its device image
-// with max_read_len / max_hap_len filled in.
+// Stages the arrays of a host batch into the engine's buffers: in(buffer, field, count) replaces
+// the host pointer in `field` by its device copy (NULL stays NULL).  After a failure the remaining
+// calls do nothing and rc holds the code.
+struct Stager {
+    gasalx_engine *eng;
+    hipStream_t st;
+    int rc = GASALX_OK;
+    template <class T>
+    void operator()(Buf b, const T *&field, size_t count) {
+        T *d = nullptr;
+        if (!rc) rc = stage_in(eng->buf[b], field, count, st, &d);
+        field = d;
+    }
+};
+
+// The three input forms, staged: db (dp, dt) = the device image of the host batch.
+// PairHMM parameter form; max_read_len / max_hap_len filled in.
 int hmm_stage_host(gasalx_engine *eng, const gasalx_hmm_batch *hb, hipStream_t st, gasalx_hmm_batch &db) {
     const uint32_t n = hb->n_pairs;
     db = *hb;
-    int rc;
-    uint8_t *p8; uint32_t *p32; float *pf;
-    if ((rc = stage_in(eng->h_reads, hb->reads, hb->read_bytes, st, &p8))) return rc; db.reads = p8;
-    if ((rc = stage_in(eng->h_ro, hb->read_offsets, n, st, &p32))) return rc; db.read_offsets = p32;
-    if ((rc = stage_in(eng->h_rl, hb->read_lens, n, st, &p32))) return rc; db.read_lens = p32;
-    if ((rc = stage_in(eng->h_qm, hb->qm, hb->read_bytes, st, &pf))) return rc; db.qm = pf;
-    if ((rc = stage_in(eng->h_de, hb->delta, hb->read_bytes, st, &pf))) return rc; db.delta = pf;
-    if ((rc = stage_in(eng->h_xi, hb->xiksi, hb->read_bytes, st, &pf))) return rc; db.xiksi = pf;
-    if ((rc = stage_in(eng->h_al, hb->alpha, hb->read_bytes, st, &pf))) return rc; db.alpha = pf;
-    if ((rc = stage_in(eng->h_haps, hb->haps, hb->hap_bytes, st, &p8))) return rc; db.haps = p8;
-    if ((rc = stage_in(eng->h_ho, hb->hap_offsets, n, st, &p32))) return rc; db.hap_offsets = p32;
-    if ((rc = stage_in(eng->h_hl, hb->hap_lens, n, st, &p32))) return rc; db.hap_lens = p32;
+    Stager in{eng, st};
+    in(B_READS, db.reads, hb->read_bytes);
+    in(B_RO, db.read_offsets, n);
+    in(B_RL, db.read_lens, n);
+    in(B_QM, db.qm, hb->read_bytes);
+    in(B_DE, db.delta, hb->read_bytes);
+    in(B_XI, db.xiksi, hb->read_bytes);
+    in(B_AL, db.alpha, hb->read_bytes);
+    in(B_HAPS, db.haps, hb->hap_bytes);
+    in(B_HO, db.hap_offsets, n);
+    in(B_HL, db.hap_lens, n);
+    if (in.rc) return in.rc;
     db.max_read_len = hb->max_read_len ? hb->max_read_len : host_max(hb->read_lens, n);
     db.max_hap_len = hb->max_hap_len ? hb->max_hap_len : host_max(hb->hap_lens, n);
     return GASALX_OK;
+}
+
+// PairHMM quality form; the maxima stay the caller's.
+int hmm_stage_quals(gasalx_engine *eng, const gasalx_hmm_qual_batch *hb, hipStream_t st, gasalx_hmm_qual_batch &db) {
+    const uint32_t n = hb->n_pairs;
+    db = *hb;
+    Stager in{eng, st};
+    in(B_READS, db.reads, hb->read_bytes);
+    in(B_BQ, db.base_quals, hb->read_bytes);
+    in(B_IQ, db.ins_quals, hb->read_bytes);
+    in(B_DQ, db.del_quals, hb->read_bytes);
+    in(B_RO, db.read_offsets, n);
+    in(B_RL, db.read_lens, n);
+    in(B_HAPS, db.haps, hb->hap_bytes);
+    in(B_HO, db.hap_offsets, n);
+    in(B_HL, db.hap_lens, n);
+    return in.rc;
+}
+
+// nvbio string pair: patterns and texts (one shared text has no offsets).
+int nv_stage_strings(gasalx_engine *eng, uint32_t n, const gasalx_nv_strings *pat, uint64_t pat_words,
+                     const gasalx_nv_strings *txt, uint64_t txt_words, hipStream_t st, gasalx_nv_strings &dp,
+                     gasalx_nv_strings &dt) {
+    dp = *pat;
+    dt = *txt;
+    Stager in{eng, st};
+    in(B_NV_PW, dp.words, pat_words);
+    in(B_NV_PO, dp.offsets, (size_t)n + 1);
+    in(B_NV_TW, dt.words, txt_words);
+    in(B_NV_TO, dt.offsets, (size_t)n + 1);
+    return in.rc;
 }
 
 bool valid_params(const gasalx_params *p) {
@@ -124,6 +222,385 @@ bool valid_params(const gasalx_params *p) {
     if (p->start_pos < 0 || p->start_pos > 2) return false;
     if (p->head < 0 || p->head > 3 || p->tail < 0 || p->tail > 3) return false;
     return true;
+}
+
+// gasalx_results as a table: field f is the struct's f-th pointer.  Every field holds one 4-byte
+// entry per pair but cigar, whose q_bytes bytes sit at the pairs' query offsets.  The single-shot
+// path stages field f in buffer B_OUT + f; a pipelined chunk lays the per-pair fields out as
+// columns in this order.  The fields' types differ (int32_t *, uint8_t *, uint32_t *), so one array
+// of member pointers cannot name them all; the pointers are read and written as bytes instead
+// (memcpy, so no object is accessed through another pointer type), and the copies move bytes.
+constexpr int kFields = 10, kCigar = 8, kNops = 9;
+static_assert(sizeof(gasalx_results) == kFields * sizeof(void *) && offsetof(gasalx_results, cigar) == kCigar * sizeof(void *) &&
+                  offsetof(gasalx_results, n_cigar_ops) == kNops * sizeof(void *) && B_OUT_LAST - B_OUT + 1 == kFields,
+              "gasalx_results: ten pointers");
+void *get_field(const gasalx_results &r, int f) {
+    void *p;
+    std::memcpy(&p, reinterpret_cast<const char *>(&r) + f * sizeof(void *), sizeof(p));
+    return p;
+}
+void set_field(gasalx_results &r, int f, void *p) {
+    std::memcpy(reinterpret_cast<char *>(&r) + f * sizeof(void *), &p, sizeof(p));
+}
+size_t field_bytes(int f, uint32_t n, uint32_t q_bytes) { return f == kCigar ? q_bytes : (size_t)n * 4; }
+
+// Sequences laid out back to back from offset 0 (what gasal_host_batch_fill
+// produces): chunks of pairs then own contiguous byte ranges.
+bool contiguous(const uint32_t *off, const uint32_t *len, uint32_t n, uint32_t bytes) {
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        if (off[i] != at) return false;
+        at += gx::pad8(len[i]);
+    }
+    return at == bytes;
+}
+
+// Large host batches: chunks of pairs alternate between two streams, so the
+// H2D copy of chunk k+1 overlaps the kernels of chunk k (the copies run at
+// PCIe speed from pageable memory on this platform, tools/h2d_probe.cpp).
+// Per chunk: two sequence copies plus ONE copy of everything per-pair
+// (rebased offsets, lengths, ops, seeds, the caller's output contents) and
+// ONE copy back of the per-pair outputs.  mq, mt: the batch's maximum lengths.
+int align_host_pipelined(gasalx_engine *eng, const gasalx_params *params, const gasalx_batch *hb,
+                         const gasalx_results *ho, uint32_t chunk, bool tb, uint32_t mq, uint32_t mt) {
+    const uint32_t n = hb->n_alns;
+    // the caller's per-pair result fields, one column each: all but cigar (the slot's own buffer,
+    // copied on its own), n_cigar_ops only with traceback
+    uint8_t *hcol[kFields];
+    for (int f = 0; f < kFields; f++)
+        hcol[f] = (f == kCigar || (f == kNops && !tb)) ? nullptr : static_cast<uint8_t *>(get_field(*ho, f));
+    // outputs every kernel of the algorithm writes (generic.hpp, wavefront*.hpp):
+    // the score for all aligning algos, the ends for all but GLOBAL
+    const bool ends = params->algo == 2 || params->algo == 3 || params->algo == 5 || params->algo == 6;
+    const bool aligns = ends || params->algo == 1;   // UNKNOWN / MICROLOCAL launch nothing
+    const bool written[kFields] = {aligns, ends, ends};
+    for (HostSlot &s : eng->slot) {
+        if (!s.st) CK(hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking));
+        s.ws.device = eng->device;
+    }
+    // per-pair region of a chunk of m pairs: 4-byte columns, 16-byte aligned
+    auto col = [](uint32_t m) { return ((size_t)m * 4 + 15) & ~(size_t)15; };
+    auto bcol = [](uint32_t m) { return ((size_t)m + 15) & ~(size_t)15; };
+    struct Pending { uint32_t i0, i1; uint64_t qlo, qhi; size_t out_at, out_len; bool live; } pend[2] = {};
+    auto drain = [&](int k) -> int {   // the slot's previous chunk: results back to the caller
+        Pending &pp = pend[k];
+        if (!pp.live) return GASALX_OK;
+        HostSlot &s = eng->slot[k];
+        const uint32_t m = pp.i1 - pp.i0;
+        if (pp.out_len)
+            CK(hipMemcpyAsync(s.hmeta.data() + pp.out_at, s.buf[S_META].as<uint8_t>() + pp.out_at, pp.out_len,
+                              hipMemcpyDeviceToHost, s.st));
+        if (tb && ho->cigar)
+            CK(hipMemcpyAsync(ho->cigar + pp.qlo, s.buf[S_CIG].p, pp.qhi - pp.qlo, hipMemcpyDeviceToHost, s.st));
+        CK(hipStreamSynchronize(s.st));
+        size_t at = pp.out_at;
+        for (int f = 0; f < kFields; f++)
+            if (hcol[f]) { std::memcpy(hcol[f] + pp.i0 * 4ull, s.hmeta.data() + at, m * 4ull); at += col(m); }
+        pp.live = false;
+        return GASALX_OK;
+    };
+    int rc = GASALX_OK, k = 0;
+    for (uint32_t i0 = 0; i0 < n; i0 += chunk, k ^= 1) {
+        const uint32_t i1 = std::min(n, i0 + chunk), m = i1 - i0;
+        HostSlot &s = eng->slot[k];
+        if ((rc = drain(k))) return rc;
+        const uint64_t qlo = hb->q_offsets[i0], qhi = (uint64_t)hb->q_offsets[i1 - 1] + gx::pad8(hb->q_lens[i1 - 1]);
+        const uint64_t tlo = hb->t_offsets[i0], thi = (uint64_t)hb->t_offsets[i1 - 1] + gx::pad8(hb->t_lens[i1 - 1]);
+        // host image of the per-pair region
+        size_t at = 0;
+        const size_t a_qo = at; at += col(m);
+        const size_t a_to = at; at += col(m);
+        const size_t a_ql = at; at += col(m);
+        const size_t a_tl = at; at += col(m);
+        const size_t a_qop = at; if (hb->q_ops) at += bcol(m);
+        const size_t a_top = at; if (hb->t_ops) at += bcol(m);
+        const size_t a_seed = at; if (hb->seed_scores) at += col(m);
+        const size_t out_at = at;
+        size_t a_out[kFields];
+        for (int f = 0; f < kFields; f++) { a_out[f] = at; if (hcol[f]) at += col(m); }
+        const size_t total = at;
+        s.hmeta.resize(total);
+        uint8_t *h = s.hmeta.data();
+        uint32_t *qo = reinterpret_cast<uint32_t *>(h + a_qo), *to = reinterpret_cast<uint32_t *>(h + a_to);
+        for (uint32_t i = 0; i < m; i++) {
+            qo[i] = hb->q_offsets[i0 + i] - (uint32_t)qlo;
+            to[i] = hb->t_offsets[i0 + i] - (uint32_t)tlo;
+        }
+        std::memcpy(h + a_ql, hb->q_lens + i0, m * 4ull);
+        std::memcpy(h + a_tl, hb->t_lens + i0, m * 4ull);
+        if (hb->q_ops) std::memcpy(h + a_qop, hb->q_ops + i0, m);
+        if (hb->t_ops) std::memcpy(h + a_top, hb->t_ops + i0, m);
+        if (hb->seed_scores) std::memcpy(h + a_seed, hb->seed_scores + i0, m * 4ull);
+        // the caller's contents, so fields the reference does not write come back
+        // unchanged; fields every kernel of this algo writes need no copy in
+        for (int f = 0; f < kFields; f++)
+            if (hcol[f] && !written[f]) std::memcpy(h + a_out[f], hcol[f] + i0 * 4ull, m * 4ull);
+        CK(s.buf[S_META].reserve(total + 16));
+        uint8_t *dm = s.buf[S_META].as<uint8_t>();
+        uint8_t *p8;
+        // isPacked (score-only): the caller's pages hold 4-bit words, half the bytes of the
+        // unpacked units that offsets and q_bytes count (pack_rc_seqs.h:24-31); only those move
+        const uint64_t pk = params->is_packed ? 2 : 1;
+        if ((rc = stage_in(s.buf[S_Q], hb->q_batch + qlo / pk, (qhi - qlo) / pk, s.st, &p8))) return rc;
+        gasalx_batch db = *hb;
+        db.q_batch = p8;
+        if ((rc = stage_in(s.buf[S_T], hb->t_batch + tlo / pk, (thi - tlo) / pk, s.st, &p8))) return rc;
+        db.t_batch = p8;
+        CK(hipMemcpyAsync(dm, h, total, hipMemcpyHostToDevice, s.st));
+        db.q_offsets = reinterpret_cast<uint32_t *>(dm + a_qo);
+        db.t_offsets = reinterpret_cast<uint32_t *>(dm + a_to);
+        db.q_lens = reinterpret_cast<uint32_t *>(dm + a_ql);
+        db.t_lens = reinterpret_cast<uint32_t *>(dm + a_tl);
+        db.q_ops = hb->q_ops ? dm + a_qop : nullptr;
+        db.t_ops = hb->t_ops ? dm + a_top : nullptr;
+        db.seed_scores = hb->seed_scores ? reinterpret_cast<uint32_t *>(dm + a_seed) : nullptr;
+        db.q_bytes = (uint32_t)(qhi - qlo);
+        db.t_bytes = (uint32_t)(thi - tlo);
+        db.n_alns = m;
+        db.max_q_len = mq;
+        db.max_t_len = mt;
+        gasalx_results dout;
+        for (int f = 0; f < kFields; f++) set_field(dout, f, hcol[f] ? dm + a_out[f] : nullptr);
+        if (tb && ho->cigar) {
+            CK(s.buf[S_CIG].reserve(qhi - qlo + 16));
+            dout.cigar = s.buf[S_CIG].as<uint8_t>();
+        }
+        gx::BatchShape shape;
+        shape.max_q = mq;
+        shape.max_t = mt;
+        shape.sort = gx::uneven_lengths(*params, hb->q_lens + i0, hb->t_lens + i0, m);
+        shape.one_t8 = gx::one_pad8(hb->t_lens + i0, m, shape.max_t);
+        shape.tb_split = false;   // the two slots' streams already overlap one chunk's walk with the next DP
+        if ((rc = gx::align_device(s.ws, *params, db, dout, s.st, shape))) {
+            for (HostSlot &x : eng->slot) (void)hipStreamSynchronize(x.st);
+            return rc;
+        }
+        pend[k] = {i0, i1, qlo, qhi, out_at, total - out_at, true};
+    }
+    for (int j = 0; j < 2; j++) {
+        k ^= 1;
+        if ((rc = drain(k))) return rc;
+    }
+    return GASALX_OK;
+}
+
+// ph2pr[q] = powf(10, -q/10) on the host, as the reference builds it (tile_1.cu:216-220)
+void ph2pr_table(float *t) {
+    for (int i = 0; i < 128; i++) t[i] = powf(10.f, -((float)i) / 10.f);
+}
+
+// The engine's device copy of the table (uploaded once, synchronously).
+int ph2pr_device(gasalx_engine *eng, const float **out) {
+    gx::DevBuf &tab = eng->buf[B_PH2PR];
+    if (!tab.p) {
+        float t[128];
+        ph2pr_table(t);
+        CK(tab.reserve(sizeof(t)));
+        CK(hipMemcpy(tab.p, t, sizeof(t), hipMemcpyHostToDevice));
+    }
+    *out = tab.as<float>();
+    return GASALX_OK;
+}
+
+bool hmm_qual_batch_ok(const gasalx_hmm_qual_batch *b) {
+    return b && (b->n_pairs == 0 || (b->reads && b->read_offsets && b->read_lens && b->base_quals && b->ins_quals &&
+                                     b->del_quals && b->haps && b->hap_offsets && b->hap_lens));
+}
+
+// The fp32 pass of a host batch in parameter form: staged (db = the device image), results in
+// B_RES.  Like quals_host_fp32 it synchronises the stream only when its launch fails; after a good
+// launch the caller queues what follows (the copy back, the rescue pass) and waits once.
+int hmm_host_fp32(gasalx_engine *eng, const gasalx_hmm_batch *hb, hipStream_t st, gasalx_hmm_batch &db) {
+    int rc = hmm_stage_host(eng, hb, st, db);
+    if (rc) return rc;
+    CK(eng->buf[B_RES].reserve((size_t)hb->n_pairs * 4 + 16));
+    rc = gx::pairhmm_device(eng->ws, db, eng->buf[B_RES].as<float>(), st, db.max_read_len, db.max_hap_len);
+    if (rc) (void)hipStreamSynchronize(st);   // on error only: the caller's host_finish is the one wait of a good call
+    return rc;
+}
+
+// The fp32 pass of a host batch in quality form: pairs staged into the engine's device buffers
+// (db = the device image, max lengths filled in), run sorted by (read length, haplotype length)
+// in classes of reads that share a lane-group size, results in B_RES by pair index.
+// perm: the slot order, the caller's so that it outlives its copy (until the stream is synchronised).
+int quals_host_fp32(gasalx_engine *eng, const gasalx_hmm_qual_batch *hb, hipStream_t st, gasalx_hmm_qual_batch &db,
+                    const float **tab_out, std::vector<uint32_t> &perm) {
+    const uint32_t n = hb->n_pairs;
+    // slots in (read length, haplotype length) order (tile_1.cu:180-195 operator<, :325)
+    perm.resize(n);
+    for (uint32_t i = 0; i < n; i++) perm[i] = i;
+    std::stable_sort(perm.begin(), perm.end(), [&](uint32_t x, uint32_t y) {
+        const uint32_t rx = hb->read_lens[x], ry = hb->read_lens[y];
+        return rx != ry ? rx < ry : hb->hap_lens[x] < hb->hap_lens[y];
+    });
+    // classes: runs of slots whose reads need the same lane-group size
+    std::vector<gx::HmmClass> classes;
+    uint32_t mr = 0, mh = 0;
+    for (uint32_t s = 0; s < n; s++) {
+        const uint32_t r = hb->read_lens[perm[s]], h = hb->hap_lens[perm[s]];
+        const int g = gx::pairhmm_group(r);
+        if (classes.empty() || gx::pairhmm_group(classes.back().max_r) != g) classes.push_back({s, s, 0, 0});
+        gx::HmmClass &c = classes.back();
+        c.slot1 = s + 1;
+        c.max_r = std::max(c.max_r, r);
+        c.max_h = std::max(c.max_h, h);
+        mr = std::max(mr, r);
+        mh = std::max(mh, h);
+    }
+    int rc = hmm_stage_quals(eng, hb, st, db);
+    if (rc) return rc;
+    db.max_read_len = mr;
+    db.max_hap_len = mh;
+    uint32_t *dperm;
+    if ((rc = stage_in(eng->buf[B_PERM], perm.data(), n, st, &dperm))) return rc;
+    CK(eng->buf[B_RES].reserve((size_t)n * 4 + 16));
+    if ((rc = ph2pr_device(eng, tab_out))) return rc;
+    rc = gx::pairhmm_quals_device(eng->ws, db, eng->buf[B_RES].as<float>(), st, *tab_out, dperm, classes.data(),
+                                  (int)classes.size(), 0, 0);
+    if (rc) (void)hipStreamSynchronize(st);   // on error only, as hmm_host_fp32
+    return rc;
+}
+
+// ---- PairHMM in float64 and the log10 entry points (pairhmm64.hip) ----
+// The rescue pass after an fp32 pass whose results are at r32 (device): scratch from the engine.
+int log10_rescue(gasalx_engine *eng, const gx::Hmm64Src &src, uint32_t n, const float *r32, float min_accepted,
+                 double *out, uint8_t *used, hipStream_t st, uint32_t mr, uint32_t mh) {
+    CK(eng->buf[B_HM_LIST].reserve(((size_t)n + 4) * 4));
+    uint32_t *count = eng->buf[B_HM_LIST].as<uint32_t>();
+    return gx::pairhmm_log10_device(src, n, r32, min_accepted, out, used, count, count + 4, st, mr, mh);
+}
+
+// Host forms: device outputs in B_RES64 / B_USED, copied back with the count.
+int log10_host_finish(gasalx_engine *eng, const gx::Hmm64Src &src, uint32_t n, float min_accepted, double *hlog,
+                      uint8_t *hused, uint32_t *n_rescued, hipStream_t st, uint32_t mr, uint32_t mh) {
+    gx::DevBuf &res = eng->buf[B_RES64], &used = eng->buf[B_USED];
+    CK(res.reserve((size_t)n * 8 + 16));
+    CK(used.reserve((size_t)n + 16));
+    int rc = log10_rescue(eng, src, n, eng->buf[B_RES].as<float>(), min_accepted, res.as<double>(),
+                          hused ? used.as<uint8_t>() : nullptr, st, mr, mh);
+    uint32_t cnt = 0;
+    rc = host_finish(st, rc, {{hlog, res.p, (size_t)n * 8}, {hused, used.p, n}, {&cnt, eng->buf[B_HM_LIST].p, 4}});
+    if (!rc && n_rescued) *n_rescued = cnt;
+    return rc;
+}
+
+// The float64 forward values of a staged host batch (src points at its device image), copied out.
+int hmm64_host_run(gasalx_engine *eng, const gx::Hmm64Src &src, uint32_t n, double *hres, hipStream_t st, uint32_t mr,
+                   uint32_t mh) {
+    gx::DevBuf &res = eng->buf[B_RES64];
+    CK(res.reserve((size_t)n * 8 + 16));
+    const int rc = gx::pairhmm64_device(src, n, res.as<double>(), st, mr, mh);
+    return host_finish(st, rc, {{hres, res.p, (size_t)n * 8}});
+}
+
+// nvbio BatchedAlignmentTraceback (nvtrace.hpp).  nvbio keeps its DP columns and checkpoints in
+// int16 (alignment/utils.h:49-64): the scores of every cell must stay within them.
+int64_t nv_score_mag(const gasalx_nv_aligner *al) {
+    if (al->aligner == GASALX_NV_ED) return 1;   // ED: EditDistanceSWScheme's 0 / -1 (ed_utils.h:45-52)
+    return std::max<int64_t>({std::abs((int64_t)al->match), std::abs((int64_t)al->mismatch),
+                              std::abs((int64_t)al->gap_open), std::abs((int64_t)al->gap_ext),
+                              std::abs((int64_t)al->deletion), std::abs((int64_t)al->insertion), 1});
+}
+
+// nvbio traceback workspace per call (the engine's: flags of every cell, one DP row per pair) and
+// the chunk budget the device entry points split a batch by
+constexpr uint64_t kNvTbBudget = 4ull << 30;
+// GASALX_NV_TB_BUDGET (bytes) replaces it for tests that force several chunks; read on every
+// call, and unset, empty, zero or unparsable leave the 4 GiB
+uint64_t nv_tb_budget() {
+    const char *e = std::getenv("GASALX_NV_TB_BUDGET");
+    if (!e || !*e) return kNvTbBudget;
+    for (const char *c = e; *c; c++)
+        if (*c < '0' || *c > '9') return kNvTbBudget;
+    errno = 0;
+    const unsigned long long v = std::strtoull(e, nullptr, 10);
+    return (errno || !v) ? kNvTbBudget : (uint64_t)v;
+}
+// pairs per chunk of a batch of n whose workspace takes `per` bytes per pair
+uint64_t nv_tb_chunk(uint32_t n, uint64_t per) {
+    return std::max<uint64_t>(1, std::min<uint64_t>(n, nv_tb_budget() / std::max<uint64_t>(per, 1)));
+}
+
+int nv_tb_checks(const gasalx_nv_aligner *al, uint32_t max_p, uint32_t max_t, uint32_t ops_stride) {
+    const int64_t mag = nv_score_mag(al);
+    if (((int64_t)max_p + max_t + 2) * mag > 32767) {
+        gx::set_error("traceback: scores would leave nvbio's int16 columns (lengths x |score|)");
+        return GASALX_ERANGE;
+    }
+    if (ops_stride < max_p + max_t) { gx::set_error("traceback: ops_stride < max pattern + max text length"); return GASALX_EINVAL; }
+    if ((uint64_t)max_p * max_t > (1ull << 24)) { gx::set_error("traceback: pattern x text above 16 M cells"); return GASALX_ERANGE; }
+    return GASALX_OK;
+}
+
+// nvbio BatchedBandedAlignmentTraceback<band> (nvtrace.hpp).  nvbio's checkpoints are int16
+// pairs clamped at -32736 (gotoh_banded_inl.h:234-239): every score must stay above it.
+int nv_btb_checks(const gasalx_nv_aligner *al, uint32_t band, uint32_t max_p, uint32_t ops_stride) {
+    if (band < 2 || band > 32) { gx::set_error("band length must be 2..32"); return GASALX_EINVAL; }
+    if (((int64_t)max_p + band + 3) * nv_score_mag(al) > 32736) {
+        gx::set_error("banded traceback: scores would leave nvbio's int16 checkpoints (lengths x |score|)");
+        return GASALX_ERANGE;
+    }
+    if ((uint64_t)ops_stride < 2ull * max_p + band) {
+        gx::set_error("banded traceback: ops_stride < 2 x max pattern length + band");
+        return GASALX_EINVAL;
+    }
+    return GASALX_OK;
+}
+
+// The outputs of a traceback call, device or host.
+struct NvTbOut {
+    int32_t *scores;
+    uint32_t *sources, *sinks;
+    uint8_t *ops;
+    uint32_t ops_stride;
+    uint32_t *n_ops;
+};
+
+// A traceback batch in chunks of `chunk` pairs over the engine's workspace (band 0: the full DP):
+// the chunk from pair s on works on offsets + s, scores + s, sources + 2s, sinks + 2s,
+// ops + s * ops_stride and n_ops + s.
+int nv_tb_chunks(gasalx_engine *eng, const gasalx_nv_aligner *al, uint32_t band, uint32_t n, const gasalx_nv_strings *pat,
+                 const gasalx_nv_strings *txt, uint32_t max_p, uint32_t max_t, const NvTbOut &o, uint32_t chunk,
+                 hipStream_t st) {
+    gx::DevBuf &dir = eng->buf[B_NV_DIR];
+    for (uint32_t s = 0; s < n; s += chunk) {
+        const uint32_t m = std::min(chunk, n - s);
+        gasalx_nv_strings p = *pat, t = *txt;
+        p.offsets = pat->offsets + s;
+        if (txt->offsets) t.offsets = txt->offsets + s;
+        int32_t *scores = o.scores + s;
+        uint32_t *sources = o.sources + 2ull * s, *sinks = o.sinks + 2ull * s, *n_ops = o.n_ops + s;
+        uint8_t *ops = o.ops + (size_t)s * o.ops_stride;
+        const int rc = band ? gx::nv_banded_traceback_device(*al, band, m, p, t, max_p, dir.as<uint32_t>(), scores, sources,
+                                                             sinks, ops, o.ops_stride, n_ops, st)
+                            : gx::nv_traceback_device(*al, m, p, t, max_p, max_t, dir.as<uint8_t>(),
+                                                      eng->buf[B_NV_ROW].as<int32_t>(), scores, sources, sinks, ops,
+                                                      o.ops_stride, n_ops, st);
+        if (rc) return rc;
+    }
+    return GASALX_OK;
+}
+
+// The two traceback host forms after staging: the five device outputs reserved, the device form
+// (band 0: the full DP) run on them, the results copied to the caller's arrays `h`.
+int nv_tb_host_run(gasalx_engine *eng, const gasalx_nv_aligner *al, uint32_t band, uint32_t n,
+                   const gasalx_nv_strings *dp, const gasalx_nv_strings *dt, uint32_t max_p, uint32_t max_t,
+                   const NvTbOut &h, hipStream_t st) {
+    gx::DevBuf &s = eng->buf[B_NV_S], &src = eng->buf[B_NV_SRC], &snk = eng->buf[B_NV_SNK], &ops = eng->buf[B_NV_OPS],
+               &nops = eng->buf[B_NV_NOPS];
+    CK(s.reserve((size_t)n * 4));
+    CK(src.reserve((size_t)n * 8));
+    CK(snk.reserve((size_t)n * 8));
+    CK(ops.reserve((size_t)n * h.ops_stride + 64));
+    CK(nops.reserve((size_t)n * 4));
+    const int rc =
+        band ? gasalx_nv_banded_traceback_device(eng, al, band, n, dp, dt, max_p, s.as<int32_t>(), src.as<uint32_t>(),
+                                                 snk.as<uint32_t>(), ops.as<uint8_t>(), h.ops_stride, nops.as<uint32_t>(), st)
+             : gasalx_nv_traceback_device(eng, al, n, dp, dt, max_p, max_t, s.as<int32_t>(), src.as<uint32_t>(),
+                                          snk.as<uint32_t>(), ops.as<uint8_t>(), h.ops_stride, nops.as<uint32_t>(), st);
+    return host_finish(st, rc, {{h.scores, s.p, (size_t)n * 4}, {h.sources, src.p, (size_t)n * 8},
+                                {h.sinks, snk.p, (size_t)n * 8}, {h.ops, ops.p, (size_t)n * h.ops_stride},
+                                {h.n_ops, nops.p, (size_t)n * 4}});
 }
 
 }  // namespace
@@ -178,170 +655,15 @@ int gasalx_describe_plan(const gasalx_params *params, uint32_t max_q_len, uint32
 int gasalx_align_device(gasalx_engine *eng, const gasalx_params *params, const gasalx_batch *b,
                         const gasalx_results *out, void *stream) {
     if (!eng || !valid_params(params) || !b || !out) { gx::set_error("null argument"); return GASALX_EINVAL; }
-    CK(hipSetDevice(eng->device));
-    hipStream_t st = stream ? (hipStream_t)stream : eng->stream;
+    hipStream_t st;
+    int rc = enter(eng, stream, &st);
+    if (rc) return rc;
     gx::BatchShape shape;
     shape.max_q = b->max_q_len;
     shape.max_t = b->max_t_len;
-    if ((shape.max_q == 0 || shape.max_t == 0) && b->n_alns) {
-        int rc = device_max_lens(eng, b->q_lens, b->t_lens, b->n_alns, st, &shape.max_q, &shape.max_t);
-        if (rc) return rc;
-    }
+    if ((rc = device_max_lens(b->q_lens, b->t_lens, b->n_alns, st, &shape.max_q, &shape.max_t))) return rc;
     return gx::align_device(eng->ws, *params, *b, *out, st, shape);
 }
-
-namespace {
-
-
-// Sequences laid out back to back from offset 0 (what gasal_host_batch_fill
-// produces): chunks of pairs then own contiguous byte ranges.
-bool contiguous(const uint32_t *off, const uint32_t *len, uint32_t n, uint32_t bytes) {
-    uint64_t at = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        if (off[i] != at) return false;
-        at += gx::pad8(len[i]);
-    }
-    return at == bytes;
-}
-
-// Large host batches: chunks of pairs alternate between two streams, so the
-// H2D copy of chunk k+1 overlaps the kernels of chunk k (the copies run at
-// PCIe speed from pageable memory on this platform, tools/h2d_probe.cpp).
-// Per chunk: two sequence copies plus ONE copy of everything per-pair
-// (rebased offsets, lengths, ops, seeds, the caller's output contents) and
-// ONE copy back of the per-pair outputs.
-int align_host_pipelined(gasalx_engine *eng, const gasalx_params *params, const gasalx_batch *hb,
-                         const gasalx_results *ho, uint32_t chunk) {
-    const uint32_t n = hb->n_alns;
-    const bool tb = params->start_pos == 2;
-    const uint32_t mq = hb->max_q_len ? hb->max_q_len : host_max(hb->q_lens, n);
-    const uint32_t mt = hb->max_t_len ? hb->max_t_len : host_max(hb->t_lens, n);
-    int32_t *const hout[8] = {ho->aln_score, ho->q_end, ho->t_end, ho->q_start,
-                              ho->t_start, ho->aln_score2, ho->q_end2, ho->t_end2};
-    uint32_t *const hnops = tb ? ho->n_cigar_ops : nullptr;
-    // outputs every kernel of the algorithm writes (generic.hpp, wavefront*.hpp):
-    // the score for all aligning algos, the ends for all but GLOBAL
-    const bool ends = params->algo == 2 || params->algo == 3 || params->algo == 5 || params->algo == 6;
-    const bool aligns = ends || params->algo == 1;   // UNKNOWN / MICROLOCAL launch nothing
-    const bool written[8] = {aligns, ends, ends, false, false, false, false, false};
-    for (HostSlot &s : eng->slot) {
-        if (!s.st) CK(hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking));
-        s.ws.device = eng->device;
-    }
-    // per-pair region of a chunk of m pairs: 4-byte columns, 16-byte aligned
-    auto col = [](uint32_t m) { return ((size_t)m * 4 + 15) & ~(size_t)15; };
-    auto bcol = [](uint32_t m) { return ((size_t)m + 15) & ~(size_t)15; };
-    struct Pending { uint32_t i0, i1; uint64_t qlo, qhi; size_t out_at, out_len; bool live; } pend[2] = {};
-    auto drain = [&](int k) -> int {   // the slot's previous chunk: results back to the caller
-        Pending &pp = pend[k];
-        if (!pp.live) return GASALX_OK;
-        HostSlot &s = eng->slot[k];
-        const uint32_t m = pp.i1 - pp.i0;
-        if (pp.out_len)
-            CK(hipMemcpyAsync(s.hmeta.data() + pp.out_at, s.meta.as<uint8_t>() + pp.out_at, pp.out_len,
-                              hipMemcpyDeviceToHost, s.st));
-        if (tb && ho->cigar)
-            CK(hipMemcpyAsync(ho->cigar + pp.qlo, s.cig.p, pp.qhi - pp.qlo, hipMemcpyDeviceToHost, s.st));
-        CK(hipStreamSynchronize(s.st));
-        size_t at = pp.out_at;
-        for (int f = 0; f < 8; f++)
-            if (hout[f]) { std::memcpy(hout[f] + pp.i0, s.hmeta.data() + at, m * 4ull); at += col(m); }
-        if (hnops) std::memcpy(hnops + pp.i0, s.hmeta.data() + at, m * 4ull);
-        pp.live = false;
-        return GASALX_OK;
-    };
-    int rc = GASALX_OK, k = 0;
-    for (uint32_t i0 = 0; i0 < n; i0 += chunk, k ^= 1) {
-        const uint32_t i1 = std::min(n, i0 + chunk), m = i1 - i0;
-        HostSlot &s = eng->slot[k];
-        if ((rc = drain(k))) return rc;
-        const uint64_t qlo = hb->q_offsets[i0], qhi = (uint64_t)hb->q_offsets[i1 - 1] + gx::pad8(hb->q_lens[i1 - 1]);
-        const uint64_t tlo = hb->t_offsets[i0], thi = (uint64_t)hb->t_offsets[i1 - 1] + gx::pad8(hb->t_lens[i1 - 1]);
-        // host image of the per-pair region
-        size_t at = 0;
-        const size_t a_qo = at; at += col(m);
-        const size_t a_to = at; at += col(m);
-        const size_t a_ql = at; at += col(m);
-        const size_t a_tl = at; at += col(m);
-        const size_t a_qop = at; if (hb->q_ops) at += bcol(m);
-        const size_t a_top = at; if (hb->t_ops) at += bcol(m);
-        const size_t a_seed = at; if (hb->seed_scores) at += col(m);
-        const size_t out_at = at;
-        size_t a_out[8];
-        for (int f = 0; f < 8; f++) { a_out[f] = at; if (hout[f]) at += col(m); }
-        const size_t a_nops = at; if (hnops) at += col(m);
-        const size_t total = at;
-        s.hmeta.resize(total);
-        uint8_t *h = s.hmeta.data();
-        uint32_t *qo = reinterpret_cast<uint32_t *>(h + a_qo), *to = reinterpret_cast<uint32_t *>(h + a_to);
-        for (uint32_t i = 0; i < m; i++) {
-            qo[i] = hb->q_offsets[i0 + i] - (uint32_t)qlo;
-            to[i] = hb->t_offsets[i0 + i] - (uint32_t)tlo;
-        }
-        std::memcpy(h + a_ql, hb->q_lens + i0, m * 4ull);
-        std::memcpy(h + a_tl, hb->t_lens + i0, m * 4ull);
-        if (hb->q_ops) std::memcpy(h + a_qop, hb->q_ops + i0, m);
-        if (hb->t_ops) std::memcpy(h + a_top, hb->t_ops + i0, m);
-        if (hb->seed_scores) std::memcpy(h + a_seed, hb->seed_scores + i0, m * 4ull);
-        // the caller's contents, so fields the reference does not write come back
-        // unchanged; fields every kernel of this algo writes need no copy in
-        for (int f = 0; f < 8; f++)
-            if (hout[f] && !written[f]) std::memcpy(h + a_out[f], hout[f] + i0, m * 4ull);
-        if (hnops) std::memcpy(h + a_nops, hnops + i0, m * 4ull);
-        CK(s.meta.reserve(total + 16));
-        uint8_t *dm = s.meta.as<uint8_t>();
-        uint8_t *p8;
-        // isPacked (score-only): the caller's pages hold 4-bit words, half the bytes of the
-        // unpacked units that offsets and q_bytes count (pack_rc_seqs.h:24-31); only those move
-        const uint64_t pk = params->is_packed ? 2 : 1;
-        if ((rc = stage_in(s.q, hb->q_batch + qlo / pk, (qhi - qlo) / pk, s.st, &p8))) return rc;
-        gasalx_batch db = *hb;
-        db.q_batch = p8;
-        if ((rc = stage_in(s.t, hb->t_batch + tlo / pk, (thi - tlo) / pk, s.st, &p8))) return rc;
-        db.t_batch = p8;
-        CK(hipMemcpyAsync(dm, h, total, hipMemcpyHostToDevice, s.st));
-        db.q_offsets = reinterpret_cast<uint32_t *>(dm + a_qo);
-        db.t_offsets = reinterpret_cast<uint32_t *>(dm + a_to);
-        db.q_lens = reinterpret_cast<uint32_t *>(dm + a_ql);
-        db.t_lens = reinterpret_cast<uint32_t *>(dm + a_tl);
-        db.q_ops = hb->q_ops ? dm + a_qop : nullptr;
-        db.t_ops = hb->t_ops ? dm + a_top : nullptr;
-        db.seed_scores = hb->seed_scores ? reinterpret_cast<uint32_t *>(dm + a_seed) : nullptr;
-        db.q_bytes = (uint32_t)(qhi - qlo);
-        db.t_bytes = (uint32_t)(thi - tlo);
-        db.n_alns = m;
-        db.max_q_len = mq;
-        db.max_t_len = mt;
-        gasalx_results dout;
-        std::memset(&dout, 0, sizeof(dout));
-        int32_t **dfield[8] = {&dout.aln_score, &dout.q_end, &dout.t_end, &dout.q_start,
-                               &dout.t_start, &dout.aln_score2, &dout.q_end2, &dout.t_end2};
-        for (int f = 0; f < 8; f++) *dfield[f] = hout[f] ? reinterpret_cast<int32_t *>(dm + a_out[f]) : nullptr;
-        if (hnops) dout.n_cigar_ops = reinterpret_cast<uint32_t *>(dm + a_nops);
-        if (tb && ho->cigar) {
-            CK(s.cig.reserve(qhi - qlo + 16));
-            dout.cigar = s.cig.as<uint8_t>();
-        }
-        gx::BatchShape shape;
-        shape.max_q = mq;
-        shape.max_t = mt;
-        shape.sort = gx::uneven_lengths(*params, hb->q_lens + i0, hb->t_lens + i0, m);
-        shape.one_t8 = gx::one_pad8(hb->t_lens + i0, m, shape.max_t);
-        shape.tb_split = false;   // the two slots' streams already overlap one chunk's walk with the next DP
-        if ((rc = gx::align_device(s.ws, *params, db, dout, s.st, shape))) {
-            for (HostSlot &x : eng->slot) (void)hipStreamSynchronize(x.st);
-            return rc;
-        }
-        pend[k] = {i0, i1, qlo, qhi, out_at, total - out_at, true};
-    }
-    for (int j = 0; j < 2; j++) {
-        k ^= 1;
-        if ((rc = drain(k))) return rc;
-    }
-    return GASALX_OK;
-}
-
-}  // namespace
 
 int gasalx_align_host(gasalx_engine *eng, const gasalx_params *params, const gasalx_batch *hb,
                       const gasalx_results *ho) {
@@ -350,297 +672,135 @@ int gasalx_align_host(gasalx_engine *eng, const gasalx_params *params, const gas
         gx::set_error("missing batch array");
         return GASALX_EINVAL;
     }
-    CK(hipSetDevice(eng->device));
-    hipStream_t st = eng->stream;
+    hipStream_t st;
+    int rc = enter(eng, nullptr, &st);
+    if (rc) return rc;
     const uint32_t n = hb->n_alns;
+    const bool tb = params->start_pos == 2;
+    const uint32_t mq = hb->max_q_len ? hb->max_q_len : host_max(hb->q_lens, n);
+    const uint32_t mt = hb->max_t_len ? hb->max_t_len : host_max(hb->t_lens, n);
     // large batches in the standard layout go through the two-stream pipeline
     // TB: the traceback walk is latency-bound per chunk whatever its size, so chunks
     // of ~5.5 G padded cells, 2 to 8 of them (1 M x 150 bp: 4, 34.0 ms pageable against
     // 50.5 with 2; 100 K x 300 bp: 2); score-only: 8
     uint32_t n_chunks = 8;
-    if (params->start_pos == 2) {
-        const double mq = hb->max_q_len ? hb->max_q_len : host_max(hb->q_lens, n);
-        const double mt = hb->max_t_len ? hb->max_t_len : host_max(hb->t_lens, n);
-        n_chunks = (uint32_t)std::min(8.0, std::max(2.0, std::round((double)n * mq * mt / 5.5e9)));
-    }
+    if (tb) n_chunks = (uint32_t)std::min(8.0, std::max(2.0, std::round((double)n * mq * mt / 5.5e9)));
     const uint32_t chunk = std::max<uint32_t>(16384, (uint32_t)(((uint64_t)n + n_chunks - 1) / n_chunks));
-    const bool tb = params->start_pos == 2;
     if (n >= 2 * chunk && !(params->is_packed && tb) && contiguous(hb->q_offsets, hb->q_lens, n, hb->q_bytes) &&
         contiguous(hb->t_offsets, hb->t_lens, n, hb->t_bytes))
-        return align_host_pipelined(eng, params, hb, ho, chunk);
+        return align_host_pipelined(eng, params, hb, ho, chunk, tb, mq, mt);
     gasalx_batch db = *hb;
-    int rc = 0;
-    uint8_t *p8; uint32_t *p32;
     // isPacked without traceback: only the packed half of the pages moves (with traceback the
     // device CIGAR buffer starts as the whole query batch, gasal_align.cu:281)
     const uint32_t pk = params->is_packed && !tb ? 2 : 1;
-    if ((rc = stage_in(eng->q, hb->q_batch, hb->q_bytes / pk, st, &p8))) return rc; db.q_batch = p8;
-    if ((rc = stage_in(eng->t, hb->t_batch, hb->t_bytes / pk, st, &p8))) return rc; db.t_batch = p8;
-    if ((rc = stage_in(eng->qo, hb->q_offsets, n, st, &p32))) return rc; db.q_offsets = p32;
-    if ((rc = stage_in(eng->to, hb->t_offsets, n, st, &p32))) return rc; db.t_offsets = p32;
-    if ((rc = stage_in(eng->ql, hb->q_lens, n, st, &p32))) return rc; db.q_lens = p32;
-    if ((rc = stage_in(eng->tl, hb->t_lens, n, st, &p32))) return rc; db.t_lens = p32;
-    if ((rc = stage_in(eng->qop, hb->q_ops, n, st, &p8))) return rc; db.q_ops = p8;
-    if ((rc = stage_in(eng->top, hb->t_ops, n, st, &p8))) return rc; db.t_ops = p8;
-    if ((rc = stage_in(eng->seed, hb->seed_scores, n, st, &p32))) return rc; db.seed_scores = p32;
-    if (!db.max_q_len) db.max_q_len = host_max(hb->q_lens, n);
-    if (!db.max_t_len) db.max_t_len = host_max(hb->t_lens, n);
-
+    Stager in{eng, st};
+    in(B_Q, db.q_batch, hb->q_bytes / pk);
+    in(B_T, db.t_batch, hb->t_bytes / pk);
+    in(B_QO, db.q_offsets, n);
+    in(B_TO, db.t_offsets, n);
+    in(B_QL, db.q_lens, n);
+    in(B_TL, db.t_lens, n);
+    in(B_QOP, db.q_ops, n);
+    in(B_TOP, db.t_ops, n);
+    in(B_SEED, db.seed_scores, n);
+    db.max_q_len = mq;
+    db.max_t_len = mt;
     // outputs: staged in with the caller's contents so fields the reference
     // would not write come back unchanged
     gasalx_results dout;
-    std::memset(&dout, 0, sizeof(dout));
-    int32_t *i32;
-    if ((rc = stage_in(eng->o_score, ho->aln_score, n, st, &i32))) return rc; dout.aln_score = i32;
-    if ((rc = stage_in(eng->o_qe, ho->q_end, n, st, &i32))) return rc; dout.q_end = i32;
-    if ((rc = stage_in(eng->o_te, ho->t_end, n, st, &i32))) return rc; dout.t_end = i32;
-    if ((rc = stage_in(eng->o_qs, ho->q_start, n, st, &i32))) return rc; dout.q_start = i32;
-    if ((rc = stage_in(eng->o_ts, ho->t_start, n, st, &i32))) return rc; dout.t_start = i32;
-    if ((rc = stage_in(eng->o_s2, ho->aln_score2, n, st, &i32))) return rc; dout.aln_score2 = i32;
-    if ((rc = stage_in(eng->o_qe2, ho->q_end2, n, st, &i32))) return rc; dout.q_end2 = i32;
-    if ((rc = stage_in(eng->o_te2, ho->t_end2, n, st, &i32))) return rc; dout.t_end2 = i32;
-    if ((rc = stage_in(eng->o_cig, ho->cigar, hb->q_bytes, st, &p8))) return rc; dout.cigar = p8;
-    if ((rc = stage_in(eng->o_nops, ho->n_cigar_ops, n, st, &p32))) return rc; dout.n_cigar_ops = p32;
-
+    for (int f = 0; f < kFields; f++) {
+        const uint8_t *p = static_cast<const uint8_t *>(get_field(*ho, f));
+        in(Buf(B_OUT + f), p, field_bytes(f, n, hb->q_bytes));
+        set_field(dout, f, const_cast<uint8_t *>(p));
+    }
+    if (in.rc) return in.rc;
     gx::BatchShape shape;
-    shape.max_q = db.max_q_len;
-    shape.max_t = db.max_t_len;
+    shape.max_q = mq;
+    shape.max_t = mt;
     shape.sort = gx::uneven_lengths(*params, hb->q_lens, hb->t_lens, n);
     shape.one_t8 = gx::one_pad8(hb->t_lens, n, shape.max_t);
-    rc = gx::align_device(eng->ws, *params, db, dout, st, shape);
-    if (rc) { (void)hipStreamSynchronize(st); return rc; }
-#define BACK(h, d, cnt)                                                                             \
-    if (h) CK(hipMemcpyAsync((void *)(h), (d), (size_t)(cnt) * sizeof(*(h)), hipMemcpyDeviceToHost, st));
-    BACK(ho->aln_score, dout.aln_score, n)
-    BACK(ho->q_end, dout.q_end, n)
-    BACK(ho->t_end, dout.t_end, n)
-    BACK(ho->q_start, dout.q_start, n)
-    BACK(ho->t_start, dout.t_start, n)
-    BACK(ho->aln_score2, dout.aln_score2, n)
-    BACK(ho->q_end2, dout.q_end2, n)
-    BACK(ho->t_end2, dout.t_end2, n)
-    BACK(ho->cigar, dout.cigar, hb->q_bytes)
-    BACK(ho->n_cigar_ops, dout.n_cigar_ops, n)
-#undef BACK
-    CK(hipStreamSynchronize(st));
-    return GASALX_OK;
+    if ((rc = gx::align_device(eng->ws, *params, db, dout, st, shape))) return host_finish(st, rc, {});
+    for (int f = 0; f < kFields; f++)
+        if (void *h = get_field(*ho, f))
+            CK(hipMemcpyAsync(h, get_field(dout, f), field_bytes(f, n, hb->q_bytes), hipMemcpyDeviceToHost, st));
+    return host_finish(st, GASALX_OK, {});
 }
 
 int gasalx_pairhmm_device(gasalx_engine *eng, const gasalx_hmm_batch *b, float *res, void *stream) {
     if (!eng || !b || !res) { gx::set_error("null argument"); return GASALX_EINVAL; }
-    CK(hipSetDevice(eng->device));
-    hipStream_t st = stream ? (hipStream_t)stream : eng->stream;
+    hipStream_t st;
+    int rc = enter(eng, stream, &st);
+    if (rc) return rc;
     uint32_t mr = b->max_read_len, mh = b->max_hap_len;
-    if ((!mr || !mh) && b->n_pairs) {
-        int rc = device_max_lens(eng, b->read_lens, b->hap_lens, b->n_pairs, st, &mr, &mh);
-        if (rc) return rc;
-    }
+    if ((rc = device_max_lens(b->read_lens, b->hap_lens, b->n_pairs, st, &mr, &mh))) return rc;
     return gx::pairhmm_device(eng->ws, *b, res, st, mr, mh);
 }
 
 int gasalx_pairhmm_host(gasalx_engine *eng, const gasalx_hmm_batch *hb, float *hres) {
     if (!eng || !hb || !hres) { gx::set_error("null argument"); return GASALX_EINVAL; }
-    CK(hipSetDevice(eng->device));
-    hipStream_t st = eng->stream;
-    const uint32_t n = hb->n_pairs;
-    gasalx_hmm_batch db;
-    int rc = hmm_stage_host(eng, hb, st, db);
+    hipStream_t st;
+    int rc = enter(eng, nullptr, &st);
     if (rc) return rc;
-    CK(eng->h_res.reserve((size_t)n * 4 + 16));
-    rc = gx::pairhmm_device(eng->ws, db, eng->h_res.as<float>(), st, db.max_read_len, db.max_hap_len);
-    if (rc) { (void)hipStreamSynchronize(st); return rc; }
-    CK(hipMemcpyAsync(hres, eng->h_res.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    CK(hipStreamSynchronize(st));
-    return GASALX_OK;
+    gasalx_hmm_batch db;
+    if ((rc = hmm_host_fp32(eng, hb, st, db))) return rc;
+    return host_finish(st, GASALX_OK, {{hres, eng->buf[B_RES].p, (size_t)hb->n_pairs * 4}});
 }
-
-}  // extern "C"
-
-namespace {
-
-// ph2pr[q] = powf(10, -q/10) on the host, as the reference builds it (tile_1.cu:216-220)
-void ph2pr_table(float *t) {
-    for (int i = 0; i < 128; i++) t[i] = powf(10.f, -((float)i) / 10.f);
-}
-
-// The engine's device copy of the table (uploaded once, synchronously).
-int ph2pr_device(gasalx_engine *eng, const float **out) {
-    if (!eng->ph2pr.p) {
-        float t[128];
-        ph2pr_table(t);
-        CK(eng->ph2pr.reserve(sizeof(t)));
-        CK(hipMemcpy(eng->ph2pr.p, t, sizeof(t), hipMemcpyHostToDevice));
-    }
-    *out = eng->ph2pr.as<float>();
-    return GASALX_OK;
-}
-
-bool hmm_qual_batch_ok(const gasalx_hmm_qual_batch *b) {
-    return b && (b->n_pairs == 0 || (b->reads && b->read_offsets && b->read_lens && b->base_quals && b->ins_quals &&
-                                     b->del_quals && b->haps && b->hap_offsets && b->hap_lens));
-}
-
-}  // namespace
-
-extern "C" {
 
 int gasalx_pairhmm_quals_device(gasalx_engine *eng, const gasalx_hmm_qual_batch *b, float *res, void *stream) {
     if (!eng || !hmm_qual_batch_ok(b) || !res) { gx::set_error("null argument"); return GASALX_EINVAL; }
-    CK(hipSetDevice(eng->device));
-    hipStream_t st = stream ? (hipStream_t)stream : eng->stream;
-    uint32_t mr = b->max_read_len, mh = b->max_hap_len;
-    if ((!mr || !mh) && b->n_pairs) {
-        int rc = device_max_lens(eng, b->read_lens, b->hap_lens, b->n_pairs, st, &mr, &mh);
-        if (rc) return rc;
-    }
-    const float *tab;
-    int rc = ph2pr_device(eng, &tab);
+    hipStream_t st;
+    int rc = enter(eng, stream, &st);
     if (rc) return rc;
+    uint32_t mr = b->max_read_len, mh = b->max_hap_len;
+    if ((rc = device_max_lens(b->read_lens, b->hap_lens, b->n_pairs, st, &mr, &mh))) return rc;
+    const float *tab;
+    if ((rc = ph2pr_device(eng, &tab))) return rc;
     return gx::pairhmm_quals_device(eng->ws, *b, res, st, tab, nullptr, nullptr, 0, mr, mh);
 }
-
-namespace {
-// The fp32 pass of a host batch in quality form: pairs staged into the engine's device buffers
-// (db = the device image, max lengths filled in), run sorted by (read length, haplotype length)
-// in classes of reads that share a lane-group size, results in eng->h_res by pair index.
-// perm: the slot order, the caller's so that it outlives its copy (until the stream is synchronised).
-int quals_host_fp32(gasalx_engine *eng, const gasalx_hmm_qual_batch *hb, hipStream_t st, gasalx_hmm_qual_batch &db,
-                    const float **tab_out, std::vector<uint32_t> &perm) {
-    const uint32_t n = hb->n_pairs;
-    // slots in (read length, haplotype length) order (tile_1.cu:180-195 operator<, :325)
-    perm.resize(n);
-    for (uint32_t i = 0; i < n; i++) perm[i] = i;
-    std::stable_sort(perm.begin(), perm.end(), [&](uint32_t x, uint32_t y) {
-        const uint32_t rx = hb->read_lens[x], ry = hb->read_lens[y];
-        return rx != ry ? rx < ry : hb->hap_lens[x] < hb->hap_lens[y];
-    });
-    // classes: runs of slots whose reads need the same lane-group size
-    std::vector<gx::HmmClass> classes;
-    uint32_t mr = 0, mh = 0;
-    for (uint32_t s = 0; s < n; s++) {
-        const uint32_t r = hb->read_lens[perm[s]], h = hb->hap_lens[perm[s]];
-        const int g = gx::pairhmm_group(r);
-        if (classes.empty() || gx::pairhmm_group(classes.back().max_r) != g) classes.push_back({s, s, 0, 0});
-        gx::HmmClass &c = classes.back();
-        c.slot1 = s + 1;
-        c.max_r = std::max(c.max_r, r);
-        c.max_h = std::max(c.max_h, h);
-        mr = std::max(mr, r);
-        mh = std::max(mh, h);
-    }
-    db = *hb;
-    db.max_read_len = mr;
-    db.max_hap_len = mh;
-    int rc;
-    uint8_t *p8; uint32_t *p32;
-    if ((rc = stage_in(eng->h_reads, hb->reads, hb->read_bytes, st, &p8))) return rc; db.reads = p8;
-    if ((rc = stage_in(eng->h_bq, hb->base_quals, hb->read_bytes, st, &p8))) return rc; db.base_quals = p8;
-    if ((rc = stage_in(eng->h_iq, hb->ins_quals, hb->read_bytes, st, &p8))) return rc; db.ins_quals = p8;
-    if ((rc = stage_in(eng->h_dq, hb->del_quals, hb->read_bytes, st, &p8))) return rc; db.del_quals = p8;
-    if ((rc = stage_in(eng->h_ro, hb->read_offsets, n, st, &p32))) return rc; db.read_offsets = p32;
-    if ((rc = stage_in(eng->h_rl, hb->read_lens, n, st, &p32))) return rc; db.read_lens = p32;
-    if ((rc = stage_in(eng->h_haps, hb->haps, hb->hap_bytes, st, &p8))) return rc; db.haps = p8;
-    if ((rc = stage_in(eng->h_ho, hb->hap_offsets, n, st, &p32))) return rc; db.hap_offsets = p32;
-    if ((rc = stage_in(eng->h_hl, hb->hap_lens, n, st, &p32))) return rc; db.hap_lens = p32;
-    uint32_t *dperm;
-    if ((rc = stage_in(eng->h_perm, perm.data(), n, st, &dperm))) return rc;
-    CK(eng->h_res.reserve((size_t)n * 4 + 16));
-    if ((rc = ph2pr_device(eng, tab_out))) return rc;
-    rc = gx::pairhmm_quals_device(eng->ws, db, eng->h_res.as<float>(), st, *tab_out, dperm, classes.data(),
-                                  (int)classes.size(), 0, 0);
-    if (rc) (void)hipStreamSynchronize(st);
-    return rc;
-}
-}  // namespace
 
 int gasalx_pairhmm_quals_host(gasalx_engine *eng, const gasalx_hmm_qual_batch *hb, float *hres) {
     if (!eng || !hmm_qual_batch_ok(hb) || !hres) { gx::set_error("null argument"); return GASALX_EINVAL; }
     const uint32_t n = hb->n_pairs;
     if (n == 0) return GASALX_OK;
-    CK(hipSetDevice(eng->device));
-    hipStream_t st = eng->stream;
+    hipStream_t st;
+    int rc = enter(eng, nullptr, &st);
+    if (rc) return rc;
     gasalx_hmm_qual_batch db;
     const float *tab;
     std::vector<uint32_t> perm;
-    int rc = quals_host_fp32(eng, hb, st, db, &tab, perm);
-    if (rc) return rc;
-    CK(hipMemcpyAsync(hres, eng->h_res.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    CK(hipStreamSynchronize(st));
-    return GASALX_OK;
+    if ((rc = quals_host_fp32(eng, hb, st, db, &tab, perm))) return rc;
+    return host_finish(st, GASALX_OK, {{hres, eng->buf[B_RES].p, (size_t)n * 4}});
 }
-
-// ---- PairHMM in float64 and the log10 entry points (pairhmm64.hip) ----
-namespace {
-
-// max lengths of a device batch: the caller's, or read back (synchronises st)
-int hmm_lens(gasalx_engine *eng, const uint32_t *rl, const uint32_t *hl, uint32_t n, hipStream_t st, uint32_t *mr,
-             uint32_t *mh) {
-    if ((!*mr || !*mh) && n) return device_max_lens(eng, rl, hl, n, st, mr, mh);
-    return GASALX_OK;
-}
-
-// The rescue pass after an fp32 pass whose results are at r32 (device): scratch from the engine.
-int log10_rescue(gasalx_engine *eng, const gx::Hmm64Src &src, uint32_t n, const float *r32, float min_accepted,
-                 double *out, uint8_t *used, hipStream_t st, uint32_t mr, uint32_t mh) {
-    CK(eng->hm_list.reserve(((size_t)n + 4) * 4));
-    uint32_t *count = eng->hm_list.as<uint32_t>();
-    return gx::pairhmm_log10_device(src, n, r32, min_accepted, out, used, count, count + 4, st, mr, mh);
-}
-
-// Host forms: device outputs in eng->h_res64 / h_used, copied back with the count.
-int log10_host_finish(gasalx_engine *eng, const gx::Hmm64Src &src, uint32_t n, float min_accepted, double *hlog,
-                      uint8_t *hused, uint32_t *n_rescued, hipStream_t st, uint32_t mr, uint32_t mh) {
-    CK(eng->h_res64.reserve((size_t)n * 8 + 16));
-    CK(eng->h_used.reserve((size_t)n + 16));
-    int rc = log10_rescue(eng, src, n, eng->h_res.as<float>(), min_accepted, eng->h_res64.as<double>(),
-                          hused ? eng->h_used.as<uint8_t>() : nullptr, st, mr, mh);
-    if (rc) { (void)hipStreamSynchronize(st); return rc; }
-    CK(hipMemcpyAsync(hlog, eng->h_res64.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    if (hused) CK(hipMemcpyAsync(hused, eng->h_used.p, (size_t)n, hipMemcpyDeviceToHost, st));
-    uint32_t cnt = 0;
-    CK(hipMemcpyAsync(&cnt, eng->hm_list.p, 4, hipMemcpyDeviceToHost, st));
-    CK(hipStreamSynchronize(st));
-    if (n_rescued) *n_rescued = cnt;
-    return GASALX_OK;
-}
-
-}  // namespace
 
 int gasalx_pairhmm64_device(gasalx_engine *eng, const gasalx_hmm_batch *b, double *res, void *stream) {
     if (!eng || !b || !res) { gx::set_error("null argument"); return GASALX_EINVAL; }
-    CK(hipSetDevice(eng->device));
-    hipStream_t st = stream ? (hipStream_t)stream : eng->stream;
-    uint32_t mr = b->max_read_len, mh = b->max_hap_len;
-    int rc = hmm_lens(eng, b->read_lens, b->hap_lens, b->n_pairs, st, &mr, &mh);
+    hipStream_t st;
+    int rc = enter(eng, stream, &st);
     if (rc) return rc;
+    uint32_t mr = b->max_read_len, mh = b->max_hap_len;
+    if ((rc = device_max_lens(b->read_lens, b->hap_lens, b->n_pairs, st, &mr, &mh))) return rc;
     return gx::pairhmm64_device(gx::Hmm64Src{b, nullptr, nullptr}, b->n_pairs, res, st, mr, mh);
 }
 
 int gasalx_pairhmm64_host(gasalx_engine *eng, const gasalx_hmm_batch *hb, double *hres) {
     if (!eng || !hb || !hres) { gx::set_error("null argument"); return GASALX_EINVAL; }
-    CK(hipSetDevice(eng->device));
-    hipStream_t st = eng->stream;
+    hipStream_t st;
+    int rc = enter(eng, nullptr, &st);
+    if (rc) return rc;
     const uint32_t n = hb->n_pairs;
     if (n == 0) return GASALX_OK;
     gasalx_hmm_batch db;
-    int rc = hmm_stage_host(eng, hb, st, db);
-    if (rc) return rc;
-    CK(eng->h_res64.reserve((size_t)n * 8 + 16));
-    rc = gx::pairhmm64_device(gx::Hmm64Src{&db, nullptr, nullptr}, n, eng->h_res64.as<double>(), st, db.max_read_len,
-                              db.max_hap_len);
-    if (rc) { (void)hipStreamSynchronize(st); return rc; }
-    CK(hipMemcpyAsync(hres, eng->h_res64.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    CK(hipStreamSynchronize(st));
-    return GASALX_OK;
+    if ((rc = hmm_stage_host(eng, hb, st, db))) return rc;
+    return hmm64_host_run(eng, gx::Hmm64Src{&db, nullptr, nullptr}, n, hres, st, db.max_read_len, db.max_hap_len);
 }
 
 int gasalx_pairhmm64_quals_device(gasalx_engine *eng, const gasalx_hmm_qual_batch *b, double *res, void *stream) {
     if (!eng || !hmm_qual_batch_ok(b) || !res) { gx::set_error("null argument"); return GASALX_EINVAL; }
-    CK(hipSetDevice(eng->device));
-    hipStream_t st = stream ? (hipStream_t)stream : eng->stream;
-    uint32_t mr = b->max_read_len, mh = b->max_hap_len;
-    int rc = hmm_lens(eng, b->read_lens, b->hap_lens, b->n_pairs, st, &mr, &mh);
+    hipStream_t st;
+    int rc = enter(eng, stream, &st);
     if (rc) return rc;
+    uint32_t mr = b->max_read_len, mh = b->max_hap_len;
+    if ((rc = device_max_lens(b->read_lens, b->hap_lens, b->n_pairs, st, &mr, &mh))) return rc;
     const float *tab;
     if ((rc = ph2pr_device(eng, &tab))) return rc;
     return gx::pairhmm64_device(gx::Hmm64Src{nullptr, b, tab}, b->n_pairs, res, st, mr, mh);
@@ -650,30 +810,16 @@ int gasalx_pairhmm64_quals_host(gasalx_engine *eng, const gasalx_hmm_qual_batch 
     if (!eng || !hmm_qual_batch_ok(hb) || !hres) { gx::set_error("null argument"); return GASALX_EINVAL; }
     const uint32_t n = hb->n_pairs;
     if (n == 0) return GASALX_OK;
-    CK(hipSetDevice(eng->device));
-    hipStream_t st = eng->stream;
-    gasalx_hmm_qual_batch db = *hb;
-    int rc;
-    uint8_t *p8; uint32_t *p32;
-    if ((rc = stage_in(eng->h_reads, hb->reads, hb->read_bytes, st, &p8))) return rc; db.reads = p8;
-    if ((rc = stage_in(eng->h_bq, hb->base_quals, hb->read_bytes, st, &p8))) return rc; db.base_quals = p8;
-    if ((rc = stage_in(eng->h_iq, hb->ins_quals, hb->read_bytes, st, &p8))) return rc; db.ins_quals = p8;
-    if ((rc = stage_in(eng->h_dq, hb->del_quals, hb->read_bytes, st, &p8))) return rc; db.del_quals = p8;
-    if ((rc = stage_in(eng->h_ro, hb->read_offsets, n, st, &p32))) return rc; db.read_offsets = p32;
-    if ((rc = stage_in(eng->h_rl, hb->read_lens, n, st, &p32))) return rc; db.read_lens = p32;
-    if ((rc = stage_in(eng->h_haps, hb->haps, hb->hap_bytes, st, &p8))) return rc; db.haps = p8;
-    if ((rc = stage_in(eng->h_ho, hb->hap_offsets, n, st, &p32))) return rc; db.hap_offsets = p32;
-    if ((rc = stage_in(eng->h_hl, hb->hap_lens, n, st, &p32))) return rc; db.hap_lens = p32;
+    hipStream_t st;
+    int rc = enter(eng, nullptr, &st);
+    if (rc) return rc;
+    gasalx_hmm_qual_batch db;
+    if ((rc = hmm_stage_quals(eng, hb, st, db))) return rc;
     const float *tab;
     if ((rc = ph2pr_device(eng, &tab))) return rc;
-    CK(eng->h_res64.reserve((size_t)n * 8 + 16));
     // one launch sized by the longest read, as the parameter form's
-    rc = gx::pairhmm64_device(gx::Hmm64Src{nullptr, &db, tab}, n, eng->h_res64.as<double>(), st,
-                              host_max(hb->read_lens, n), host_max(hb->hap_lens, n));
-    if (rc) { (void)hipStreamSynchronize(st); return rc; }
-    CK(hipMemcpyAsync(hres, eng->h_res64.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    CK(hipStreamSynchronize(st));
-    return GASALX_OK;
+    return hmm64_host_run(eng, gx::Hmm64Src{nullptr, &db, tab}, n, hres, st, host_max(hb->read_lens, n),
+                          host_max(hb->hap_lens, n));
 }
 
 int gasalx_pairhmm_log10_device(gasalx_engine *eng, const gasalx_hmm_batch *b, float min_accepted, double *dlog,
@@ -681,15 +827,15 @@ int gasalx_pairhmm_log10_device(gasalx_engine *eng, const gasalx_hmm_batch *b, f
     if (!eng || !b || !dlog) { gx::set_error("null argument"); return GASALX_EINVAL; }
     const uint32_t n = b->n_pairs;
     if (n == 0) return GASALX_OK;
-    CK(hipSetDevice(eng->device));
-    hipStream_t st = stream ? (hipStream_t)stream : eng->stream;
-    uint32_t mr = b->max_read_len, mh = b->max_hap_len;
-    int rc = hmm_lens(eng, b->read_lens, b->hap_lens, n, st, &mr, &mh);
+    hipStream_t st;
+    int rc = enter(eng, stream, &st);
     if (rc) return rc;
-    CK(eng->hm_r32.reserve((size_t)n * 4 + 16));
-    if ((rc = gx::pairhmm_device(eng->ws, *b, eng->hm_r32.as<float>(), st, mr, mh))) return rc;
-    return log10_rescue(eng, gx::Hmm64Src{b, nullptr, nullptr}, n, eng->hm_r32.as<float>(), min_accepted, dlog, dused,
-                        st, mr, mh);
+    uint32_t mr = b->max_read_len, mh = b->max_hap_len;
+    if ((rc = device_max_lens(b->read_lens, b->hap_lens, n, st, &mr, &mh))) return rc;
+    gx::DevBuf &r32 = eng->buf[B_HM_R32];
+    CK(r32.reserve((size_t)n * 4 + 16));
+    if ((rc = gx::pairhmm_device(eng->ws, *b, r32.as<float>(), st, mr, mh))) return rc;
+    return log10_rescue(eng, gx::Hmm64Src{b, nullptr, nullptr}, n, r32.as<float>(), min_accepted, dlog, dused, st, mr, mh);
 }
 
 int gasalx_pairhmm_log10_host(gasalx_engine *eng, const gasalx_hmm_batch *hb, float min_accepted, double *hlog,
@@ -698,14 +844,11 @@ int gasalx_pairhmm_log10_host(gasalx_engine *eng, const gasalx_hmm_batch *hb, fl
     if (n_rescued) *n_rescued = 0;
     const uint32_t n = hb->n_pairs;
     if (n == 0) return GASALX_OK;
-    CK(hipSetDevice(eng->device));
-    hipStream_t st = eng->stream;
-    gasalx_hmm_batch db;
-    int rc = hmm_stage_host(eng, hb, st, db);
+    hipStream_t st;
+    int rc = enter(eng, nullptr, &st);
     if (rc) return rc;
-    CK(eng->h_res.reserve((size_t)n * 4 + 16));
-    rc = gx::pairhmm_device(eng->ws, db, eng->h_res.as<float>(), st, db.max_read_len, db.max_hap_len);
-    if (rc) { (void)hipStreamSynchronize(st); return rc; }
+    gasalx_hmm_batch db;
+    if ((rc = hmm_host_fp32(eng, hb, st, db))) return rc;
     return log10_host_finish(eng, gx::Hmm64Src{&db, nullptr, nullptr}, n, min_accepted, hlog, hused, n_rescued, st,
                              db.max_read_len, db.max_hap_len);
 }
@@ -715,18 +858,17 @@ int gasalx_pairhmm_quals_log10_device(gasalx_engine *eng, const gasalx_hmm_qual_
     if (!eng || !hmm_qual_batch_ok(b) || !dlog) { gx::set_error("null argument"); return GASALX_EINVAL; }
     const uint32_t n = b->n_pairs;
     if (n == 0) return GASALX_OK;
-    CK(hipSetDevice(eng->device));
-    hipStream_t st = stream ? (hipStream_t)stream : eng->stream;
-    uint32_t mr = b->max_read_len, mh = b->max_hap_len;
-    int rc = hmm_lens(eng, b->read_lens, b->hap_lens, n, st, &mr, &mh);
+    hipStream_t st;
+    int rc = enter(eng, stream, &st);
     if (rc) return rc;
+    uint32_t mr = b->max_read_len, mh = b->max_hap_len;
+    if ((rc = device_max_lens(b->read_lens, b->hap_lens, n, st, &mr, &mh))) return rc;
     const float *tab;
     if ((rc = ph2pr_device(eng, &tab))) return rc;
-    CK(eng->hm_r32.reserve((size_t)n * 4 + 16));
-    if ((rc = gx::pairhmm_quals_device(eng->ws, *b, eng->hm_r32.as<float>(), st, tab, nullptr, nullptr, 0, mr, mh)))
-        return rc;
-    return log10_rescue(eng, gx::Hmm64Src{nullptr, b, tab}, n, eng->hm_r32.as<float>(), min_accepted, dlog, dused, st,
-                        mr, mh);
+    gx::DevBuf &r32 = eng->buf[B_HM_R32];
+    CK(r32.reserve((size_t)n * 4 + 16));
+    if ((rc = gx::pairhmm_quals_device(eng->ws, *b, r32.as<float>(), st, tab, nullptr, nullptr, 0, mr, mh))) return rc;
+    return log10_rescue(eng, gx::Hmm64Src{nullptr, b, tab}, n, r32.as<float>(), min_accepted, dlog, dused, st, mr, mh);
 }
 
 int gasalx_pairhmm_quals_log10_host(gasalx_engine *eng, const gasalx_hmm_qual_batch *hb, float min_accepted,
@@ -735,41 +877,26 @@ int gasalx_pairhmm_quals_log10_host(gasalx_engine *eng, const gasalx_hmm_qual_ba
     if (n_rescued) *n_rescued = 0;
     const uint32_t n = hb->n_pairs;
     if (n == 0) return GASALX_OK;
-    CK(hipSetDevice(eng->device));
-    hipStream_t st = eng->stream;
+    hipStream_t st;
+    int rc = enter(eng, nullptr, &st);
+    if (rc) return rc;
     gasalx_hmm_qual_batch db;
     const float *tab;
     std::vector<uint32_t> perm;
-    int rc = quals_host_fp32(eng, hb, st, db, &tab, perm);
-    if (rc) return rc;
+    if ((rc = quals_host_fp32(eng, hb, st, db, &tab, perm))) return rc;
     // the rescue pass: one launch over the list, sized by the batch's longest read
     return log10_host_finish(eng, gx::Hmm64Src{nullptr, &db, tab}, n, min_accepted, hlog, hused, n_rescued, st,
                              db.max_read_len, db.max_hap_len);
 }
 
-namespace {
-// max over i of off[i+1] - off[i]
-uint32_t max_span(const uint32_t *off, uint32_t n) {
-    uint32_t m = 0;
-    for (uint32_t i = 0; i < n; i++) m = std::max(m, off[i + 1] - off[i]);
-    return m;
-}
-}  // namespace
-
 int gasalx_nv_score_device(gasalx_engine *eng, const gasalx_nv_aligner *al, uint32_t n, const gasalx_nv_strings *pat,
                            const gasalx_nv_strings *txt, int32_t *scores, int16_t *scores16, uint32_t max_p,
                            uint32_t max_t, void *stream) {
     if (!eng || !al || !pat || !txt) { gx::set_error("null argument"); return GASALX_EINVAL; }
-    CK(hipSetDevice(eng->device));
-    hipStream_t st = stream ? (hipStream_t)stream : eng->stream;
-    if (n && (!max_p || (txt->offsets && !max_t))) {   // read the offsets back (synchronises the stream)
-        std::vector<uint32_t> po(n + 1), to(txt->offsets ? n + 1 : 0);
-        CK(hipMemcpyAsync(po.data(), pat->offsets, (n + 1) * 4ull, hipMemcpyDeviceToHost, st));
-        if (txt->offsets) CK(hipMemcpyAsync(to.data(), txt->offsets, (n + 1) * 4ull, hipMemcpyDeviceToHost, st));
-        CK(hipStreamSynchronize(st));
-        if (!max_p) max_p = max_span(po.data(), n);
-        if (txt->offsets && !max_t) max_t = max_span(to.data(), n);
-    }
+    hipStream_t st;
+    int rc = enter(eng, stream, &st);
+    if (rc) return rc;
+    if ((rc = device_max_spans(pat, txt, n, st, &max_p, &max_t))) return rc;
     return gx::nv_score_device(*al, n, *pat, *txt, scores, scores16, max_p, max_t, st);
 }
 
@@ -788,42 +915,29 @@ int gasalx_nv_score_host(gasalx_engine *eng, const gasalx_nv_aligner *al, uint32
         return GASALX_EINVAL;
     }
     if (n == 0) return GASALX_OK;
-    CK(hipSetDevice(eng->device));
-    hipStream_t st = eng->stream;
+    hipStream_t st;
+    int rc = enter(eng, nullptr, &st);
+    if (rc) return rc;
     const uint32_t max_p = max_span(pat->offsets, n);
     const uint32_t max_t = txt->offsets ? max_span(txt->offsets, n) : txt->length;
-    gasalx_nv_strings dp = *pat, dt = *txt;
-    int rc;
-    uint32_t *p32;
-    if ((rc = stage_in(eng->nv_pw, pat->words, pat_words, st, &p32))) return rc; dp.words = p32;
-    if ((rc = stage_in(eng->nv_po, pat->offsets, (size_t)n + 1, st, &p32))) return rc; dp.offsets = p32;
-    if ((rc = stage_in(eng->nv_tw, txt->words, txt_words, st, &p32))) return rc; dt.words = p32;
-    if ((rc = stage_in(eng->nv_to, txt->offsets, txt->offsets ? (size_t)n + 1 : 0, st, &p32))) return rc;
-    dt.offsets = txt->offsets ? p32 : nullptr;
+    gasalx_nv_strings dp, dt;
+    if ((rc = nv_stage_strings(eng, n, pat, pat_words, txt, txt_words, st, dp, dt))) return rc;
     int32_t *ds = nullptr;
     int16_t *ds16 = nullptr;
-    if (scores) { CK(eng->nv_s.reserve((size_t)n * 4)); ds = eng->nv_s.as<int32_t>(); }
-    if (scores16) { CK(eng->nv_s16.reserve((size_t)n * 2)); ds16 = eng->nv_s16.as<int16_t>(); }
+    if (scores) { CK(eng->buf[B_NV_S].reserve((size_t)n * 4)); ds = eng->buf[B_NV_S].as<int32_t>(); }
+    if (scores16) { CK(eng->buf[B_NV_S16].reserve((size_t)n * 2)); ds16 = eng->buf[B_NV_S16].as<int16_t>(); }
     rc = gx::nv_score_device(*al, n, dp, dt, ds, ds16, max_p, max_t, st);
-    if (rc) { (void)hipStreamSynchronize(st); return rc; }
-    if (scores) CK(hipMemcpyAsync(scores, ds, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    if (scores16) CK(hipMemcpyAsync(scores16, ds16, (size_t)n * 2, hipMemcpyDeviceToHost, st));
-    CK(hipStreamSynchronize(st));
-    return GASALX_OK;
+    return host_finish(st, rc, {{scores, ds, (size_t)n * 4}, {scores16, ds16, (size_t)n * 2}});
 }
 
 int gasalx_nv_banded_score_device(gasalx_engine *eng, const gasalx_nv_aligner *al, uint32_t band, uint32_t n,
                                   const gasalx_nv_strings *pat, const gasalx_nv_strings *txt, int32_t *scores,
                                   uint32_t max_p, void *stream) {
     if (!eng || !al || !pat || !txt) { gx::set_error("null argument"); return GASALX_EINVAL; }
-    CK(hipSetDevice(eng->device));
-    hipStream_t st = stream ? (hipStream_t)stream : eng->stream;
-    if (n && !max_p && pat->offsets) {   // read the offsets back (synchronises the stream)
-        std::vector<uint32_t> po(n + 1);
-        CK(hipMemcpyAsync(po.data(), pat->offsets, (n + 1) * 4ull, hipMemcpyDeviceToHost, st));
-        CK(hipStreamSynchronize(st));
-        max_p = max_span(po.data(), n);
-    }
+    hipStream_t st;
+    int rc = enter(eng, stream, &st);
+    if (rc) return rc;
+    if (pat->offsets && (rc = device_max_spans(pat, nullptr, n, st, &max_p, nullptr))) return rc;
     return gx::nv_banded_score_device(*al, band, n, *pat, *txt, scores, st, max_p);
 }
 
@@ -836,67 +950,24 @@ int gasalx_nv_banded_score_host(gasalx_engine *eng, const gasalx_nv_aligner *al,
     }
     if (band < 2 || band > 32) { gx::set_error("band length must be 2..32"); return GASALX_EINVAL; }
     if (n == 0) return GASALX_OK;
-    CK(hipSetDevice(eng->device));
-    hipStream_t st = eng->stream;
-    gasalx_nv_strings dp = *pat, dt = *txt;
-    int rc;
-    uint32_t *p32;
-    if ((rc = stage_in(eng->nv_pw, pat->words, pat_words, st, &p32))) return rc; dp.words = p32;
-    if ((rc = stage_in(eng->nv_po, pat->offsets, (size_t)n + 1, st, &p32))) return rc; dp.offsets = p32;
-    if ((rc = stage_in(eng->nv_tw, txt->words, txt_words, st, &p32))) return rc; dt.words = p32;
-    if ((rc = stage_in(eng->nv_to, txt->offsets, txt->offsets ? (size_t)n + 1 : 0, st, &p32))) return rc;
-    dt.offsets = txt->offsets ? p32 : nullptr;
-    CK(eng->nv_s.reserve((size_t)n * 4));
-    rc = gx::nv_banded_score_device(*al, band, n, dp, dt, eng->nv_s.as<int32_t>(), st, max_span(pat->offsets, n));
-    if (rc) { (void)hipStreamSynchronize(st); return rc; }
-    CK(hipMemcpyAsync(scores, eng->nv_s.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    CK(hipStreamSynchronize(st));
-    return GASALX_OK;
+    hipStream_t st;
+    int rc = enter(eng, nullptr, &st);
+    if (rc) return rc;
+    gasalx_nv_strings dp, dt;
+    if ((rc = nv_stage_strings(eng, n, pat, pat_words, txt, txt_words, st, dp, dt))) return rc;
+    gx::DevBuf &ds = eng->buf[B_NV_S];
+    CK(ds.reserve((size_t)n * 4));
+    rc = gx::nv_banded_score_device(*al, band, n, dp, dt, ds.as<int32_t>(), st, max_span(pat->offsets, n));
+    return host_finish(st, rc, {{scores, ds.p, (size_t)n * 4}});
 }
 
-// nvbio BatchedAlignmentTraceback (nvtrace.hpp).  nvbio keeps its DP columns and checkpoints in
-// int16 (alignment/utils.h:49-64): the scores of every cell must stay within them.
-static int64_t nv_score_mag(const gasalx_nv_aligner *al) {
-    if (al->aligner == GASALX_NV_ED) return 1;   // ED: EditDistanceSWScheme's 0 / -1 (ed_utils.h:45-52)
-    return std::max<int64_t>({std::abs((int64_t)al->match), std::abs((int64_t)al->mismatch),
-                              std::abs((int64_t)al->gap_open), std::abs((int64_t)al->gap_ext),
-                              std::abs((int64_t)al->deletion), std::abs((int64_t)al->insertion), 1});
-}
-
-// nvbio traceback workspace per call (the engine's: flags of every cell, one DP row per pair) and
-// the chunk budget the device entry points split a batch by
-static constexpr uint64_t kNvTbBudget = 4ull << 30;
-// GASALX_NV_TB_BUDGET (bytes) replaces it for tests that force several chunks; read on every
-// call, and unset, empty, zero or unparsable leave the 4 GiB
-static uint64_t nv_tb_budget() {
-    const char *e = std::getenv("GASALX_NV_TB_BUDGET");
-    if (!e || !*e) return kNvTbBudget;
-    for (const char *c = e; *c; c++)
-        if (*c < '0' || *c > '9') return kNvTbBudget;
-    errno = 0;
-    const unsigned long long v = std::strtoull(e, nullptr, 10);
-    return (errno || !v) ? kNvTbBudget : (uint64_t)v;
-}
 uint64_t gasalx_nv_traceback_workspace(uint32_t max_p, uint32_t max_t, uint32_t n) {
     const uint64_t per = (uint64_t)((max_p + 7) / 8) * 8 * max_t + (uint64_t)max_t * 8;
-    const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(n, nv_tb_budget() / std::max<uint64_t>(per, 1)));
-    return per * chunk + 128;
+    return per * nv_tb_chunk(n, per) + 128;
 }
 uint64_t gasalx_nv_banded_traceback_workspace(uint32_t max_p, uint32_t band, uint32_t n) {
     const uint64_t per = (uint64_t)max_p * ((band + 3) / 4) * 4;
-    const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(n, nv_tb_budget() / std::max<uint64_t>(per, 1)));
-    return per * chunk + 64;
-}
-
-static int nv_tb_checks(const gasalx_nv_aligner *al, uint32_t max_p, uint32_t max_t, uint32_t ops_stride) {
-    const int64_t mag = nv_score_mag(al);
-    if (((int64_t)max_p + max_t + 2) * mag > 32767) {
-        gx::set_error("traceback: scores would leave nvbio's int16 columns (lengths x |score|)");
-        return GASALX_ERANGE;
-    }
-    if (ops_stride < max_p + max_t) { gx::set_error("traceback: ops_stride < max pattern + max text length"); return GASALX_EINVAL; }
-    if ((uint64_t)max_p * max_t > (1ull << 24)) { gx::set_error("traceback: pattern x text above 16 M cells"); return GASALX_ERANGE; }
-    return GASALX_OK;
+    return per * nv_tb_chunk(n, per) + 64;
 }
 
 int gasalx_nv_traceback_device(gasalx_engine *eng, const gasalx_nv_aligner *al, uint32_t n,
@@ -905,36 +976,18 @@ int gasalx_nv_traceback_device(gasalx_engine *eng, const gasalx_nv_aligner *al, 
                                uint32_t ops_stride, uint32_t *n_ops, void *stream) {
     if (!eng || !al || !pat || !txt) { gx::set_error("null argument"); return GASALX_EINVAL; }
     if (n == 0) return GASALX_OK;
-    CK(hipSetDevice(eng->device));
-    hipStream_t st = stream ? (hipStream_t)stream : eng->stream;
-    if (!max_p || (txt->offsets && !max_t)) {   // read the offsets back (synchronises the stream)
-        std::vector<uint32_t> po(n + 1), to(txt->offsets ? n + 1 : 0);
-        CK(hipMemcpyAsync(po.data(), pat->offsets, (n + 1) * 4ull, hipMemcpyDeviceToHost, st));
-        if (txt->offsets) CK(hipMemcpyAsync(to.data(), txt->offsets, (n + 1) * 4ull, hipMemcpyDeviceToHost, st));
-        CK(hipStreamSynchronize(st));
-        if (!max_p) max_p = max_span(po.data(), n);
-        if (txt->offsets && !max_t) max_t = max_span(to.data(), n);
-    }
-    if (!txt->offsets) max_t = txt->length;
-    int rc = nv_tb_checks(al, max_p, max_t, ops_stride);
+    hipStream_t st;
+    int rc = enter(eng, stream, &st);
     if (rc) return rc;
+    if ((rc = device_max_spans(pat, txt, n, st, &max_p, &max_t))) return rc;
+    if (!txt->offsets) max_t = txt->length;
+    if ((rc = nv_tb_checks(al, max_p, max_t, ops_stride))) return rc;
     // the batch runs in chunks whose workspace (flags of every cell + one row per pair) stays
     // within nv_tb_budget() (1 M 150 x 182 pairs would otherwise take 28 GB of HBM)
-    const uint64_t per = gasalx_nv_traceback_workspace(max_p, max_t, 1);
-    const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n, nv_tb_budget() / per));
-    CK(eng->nv_dir.reserve((size_t)((max_p + 7) / 8) * 8 * max_t * chunk + 64));
-    CK(eng->nv_row.reserve((size_t)max_t * chunk * 8 + 64));
-    for (uint32_t s = 0; s < n; s += chunk) {
-        const uint32_t m = std::min(chunk, n - s);
-        gasalx_nv_strings p = *pat, t = *txt;
-        p.offsets = pat->offsets + s;
-        if (txt->offsets) t.offsets = txt->offsets + s;
-        rc = gx::nv_traceback_device(*al, m, p, t, max_p, max_t, eng->nv_dir.as<uint8_t>(), eng->nv_row.as<int32_t>(),
-                                     scores + s, sources + 2ull * s, sinks + 2ull * s, ops + (size_t)s * ops_stride,
-                                     ops_stride, n_ops + s, st);
-        if (rc) return rc;
-    }
-    return GASALX_OK;
+    const uint32_t chunk = (uint32_t)nv_tb_chunk(n, gasalx_nv_traceback_workspace(max_p, max_t, 1));
+    CK(eng->buf[B_NV_DIR].reserve((size_t)((max_p + 7) / 8) * 8 * max_t * chunk + 64));
+    CK(eng->buf[B_NV_ROW].reserve((size_t)max_t * chunk * 8 + 64));
+    return nv_tb_chunks(eng, al, 0, n, pat, txt, max_p, max_t, {scores, sources, sinks, ops, ops_stride, n_ops}, chunk, st);
 }
 
 int gasalx_nv_traceback_host(gasalx_engine *eng, const gasalx_nv_aligner *al, uint32_t n, const gasalx_nv_strings *pat,
@@ -946,50 +999,15 @@ int gasalx_nv_traceback_host(gasalx_engine *eng, const gasalx_nv_aligner *al, ui
         return GASALX_EINVAL;
     }
     if (n == 0) return GASALX_OK;
-    CK(hipSetDevice(eng->device));
-    hipStream_t st = eng->stream;
+    hipStream_t st;
+    int rc = enter(eng, nullptr, &st);
+    if (rc) return rc;
     const uint32_t max_p = max_span(pat->offsets, n);
     const uint32_t max_t = txt->offsets ? max_span(txt->offsets, n) : txt->length;
-    int rc = nv_tb_checks(al, max_p, max_t, ops_stride);
-    if (rc) return rc;
-    gasalx_nv_strings dp = *pat, dt = *txt;
-    uint32_t *p32;
-    if ((rc = stage_in(eng->nv_pw, pat->words, pat_words, st, &p32))) return rc; dp.words = p32;
-    if ((rc = stage_in(eng->nv_po, pat->offsets, (size_t)n + 1, st, &p32))) return rc; dp.offsets = p32;
-    if ((rc = stage_in(eng->nv_tw, txt->words, txt_words, st, &p32))) return rc; dt.words = p32;
-    if ((rc = stage_in(eng->nv_to, txt->offsets, txt->offsets ? (size_t)n + 1 : 0, st, &p32))) return rc;
-    dt.offsets = txt->offsets ? p32 : nullptr;
-    CK(eng->nv_s.reserve((size_t)n * 4));
-    CK(eng->nv_src.reserve((size_t)n * 8));
-    CK(eng->nv_snk.reserve((size_t)n * 8));
-    CK(eng->nv_ops.reserve((size_t)n * ops_stride + 64));
-    CK(eng->nv_nops.reserve((size_t)n * 4));
-    rc = gasalx_nv_traceback_device(eng, al, n, &dp, &dt, max_p, max_t, eng->nv_s.as<int32_t>(),
-                                    eng->nv_src.as<uint32_t>(), eng->nv_snk.as<uint32_t>(), eng->nv_ops.as<uint8_t>(),
-                                    ops_stride, eng->nv_nops.as<uint32_t>(), st);
-    if (rc) { (void)hipStreamSynchronize(st); return rc; }
-    CK(hipMemcpyAsync(scores, eng->nv_s.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    CK(hipMemcpyAsync(sources, eng->nv_src.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    CK(hipMemcpyAsync(sinks, eng->nv_snk.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    CK(hipMemcpyAsync(ops, eng->nv_ops.p, (size_t)n * ops_stride, hipMemcpyDeviceToHost, st));
-    CK(hipMemcpyAsync(n_ops, eng->nv_nops.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    CK(hipStreamSynchronize(st));
-    return GASALX_OK;
-}
-
-// nvbio BatchedBandedAlignmentTraceback<band> (nvtrace.hpp).  nvbio's checkpoints are int16
-// pairs clamped at -32736 (gotoh_banded_inl.h:234-239): every score must stay above it.
-static int nv_btb_checks(const gasalx_nv_aligner *al, uint32_t band, uint32_t max_p, uint32_t ops_stride) {
-    if (band < 2 || band > 32) { gx::set_error("band length must be 2..32"); return GASALX_EINVAL; }
-    if (((int64_t)max_p + band + 3) * nv_score_mag(al) > 32736) {
-        gx::set_error("banded traceback: scores would leave nvbio's int16 checkpoints (lengths x |score|)");
-        return GASALX_ERANGE;
-    }
-    if ((uint64_t)ops_stride < 2ull * max_p + band) {
-        gx::set_error("banded traceback: ops_stride < 2 x max pattern length + band");
-        return GASALX_EINVAL;
-    }
-    return GASALX_OK;
+    if ((rc = nv_tb_checks(al, max_p, max_t, ops_stride))) return rc;
+    gasalx_nv_strings dp, dt;
+    if ((rc = nv_stage_strings(eng, n, pat, pat_words, txt, txt_words, st, dp, dt))) return rc;
+    return nv_tb_host_run(eng, al, 0, n, &dp, &dt, max_p, max_t, {scores, sources, sinks, ops, ops_stride, n_ops}, st);
 }
 
 int gasalx_nv_banded_traceback_device(gasalx_engine *eng, const gasalx_nv_aligner *al, uint32_t band, uint32_t n,
@@ -998,30 +1016,14 @@ int gasalx_nv_banded_traceback_device(gasalx_engine *eng, const gasalx_nv_aligne
                                       uint32_t ops_stride, uint32_t *n_ops, void *stream) {
     if (!eng || !al || !pat || !txt) { gx::set_error("null argument"); return GASALX_EINVAL; }
     if (n == 0) return GASALX_OK;
-    CK(hipSetDevice(eng->device));
-    hipStream_t st = stream ? (hipStream_t)stream : eng->stream;
-    if (!max_p) {   // read the offsets back (synchronises the stream)
-        std::vector<uint32_t> po(n + 1);
-        CK(hipMemcpyAsync(po.data(), pat->offsets, (n + 1) * 4ull, hipMemcpyDeviceToHost, st));
-        CK(hipStreamSynchronize(st));
-        max_p = max_span(po.data(), n);
-    }
-    int rc = nv_btb_checks(al, band, max_p, ops_stride);
+    hipStream_t st;
+    int rc = enter(eng, stream, &st);
     if (rc) return rc;
-    const uint64_t per = gasalx_nv_banded_traceback_workspace(max_p, band, 1);
-    const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n, nv_tb_budget() / per));
-    CK(eng->nv_dir.reserve((size_t)max_p * ((band + 3) / 4) * 4 * chunk + 64));
-    for (uint32_t s = 0; s < n; s += chunk) {
-        const uint32_t m = std::min(chunk, n - s);
-        gasalx_nv_strings p = *pat, t = *txt;
-        p.offsets = pat->offsets + s;
-        if (txt->offsets) t.offsets = txt->offsets + s;
-        rc = gx::nv_banded_traceback_device(*al, band, m, p, t, max_p, eng->nv_dir.as<uint32_t>(), scores + s,
-                                            sources + 2ull * s, sinks + 2ull * s, ops + (size_t)s * ops_stride,
-                                            ops_stride, n_ops + s, st);
-        if (rc) return rc;
-    }
-    return GASALX_OK;
+    if ((rc = device_max_spans(pat, nullptr, n, st, &max_p, nullptr))) return rc;
+    if ((rc = nv_btb_checks(al, band, max_p, ops_stride))) return rc;
+    const uint32_t chunk = (uint32_t)nv_tb_chunk(n, gasalx_nv_banded_traceback_workspace(max_p, band, 1));
+    CK(eng->buf[B_NV_DIR].reserve((size_t)max_p * ((band + 3) / 4) * 4 * chunk + 64));
+    return nv_tb_chunks(eng, al, band, n, pat, txt, max_p, 0, {scores, sources, sinks, ops, ops_stride, n_ops}, chunk, st);
 }
 
 int gasalx_nv_banded_traceback_host(gasalx_engine *eng, const gasalx_nv_aligner *al, uint32_t band, uint32_t n,
@@ -1037,31 +1039,11 @@ int gasalx_nv_banded_traceback_host(gasalx_engine *eng, const gasalx_nv_aligner 
     int rc = nv_btb_checks(al, band, max_p, ops_stride);
     if (rc) return rc;
     if (n == 0) return GASALX_OK;
-    CK(hipSetDevice(eng->device));
-    hipStream_t st = eng->stream;
-    gasalx_nv_strings dp = *pat, dt = *txt;
-    uint32_t *p32;
-    if ((rc = stage_in(eng->nv_pw, pat->words, pat_words, st, &p32))) return rc; dp.words = p32;
-    if ((rc = stage_in(eng->nv_po, pat->offsets, (size_t)n + 1, st, &p32))) return rc; dp.offsets = p32;
-    if ((rc = stage_in(eng->nv_tw, txt->words, txt_words, st, &p32))) return rc; dt.words = p32;
-    if ((rc = stage_in(eng->nv_to, txt->offsets, txt->offsets ? (size_t)n + 1 : 0, st, &p32))) return rc;
-    dt.offsets = txt->offsets ? p32 : nullptr;
-    CK(eng->nv_s.reserve((size_t)n * 4));
-    CK(eng->nv_src.reserve((size_t)n * 8));
-    CK(eng->nv_snk.reserve((size_t)n * 8));
-    CK(eng->nv_ops.reserve((size_t)n * ops_stride + 64));
-    CK(eng->nv_nops.reserve((size_t)n * 4));
-    rc = gasalx_nv_banded_traceback_device(eng, al, band, n, &dp, &dt, max_p, eng->nv_s.as<int32_t>(),
-                                           eng->nv_src.as<uint32_t>(), eng->nv_snk.as<uint32_t>(),
-                                           eng->nv_ops.as<uint8_t>(), ops_stride, eng->nv_nops.as<uint32_t>(), st);
-    if (rc) { (void)hipStreamSynchronize(st); return rc; }
-    CK(hipMemcpyAsync(scores, eng->nv_s.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    CK(hipMemcpyAsync(sources, eng->nv_src.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    CK(hipMemcpyAsync(sinks, eng->nv_snk.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    CK(hipMemcpyAsync(ops, eng->nv_ops.p, (size_t)n * ops_stride, hipMemcpyDeviceToHost, st));
-    CK(hipMemcpyAsync(n_ops, eng->nv_nops.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    CK(hipStreamSynchronize(st));
-    return GASALX_OK;
+    hipStream_t st;
+    if ((rc = enter(eng, nullptr, &st))) return rc;
+    gasalx_nv_strings dp, dt;
+    if ((rc = nv_stage_strings(eng, n, pat, pat_words, txt, txt_words, st, dp, dt))) return rc;
+    return nv_tb_host_run(eng, al, band, n, &dp, &dt, max_p, 0, {scores, sources, sinks, ops, ops_stride, n_ops}, st);
 }
 
 int gasalx_pairhmm_params(const uint8_t *bq, const uint8_t *iq, const uint8_t *dq, uint32_t n, float *qm,
@@ -1097,10 +1079,8 @@ int gasalx_host_free(void *p) {
     return GASALX_OK;
 }
 
-}  // extern "C"
-
 // Diagnostics (gasalx.h): the last packed launch's "aligned here" flags of each workspace.
-extern "C" int gasalx_packed_pairs(gasalx_engine *e, uint64_t *handled, uint64_t *total) {
+int gasalx_packed_pairs(gasalx_engine *e, uint64_t *handled, uint64_t *total) {
     if (!e || !handled || !total) { gx::set_error("gasalx_packed_pairs: NULL argument"); return GASALX_EINVAL; }
     *handled = *total = 0;
     CK(hipSetDevice(e->device));
@@ -1126,3 +1106,5 @@ extern "C" int gasalx_packed_pairs(gasalx_engine *e, uint64_t *handled, uint64_t
         if ((rc = one(s.ws, s.st))) return rc;
     return GASALX_OK;
 }
+
+}  // extern "C"

@@ -1,13 +1,14 @@
 #!/usr/bin/env python3
-"""The dispatcher's launch sequence, path by path, for comparing two builds of the library.
+"""The library's launch sequence, path by path, for comparing two builds of it.
 
-  launch_trace.py run            one small call per dispatcher path on device 0 (GASALX_LIB picks the
-                                 library); meant to run under `rocprofv3 --kernel-trace --output-format csv`
+  launch_trace.py run            one small call per dispatcher path and per host form of the flat API on
+                                 device 0 (GASALX_LIB picks the library); meant to run under
+                                 `rocprofv3 --kernel-trace --output-format csv`
   launch_trace.py list DIR OUT   the kernel-trace CSV(s) under DIR as an ordered list, one line per
                                  launch of the library's kernels: name, grid, block, LDS bytes
 
 Two builds launch the same sequence when their lists are equal line for line
-(profiles/dispatch_refactor/README.md).
+(profiles/dispatch_refactor/README.md, profiles/capi_refactor/README.md).
 """
 import csv
 import glob
@@ -65,6 +66,26 @@ def run():
         eng.align_host(k, G.make_params(algo=G.KSW), seed_scores=np.full(k.n, 20, np.uint32))
     pairs = helpers.hmm_unrelated(0x54, (40, 100, 150))
     eng.pairhmm_quals_host(G.HmmData.from_pairs(pairs))
+
+    # the flat API's other host forms (profiles/capi_refactor/README.md)
+    hmm = G.HmmData.from_pairs(pairs)
+    eng.pairhmm_host(*helpers.hmm_args(pairs, G.pairhmm_params))
+    eng.pairhmm64_quals_host(hmm)
+    eng.pairhmm_quals_log10_host(hmm)
+    rng = np.random.default_rng(0x55)
+    plen = rng.integers(20, 101, 200)
+    P = G.PackedSet.pack([rng.integers(0, 4, int(k)) for k in plen])
+    T = G.PackedSet.pack([rng.integers(0, 4, int(k) + 20) for k in plen], bits=2, big_endian=False)
+    al = G.NvAligner(G.NV_GOTOH, G.NV_SEMI_GLOBAL, 2, -1, -2, -1)
+    eng.nv_score_host(al, P, T)
+    eng.nv_banded_score_host(al, 16, P, T)
+    max_p = int(plen.max())
+    for per, call in ((G.nv_traceback_workspace(max_p, max_p + 20, 1), lambda: eng.nv_traceback_host(al, P, T)),
+                      (G.nv_banded_traceback_workspace(max_p, 16, 1), lambda: eng.nv_banded_traceback_host(al, 16, P, T))):
+        os.environ["GASALX_NV_TB_BUDGET"] = str(70 * per)                         # 200 pairs: chunks of 70, 70, 60
+        call()
+        del os.environ["GASALX_NV_TB_BUDGET"]
+    eng.align_host(rand_batch(0x56, 40_000, 20, 40, 20, 40), G.make_params(algo=G.LOCAL))   # the two-stream pipeline
     eng.close()
 
 
