@@ -564,6 +564,36 @@ static int launch_int32(const Plan &pl, WfFn fn, const WfArgs &A, hipStream_t st
     return GASALX_OK;
 }
 
+#ifdef GX_WF16_STAMP
+// Probe builds only (wavefront16.hpp GX_WF16_STAMP; never the library that is benchmarked): with
+// GASALX_STAMP_OUT=FILE the packed launch's waves stamp their phases, and the call waits for the
+// launch and writes the 5 words per wave to FILE (the last launch's; tools/stamp_summary.py reads it).
+static hipError_t stamp_begin(uint32_t waves, unsigned long long **buf) {
+    *buf = nullptr;
+    if (!std::getenv("GASALX_STAMP_OUT")) return hipSuccess;
+    hipError_t e = hipMalloc((void **)buf, (size_t)waves * 5 * 8);
+    if (e == hipSuccess) e = hipMemset(*buf, 0, (size_t)waves * 5 * 8);
+    if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(gx_wf16_stamp), buf, sizeof *buf);
+    return e;
+}
+static hipError_t stamp_end(uint32_t waves, unsigned long long *buf, hipStream_t st) {
+    if (!buf) return hipSuccess;
+    std::vector<unsigned long long> h((size_t)waves * 5);
+    unsigned long long *none = nullptr;
+    hipError_t e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = hipMemcpy(h.data(), buf, h.size() * 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(gx_wf16_stamp), &none, sizeof none);
+    (void)hipFree(buf);
+    if (e == hipSuccess) {
+        if (FILE *f = std::fopen(std::getenv("GASALX_STAMP_OUT"), "wb")) {
+            std::fwrite(h.data(), 8, h.size(), f);
+            std::fclose(f);
+        }
+    }
+    return e;
+}
+#endif
+
 // Launch the wavefront kernel(s) of plan `pl` over one device batch: the packed
 // kernel first when the plan has one (it flags the blocks it aligned), then the
 // int32 kernel, which aligns exactly the pairs of the declined blocks.  main_tail: the
@@ -623,7 +653,14 @@ static int launch_wavefront(Workspace &ws, const Plan &pl, const gasalx_params &
         }
         if (tail.fn) f16 = tail.fn;
         if (!f16) { set_error("no packed wavefront instance"); return GASALX_EUNSUPPORTED; }
+#ifdef GX_WF16_STAMP
+        unsigned long long *stamps = nullptr;
+        HIPCHK(stamp_begin(grid16 * kWavesPerBlock, &stamps));
+#endif
         HIPCHK(launch_lds(f16, dim3(grid16), dim3(kBlock), lds16, st, P16));
+#ifdef GX_WF16_STAMP
+        HIPCHK(stamp_end(grid16 * kWavesPerBlock, stamps, st));
+#endif
         // ... and the int32 kernel aligns the pairs of the blocks it declined
         A.skip = ws.misc.as<uint8_t>();
         A.skip_ppb = ppb16;

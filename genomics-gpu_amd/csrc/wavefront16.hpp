@@ -653,6 +653,20 @@ __host__ __device__ constexpr int wf16_waves(int algo, int R) {
            : GX_WF16_WAVES;
 }
 
+#ifdef GX_WF16_STAMP
+// Probe builds only (make variants VARIANTS=stamp:-DGX_WF16_STAMP, dispatch.hip stamp_begin): lane 0
+// of every wave stores wall_clock64() at entry, after the block's vote, after the sweep and at exit,
+// then its hardware ids, 5 words per wave at [tile * kWavesPerBlock + wave].  Null: no stamps.
+static __device__ unsigned long long *gx_wf16_stamp;
+#define GX_WF16_STAMP_AT(i)                                                               \
+    do {                                                                                  \
+        if (gx_wf16_stamp && lane == 0)                                                   \
+            gx_wf16_stamp[((size_t)wf16_bid * kWavesPerBlock + wave) * 5 + (i)] = wall_clock64(); \
+    } while (0)
+#else
+#define GX_WF16_STAMP_AT(i) do { } while (0)
+#endif
+
 template <int ALGO_, int G, int R>
 __global__ __launch_bounds__(kBlock, wf16_waves(ALGO_, R)) void wf16_kernel(WfArgs A) {
     const uint32_t wf16_bid = blockIdx.x, wf16_bl = blockIdx.x, wf16_p0 = 0, wf16_lds = A.lds_stride;

@@ -31,6 +31,14 @@
     const uint32_t nn = A.n_dev ? min(*A.n_dev > A.n_dev_off ? *A.n_dev - A.n_dev_off : 0u, A.n) : A.n;
     if (A.n_dev && wf16_p0 + wf16_bl * (uint32_t)(kWavesPerBlock * 2 * S) >= nn) return;
     const uint32_t wv = wf16_bl * kWavesPerBlock + wave;   // wave index of the region
+    GX_WF16_STAMP_AT(0);
+#ifdef GX_WF16_STAMP
+    // HW_ID (wave, SIMD, CU, SE) and XCC_ID of the wave, for the per-SIMD occupancy over time
+    if (gx_wf16_stamp && lane == 0)
+        gx_wf16_stamp[((size_t)wf16_bid * kWavesPerBlock + wave) * 5 + 4] =
+            (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) |
+            ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32);
+#endif
     const uint32_t pair0 = (TQ ? A.slot0 : wf16_p0) + wv * (2 * S);
     // GCP in a mixed-shape launch: the second region (wf16_p0 > 0) has its own band buffers
     const bool breg2 = GCP && wf16_p0 != 0;
@@ -45,9 +53,18 @@
     for (int h = 0; h < 2; ++h) {
         const uint32_t idx = pair0 + 2 * slot + h;   // slot; the pair is perm[slot] when sorted
         valid[h] = idx < nn;
-        pr[h] = (valid[h] && A.perm) ? A.perm[idx] : idx;
-        const uint32_t ql = valid[h] ? A.qlen[pr[h]] : 0, tl = valid[h] ? A.tlen[pr[h]] : 0;
-        const uint32_t qo = valid[h] ? A.qoff[pr[h]] : 0, to = valid[h] ? A.toff[pr[h]] : 0;
+        // plain LOCAL score kernels: every lane loads (an empty slot the launch's last one, nn >= 1
+        // here) and selects afterwards, so that the eight loads of the two halves are in flight
+        // together; a load under its own `valid` branch is waited for before the next one issues
+        const uint32_t ic = ALGO_ == WF_LOCAL ? min(idx, nn - 1u) : idx;
+        pr[h] = ((ALGO_ == WF_LOCAL || valid[h]) && A.perm) ? A.perm[ic] : ic;
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const bool ld = ALGO_ == WF_LOCAL || valid[h];
+        uint32_t ql = ld ? A.qlen[pr[h]] : 0, tl = ld ? A.tlen[pr[h]] : 0;
+        uint32_t qo = ld ? A.qoff[pr[h]] : 0, to = ld ? A.toff[pr[h]] : 0;
+        if (!valid[h]) ql = tl = qo = to = 0;
         xl[h] = TR ? tl : ql; yl[h] = TR ? ql : tl;
         xo[h] = TR ? to : qo; yo[h] = TR ? qo : to;
         xpad[h] = (xl[h] + 7u) & ~7u;
@@ -71,18 +88,55 @@
     const uint32_t words = wf16_lds >> 3;                // positions per slot, >= ymaxw + 2G + 4, multiple of 4
     uint2 *wl = reinterpret_cast<uint2 *>(lds) + (size_t)wave * S * words;
     bool other = false;                                  // a code the packed path cannot score
-    for (uint32_t base = 0; base < S * (words >> 2); base += 64) {
-        const uint32_t idx = base + lane;
-        const uint32_t ps = min(idx / (words >> 2), (uint32_t)S - 1);
-        const uint32_t y0 = 4 * (idx - ps * (words >> 2)) - G;   // first position of this quad
+    // The plain LOCAL score kernels fetch first and build afterwards: every global load of the
+    // prologue -- the query's dwords, then kFetch quads of the step-axis sequences per lane -- is
+    // issued back to back and waited for once, instead of one round trip per staging trip and per
+    // query byte (profiles/persist/README.md).  The other kernels keep a load per trip.
+    constexpr bool BATCH = ALGO_ == WF_LOCAL;
+    constexpr int kFetch = BATCH ? 6 : 1;                // trips per fetch at most (G8, 150 bp: all 6)
+    const uint32_t r0 = lg * R;
+    constexpr int XW = (R + 3) / 4;                      // dwords holding R bytes, one more for the lane's byte offset
+    const bool xdw = BATCH && !A.packed && !A.rev;       // (the packed and reversed forms keep their byte loads)
+    uint32_t xd[2][XW + 1];
+    if (xdw) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int i = 0; i <= XW; ++i) {
+                const uint32_t w = (r0 >> 2) + i;        // whole dwords inside the padded query
+                xd[h][i] = valid[h] && 4 * w < xpad[h] ? reinterpret_cast<const uint32_t *>(X + xo[h])[w] : 0u;
+            }
+    }
+    const uint32_t nquad = S * (words >> 2);
+    for (uint32_t base = 0; base < nquad; base += 64 * kFetch) {
+      uint32_t fps[kFetch], fy0[kFetch], fv[kFetch][2];
+#pragma unroll
+      for (int t = 0; t < kFetch; ++t) {
+        if (t && base + 64 * t >= nquad) continue;        // (wave-uniform: a short tile takes fewer trips)
+        const uint32_t idx = base + 64 * t + lane;
+        fps[t] = min(idx / (words >> 2), (uint32_t)S - 1);
+        fy0[t] = 4 * (idx - fps[t] * (words >> 2)) - G;   // first position of this quad
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const uint32_t yp = __shfl(ypad[h], fps[t] * G), yof = __shfl(yo[h], fps[t] * G);
+            const uint32_t ylen = __shfl(yl[h], fps[t] * G);
+            fv[t][h] = 0;
+            if ((int32_t)fy0[t] >= 0 && fy0[t] < yp) fv[t][h] = load4_codes_dir(A, Y, yof, ylen, fy0[t] >> 2);
+        }
+      }
+#pragma unroll
+      for (int t = 0; t < kFetch; ++t) {
+        if (t && base + 64 * t >= nquad) continue;
+        const uint32_t idx = base + 64 * t + lane, ps = fps[t], y0 = fy0[t];
         uint32_t tab[2][4];
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            const uint32_t yp = __shfl(ypad[h], ps * G), yof = __shfl(yo[h], ps * G);
+            // (shuffled again, not kept from the fetch part: two more ds_bpermute per half and trip
+            // against 24 registers held across the wait)
+            const uint32_t yp = __shfl(ypad[h], ps * G);
             const uint32_t ylen = __shfl(yl[h], ps * G);
-            uint32_t v = 0;
+            const uint32_t v = fv[t][h];
             const bool in = (int32_t)y0 >= 0 && y0 < yp;
-            if (in) v = load4_codes_dir(A, Y, yof, ylen, y0 >> 2);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const uint32_t l = in ? letter_of((v >> (8 * j)) & 15u, A.nval) : 6u;
@@ -94,15 +148,23 @@
                 tab[h][j] = l == 6 ? t_out : l == 4 ? t_n : (t_mis & ~(0xFFu << (8 * l))) | (t_match << (8 * l));
             }
         }
-        if (idx < S * (words >> 2)) {
+        if (idx < nquad) {
             uint2 *dst = wl + ps * words + 4 * (idx - ps * (words >> 2));
 #pragma unroll
             for (int j = 0; j < 4; ++j) dst[j] = make_uint2(tab[0][j], tab[1][j]);
         }
+      }
     }
     // ---- register-axis letters: selector bytes 0 / 2 (0x0C = constant 0 outside) ----
-    const uint32_t r0 = lg * R;
     uint32_t xs[R];
+    if (xdw) {
+        // the fetched dwords start at byte r0 & ~3: shifted by the lane's byte offset, dword k / 4
+        // holds the lane's bytes 4 (k / 4) ..
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int i = 0; i < XW; ++i) xd[h][i] = __builtin_amdgcn_alignbyte(xd[h][i + 1], xd[h][i], r0 & 3u);
+    }
 #pragma unroll
     for (int k = 0; k < R; ++k) {
         const uint32_t r = r0 + k;
@@ -112,7 +174,8 @@
             if (valid[h] && r < xpad[h]) {
                 // (WITH_START reverse pass: position r of "the first xl bases, reversed", N past xl)
                 const uint32_t pos = A.rev ? xl[h] - 1u - r : r;
-                const uint32_t cde = A.rev && r >= xl[h] ? (uint32_t)A.nval
+                const uint32_t cde = xdw ? (xd[h][k / 4] >> (8 * (k & 3))) & 15u
+                                     : A.rev && r >= xl[h] ? (uint32_t)A.nval
                                      : A.packed ? (load4_codes(X, xo[h], pos >> 2, 1) >> (8 * (pos & 3))) & 15u
                                                 : (uint32_t)X[xo[h] + pos] & 15u;
                 const uint32_t l = letter_of(cde, A.nval);
@@ -156,7 +219,8 @@
     } else if (threadIdx.x == 0) {
         A.handled[wf16_bid] = fast ? 1 : 0;
     }
-    if (!fast) return;                                   // the int32 kernel takes this block
+    if (!fast) return;                           // the int32 kernel takes this block
+    GX_WF16_STAMP_AT(1);
 
     const uint32_t nsteps = ymaxw + G - 1;
     const uint2 *tcol = wl + slot * words;
@@ -453,6 +517,7 @@
                 sweep(std::integral_constant<int, 0>{}, nsteps);
             }
         }
+        GX_WF16_STAMP_AT(2);
         // ---- strip-major first maximum per pair (Q1) ----
         // e-drift keys (A.kf16; not K2 / KSEG / the round-2 TB kernel): key = KOFS + H*C' + (C'-1-s),
         // C' = C + G, s = the step (column c = s - lg).  Decoding every row's key took a 32-bit
@@ -549,6 +614,7 @@
                 if (A.tend) A.tend[pr[h]] = te;
             }
         }
+        GX_WF16_STAMP_AT(3);
     } else if (ALGO == WF_GLOBAL) {
         // boundaries (global.h:57-71, Q2): H(r,-1) = -(o+e*r) (0 for r = 0), E = -inf;
         // top: H(-1,c-1) = -(o+e*c) (0 for c = 0), F = -inf.  Lanes sweep garbage
