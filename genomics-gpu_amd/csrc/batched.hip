@@ -10,6 +10,7 @@
 
 #include "engine.hpp"
 #include "nvbio.hpp"
+#include "nvbio_sink.hpp"
 #include "nvtrace.hpp"
 #include "nvbio16.hpp"
 #include "nvbanded.hpp"
@@ -31,6 +32,43 @@ NvFn nv_pick(int G, int R) {
     GX_CASE(32, 16) GX_CASE(64, 16)
 #undef GX_CASE
     return nullptr;
+}
+
+// the sink-tracking form (nvbio_sink.hpp): one instance per aligner kind, type and shape
+using NvSinkFn = void (*)(NvSinkArgs);
+template <int ALN, int TYPE>
+NvSinkFn nv_sink_pick(int G, int R) {
+#define GX_CASE(g, r) if (G == g && R == r) return &nv_sink_kernel<ALN, TYPE, g, r>;
+    GX_CASE(8, 8) GX_CASE(8, 12) GX_CASE(8, 16) GX_CASE(8, 19) GX_CASE(8, 24) GX_CASE(16, 16) GX_CASE(16, 20)
+    GX_CASE(32, 16) GX_CASE(64, 16)
+#undef GX_CASE
+    return nullptr;
+}
+template <int ALN>
+NvSinkFn nv_sink_lookup_t(int type, int G, int R) {
+    return type == NV_GLOBAL ? nv_sink_pick<ALN, NV_GLOBAL>(G, R)
+         : type == NV_SEMI ? nv_sink_pick<ALN, NV_SEMI>(G, R) : nv_sink_pick<ALN, NV_LOCAL>(G, R);
+}
+
+using Nv16SinkFn = void (*)(Nv16SinkArgs);
+template <int ALN, int TYPE, bool SHARED>
+Nv16SinkFn nv16_sink_pick(int G, int R) {
+#define GX_CASE(g, r) if (G == g && R == r) return &nv16_sink_kernel<ALN, TYPE, g, r, SHARED>;
+    GX_CASE(8, 8) GX_CASE(8, 12) GX_CASE(8, 16) GX_CASE(8, 19) GX_CASE(8, 24) GX_CASE(16, 16) GX_CASE(16, 20)
+    GX_CASE(32, 16) GX_CASE(64, 16)
+#undef GX_CASE
+    return nullptr;
+}
+template <int ALN, bool SHARED>
+Nv16SinkFn nv16_sink_lookup_t(int type, int G, int R) {
+    return type == NV_GLOBAL ? nv16_sink_pick<ALN, NV_GLOBAL, SHARED>(G, R)
+         : type == NV_SEMI ? nv16_sink_pick<ALN, NV_SEMI, SHARED>(G, R) : nv16_sink_pick<ALN, NV_LOCAL, SHARED>(G, R);
+}
+Nv16SinkFn nv16_sink_lookup(int aln, int type, bool shared, int G, int R) {
+    if (shared)
+        return aln == NV_GOTOH ? nv16_sink_lookup_t<NV_GOTOH, true>(type, G, R)
+                               : nv16_sink_lookup_t<NV_SW, true>(type, G, R);
+    return aln == NV_GOTOH ? nv16_sink_lookup_t<NV_GOTOH, false>(type, G, R) : nv16_sink_lookup_t<NV_SW, false>(type, G, R);
 }
 
 using Nv16Fn = void (*)(Nv16Args);
@@ -136,21 +174,19 @@ std::string nv_plan_name(const gasalx_nv_aligner &al, uint32_t max_p, uint32_t m
            "_G" + std::to_string(sh->G) + "R" + std::to_string(sh->R);
 }
 
-int nv_score_device(const gasalx_nv_aligner &al, uint32_t n, const gasalx_nv_strings &pat,
-                    const gasalx_nv_strings &txt, int32_t *scores, int16_t *scores16, uint32_t max_p, uint32_t max_t,
-                    hipStream_t st) {
-    if (n == 0) return GASALX_OK;
+// The checks and the kernel arguments both scoring entry points share (outputs apart): ED
+// runs as SW with EditDistanceSWScheme's scores, a shared text sets max_t.
+static int nv_score_args(const gasalx_nv_aligner &al, uint32_t n, const gasalx_nv_strings &pat,
+                         const gasalx_nv_strings &txt, bool have_out, uint32_t max_p, uint32_t &max_t, NvArgs &A) {
     if (al.aligner < 0 || al.aligner > 2 || al.type < 0 || al.type > 2) { set_error("bad aligner"); return GASALX_EINVAL; }
     for (uint32_t b : {pat.bits, txt.bits})
         if (b != 2 && b != 4 && b != 8) { set_error("symbol bits must be 2, 4 or 8"); return GASALX_EINVAL; }
-    if (!pat.words || !pat.offsets || !txt.words || (!scores && !scores16)) { set_error("null argument"); return GASALX_EINVAL; }
-    NvArgs A;
+    if (!pat.words || !pat.offsets || !txt.words || !have_out) { set_error("null argument"); return GASALX_EINVAL; }
     A.pw = pat.words; A.poff = pat.offsets; A.pbits = pat.bits; A.pbig = pat.big_endian;
     A.tw = txt.words; A.toff = txt.offsets; A.tbits = txt.bits; A.tbig = txt.big_endian;
     A.tlen0 = txt.offsets ? 0 : txt.length;
     if (!txt.offsets) max_t = txt.length;
-    A.score = scores; A.score16 = scores16; A.n = n;
-    const bool gotoh = al.aligner == NV_GOTOH;
+    A.score = nullptr; A.score16 = nullptr; A.n = n; A.lds_stride = 0;
     if (al.aligner == NV_ED) { A.match = 0; A.mismatch = -1; A.del = -1; A.ins = -1; }   // ed_utils.h:45-52
     else { A.match = al.match; A.mismatch = al.mismatch; A.del = al.deletion; A.ins = al.insertion; }
     A.go = al.gap_open; A.ge = al.gap_ext;
@@ -159,6 +195,35 @@ int nv_score_device(const gasalx_nv_aligner &al, uint32_t n, const gasalx_nv_str
                                      std::abs((int64_t)A.go), std::abs((int64_t)A.ge), std::abs((int64_t)A.del),
                                      std::abs((int64_t)A.ins), 1});
     if ((int64_t)(max_p + max_t + 2) * mag * 2 >= (1ll << 28)) { set_error("scores out of the exact range"); return GASALX_ERANGE; }
+    return GASALX_OK;
+}
+
+// the packed kernel's arguments from the int32 kernel's
+static Nv16Args nv16_args(const NvArgs &A, uint32_t base, bool shared, uint32_t max_t, int G) {
+    Nv16Args D;
+    D.pw = A.pw; D.poff = A.poff; D.pbits = A.pbits; D.pbig = A.pbig;
+    D.tw = A.tw; D.toff = A.toff; D.tbig = A.tbig; D.tlen0 = A.tlen0;
+    D.score = A.score; D.score16 = A.score16; D.n = A.n;
+    D.match = A.match; D.mismatch = A.mismatch; D.go = A.go; D.ge = A.ge; D.del = A.del; D.ins = A.ins;
+    D.base = base;
+    D.lds_cols = nv16_cols(shared, shared ? A.tlen0 : max_t, G);
+    return D;
+}
+
+static int nv_too_long(uint32_t max_p, uint32_t max_t) {
+    set_error("pattern longer than 1024 or text too long for LDS (" + std::to_string(max_p) + ", " +
+              std::to_string(max_t) + ")");
+    return GASALX_ERANGE;
+}
+
+int nv_score_device(const gasalx_nv_aligner &al, uint32_t n, const gasalx_nv_strings &pat,
+                    const gasalx_nv_strings &txt, int32_t *scores, int16_t *scores16, uint32_t max_p, uint32_t max_t,
+                    hipStream_t st) {
+    if (n == 0) return GASALX_OK;
+    NvArgs A;
+    if (int rc = nv_score_args(al, n, pat, txt, scores || scores16, max_p, max_t, A)) return rc;
+    A.score = scores; A.score16 = scores16;
+    const bool gotoh = al.aligner == NV_GOTOH;
     // LOCAL pads (pattern rows >= M, text columns >= N) never exceed a real cell when no
     // step can raise a score without a match; otherwise mask them
     const bool mask = al.type == NV_LOCAL &&
@@ -172,13 +237,7 @@ int nv_score_device(const gasalx_nv_aligner &al, uint32_t n, const gasalx_nv_str
         const bool shared = !txt.offsets;
         Nv16Fn fn = nv16_lookup(gotoh ? NV_GOTOH : NV_SW, al.type, shared, sh->G, sh->R);
         if (fn) {
-            Nv16Args D;
-            D.pw = A.pw; D.poff = A.poff; D.pbits = A.pbits; D.pbig = A.pbig;
-            D.tw = A.tw; D.toff = A.toff; D.tbig = A.tbig; D.tlen0 = A.tlen0;
-            D.score = scores; D.score16 = scores16; D.n = n;
-            D.match = A.match; D.mismatch = A.mismatch; D.go = A.go; D.ge = A.ge; D.del = A.del; D.ins = A.ins;
-            D.base = base;
-            D.lds_cols = nv16_cols(shared, shared ? A.tlen0 : max_t, sh->G);
+            const Nv16Args D = nv16_args(A, base, shared, max_t, sh->G);
             const size_t lds16 = nv16_lds(shared, shared ? A.tlen0 : max_t, sh->G);
             if (lds16 <= 160 * 1024) {
                 const uint32_t per_block = 8 * (64 / sh->G);   // two pairs per lane group
@@ -196,9 +255,50 @@ int nv_score_device(const gasalx_nv_aligner &al, uint32_t n, const gasalx_nv_str
         if (e != hipSuccess) { set_error(hipGetErrorString(e)); return GASALX_EDEVICE; }
         return GASALX_OK;
     }
-    set_error("pattern longer than 1024 or text too long for LDS (" + std::to_string(max_p) + ", " +
-              std::to_string(max_t) + ")");
-    return GASALX_ERANGE;
+    return nv_too_long(max_p, max_t);
+}
+
+// Score and BestSink position per pair (nvbio_sink.hpp).  The planner is the score-only one:
+// the packed sink kernel inside the packed kernel's window (nv16_ok, tables within LDS), the
+// int32 sink kernel otherwise, at the same lane-group shape; "_sink" marks the plan.
+std::string nv_sinks_plan_name(const gasalx_nv_aligner &al, uint32_t max_p, uint32_t max_t, bool per_pair_text,
+                               uint32_t text_bits) {
+    const std::string name = nv_plan_name(al, max_p, max_t, per_pair_text, text_bits);
+    return name == "none" ? name : name + "_sink";
+}
+
+int nv_score_sinks_device(const gasalx_nv_aligner &al, uint32_t n, const gasalx_nv_strings &pat,
+                          const gasalx_nv_strings &txt, int32_t *scores, uint32_t *sinks, uint32_t max_p,
+                          uint32_t max_t, hipStream_t st) {
+    if (n == 0) return GASALX_OK;
+    NvSinkArgs S;
+    if (int rc = nv_score_args(al, n, pat, txt, scores || sinks, max_p, max_t, S.a)) return rc;
+    S.a.score = scores; S.sinks = sinks;
+    const NvArgs &A = S.a;
+    const uint32_t stride = (std::max<uint32_t>(max_t, 1) + 7u) & ~7u;
+    size_t lds = 0;
+    const bool shared = !txt.offsets;
+    const NvShape *sh = nv_shape(max_p, stride, !shared, &lds);
+    if (!sh) return nv_too_long(max_p, max_t);
+    const int aln = al.aligner == NV_GOTOH ? NV_GOTOH : NV_SW;
+    uint32_t base = 0;
+    const size_t lds16 = nv16_lds(shared, shared ? A.tlen0 : max_t, sh->G);
+    if (lds16 <= 160 * 1024 &&
+        nv16_ok(aln, al.type, A.match, A.mismatch, A.go, A.ge, A.del, A.ins, shared, txt.bits, max_p, max_t, &base)) {
+        const Nv16SinkArgs D = {nv16_args(A, base, shared, max_t, sh->G), sinks};
+        const uint32_t per_block = 8 * (64 / sh->G);   // two pairs per lane group
+        hipError_t e = launch_lds(nv16_sink_lookup(aln, al.type, shared, sh->G, sh->R),
+                                  dim3((n + per_block - 1) / per_block), dim3(256), lds16, st, D);
+        if (e != hipSuccess) { set_error(hipGetErrorString(e)); return GASALX_EDEVICE; }
+        return GASALX_OK;
+    }
+    NvSinkFn fn = aln == NV_GOTOH ? nv_sink_lookup_t<NV_GOTOH>(al.type, sh->G, sh->R)
+                                  : nv_sink_lookup_t<NV_SW>(al.type, sh->G, sh->R);
+    S.a.lds_stride = stride;
+    const uint32_t per_block = 4 * (64 / sh->G);
+    hipError_t e = launch_lds(fn, dim3((n + per_block - 1) / per_block), dim3(256), lds, st, S);
+    if (e != hipSuccess) { set_error(hipGetErrorString(e)); return GASALX_EDEVICE; }
+    return GASALX_OK;
 }
 
 // ---- BatchedBandedAlignmentScore<band> (nvbanded.hpp): thread per pair, band in registers,

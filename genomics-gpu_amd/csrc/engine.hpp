@@ -176,6 +176,13 @@ int pairhmm_log10_device(const Hmm64Src &src, uint32_t n, const float *r32, floa
 int nv_score_device(const gasalx_nv_aligner &al, uint32_t n, const gasalx_nv_strings &pat,
                     const gasalx_nv_strings &txt, int32_t *scores, int16_t *scores16, uint32_t max_p, uint32_t max_t,
                     hipStream_t stream);
+// the same with the BestSink position (nvbio_sink.hpp): sinks[2k] = x (text), sinks[2k + 1] = y
+// (pattern), one-based; scores or sinks may be NULL
+int nv_score_sinks_device(const gasalx_nv_aligner &al, uint32_t n, const gasalx_nv_strings &pat,
+                          const gasalx_nv_strings &txt, int32_t *scores, uint32_t *sinks, uint32_t max_p,
+                          uint32_t max_t, hipStream_t stream);
+std::string nv_sinks_plan_name(const gasalx_nv_aligner &al, uint32_t max_p, uint32_t max_t, bool per_pair_text,
+                               uint32_t text_bits);
 // nvbio BatchedBandedAlignmentScore<band> (batched.hip / nvbanded.hpp): BestSink score per pair
 // max_p: the longest pattern (0: unknown; the packed kernel needs it for its value window)
 int nv_banded_score_device(const gasalx_nv_aligner &al, uint32_t band, uint32_t n, const gasalx_nv_strings &pat,

@@ -33,6 +33,7 @@ EXPORTS = (
     "gasalx_synth_spec", "gasalx_synth_pairs", "gasalx_synth_range", "gasalx_host_alloc", "gasalx_host_free",
     "gasalx_pairhmm_quals_device", "gasalx_pairhmm_quals_host", "gasalx_hmm_file_read", "gasalx_hmm_file_free",
     "gasalx_nv_score_device", "gasalx_nv_score_host", "gasalx_nv_describe_plan",
+    "gasalx_nv_score_sinks_device", "gasalx_nv_score_sinks_host", "gasalx_nv_describe_sinks_plan",
     "gasalx_nv_banded_score_device", "gasalx_nv_banded_score_host",
     "gasalx_nv_traceback_device", "gasalx_nv_traceback_host",
     "gasalx_nv_banded_traceback_device", "gasalx_nv_banded_traceback_host",
@@ -415,6 +416,38 @@ class Engine:
                                           _p(s16)), "nv_score_host")
         return (sc, s16) if int16 else sc
 
+    def nv_score_sinks_host(self, aligner: "NvAligner", patterns: "PackedSet", texts: "PackedSet", scores=True,
+                            sinks=True):
+        """Scores and BestSink positions (gasalx_nv_score_sinks_host): (scores int32[n], sinks
+        uint32[n, 2]) with sinks[k] = (x, y) = (text column, pattern row), one-based, of the last
+        maximum in nvbio's TextBlockingTag report order; (0xFFFFFFFF, 0xFFFFFFFF) and INT32_MIN for
+        a pair that reports no cell.  scores=False / sinks=False pass NULL for that output and
+        return None in its place."""
+        n = patterns.n
+        sc = np.zeros(n, np.int32) if scores else None
+        sk = np.zeros(2 * n, np.uint32) if sinks else None
+        ca = aligner.cstruct()
+        _check(lib().gasalx_nv_score_sinks_host(self._h, ctypes.byref(ca), ctypes.c_uint32(n),
+                                                ctypes.byref(patterns.cstruct()), ctypes.c_uint64(len(patterns.words)),
+                                                ctypes.byref(texts.cstruct()), ctypes.c_uint64(len(texts.words)),
+                                                _p(sc), _p(sk)), "nv_score_sinks_host")
+        return sc, (sk.reshape(n, 2) if sinks else None)
+
+    def nv_score_sinks_device_ptrs(self, aligner: "NvAligner", n: int, pat: dict, txt: dict, scores_ptr: int = 0,
+                                   sinks_ptr: int = 0, max_pattern_len: int = 0, max_text_len: int = 0,
+                                   stream: int = 0):
+        """Device-resident scores and sinks (gasalx_nv_score_sinks_device); pat/txt as
+        nv_score_device_ptrs, scores_ptr n int32, sinks_ptr 2n uint32 (either may be 0)."""
+        mk = lambda d: CNvStrings(d["words"], d.get("offsets") or None, d.get("length", 0), d["bits"],
+                                  int(d.get("big_endian", False)))
+        ca = aligner.cstruct()
+        _check(lib().gasalx_nv_score_sinks_device(self._h, ctypes.byref(ca), ctypes.c_uint32(n),
+                                                  ctypes.byref(mk(pat)), ctypes.byref(mk(txt)),
+                                                  ctypes.c_void_p(scores_ptr or None),
+                                                  ctypes.c_void_p(sinks_ptr or None),
+                                                  ctypes.c_uint32(max_pattern_len), ctypes.c_uint32(max_text_len),
+                                                  ctypes.c_void_p(stream or None)), "nv_score_sinks_device")
+
     def nv_banded_score_host(self, aligner: "NvAligner", band: int, patterns: "PackedSet", texts: "PackedSet"):
         """nvbio BatchedBandedAlignmentScore<band> (gasalx_nv_banded_score_host): BestSink
         score per pair, INT32_MIN where a text is shorter than its pattern."""
@@ -697,6 +730,16 @@ def nv_describe_plan(aligner: "NvAligner", max_p: int, max_t: int, per_pair_text
     al = aligner.cstruct()
     _check(lib().gasalx_nv_describe_plan(ctypes.byref(al), max_p, max_t, int(per_pair_texts), text_bits, buf, 128),
            "nv_describe_plan")
+    return buf.value.decode()
+
+
+def nv_describe_sinks_plan(aligner: "NvAligner", max_p: int, max_t: int, per_pair_texts: bool = False,
+                           text_bits: int = 2) -> str:
+    """The kernel Engine.nv_score_sinks_* runs for these bounds (gasalx_nv_describe_sinks_plan)."""
+    buf = ctypes.create_string_buffer(128)
+    al = aligner.cstruct()
+    _check(lib().gasalx_nv_describe_sinks_plan(ctypes.byref(al), max_p, max_t, int(per_pair_texts), text_bits, buf,
+                                               128), "nv_describe_sinks_plan")
     return buf.value.decode()
 
 

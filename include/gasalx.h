@@ -296,6 +296,31 @@ int gasalx_nv_score_host(gasalx_engine *eng, const gasalx_nv_aligner *aligner, u
                          const gasalx_nv_strings *patterns, uint64_t pattern_words, const gasalx_nv_strings *texts,
                          uint64_t text_words, int32_t *scores, int16_t *scores16);
 
+/* Score and sink: what nvbio's alignment_score(aligner, pattern, text, min_score, sink) leaves
+ * in a BestSink (sink_inl.h:59-68) under a TextBlockingTag aligner: the score and the cell where
+ * it was reached, sinks[2k] = x (text column) and sinks[2k + 1] = y (pattern row), one-based:
+ * the coordinates and layout of gasalx_nv_traceback_*'s sinks.  BestSink keeps the last maximum
+ * in report order: LOCAL reports every cell, text stripes of 8 columns left to right, inside a
+ * stripe the pattern rows top to bottom, inside a row the columns left to right; SEMI_GLOBAL the
+ * last pattern row left to right (the rightmost maximum); GLOBAL the cell (N, M).  A pair that
+ * reports no cell (an empty text; LOCAL: an empty pattern) gets INT32_MIN and (0xFFFFFFFF,
+ * 0xFFFFFFFF).  PatternBlockingTag reports in another order: its tied sinks are not provided.
+ * scores (int32) or sinks may be NULL, not both.  Limits, checks and error codes as
+ * gasalx_nv_score_*.  The full DP only (not banded). */
+int gasalx_nv_score_sinks_device(gasalx_engine *eng, const gasalx_nv_aligner *aligner, uint32_t n_pairs,
+                                 const gasalx_nv_strings *dev_patterns, const gasalx_nv_strings *dev_texts,
+                                 int32_t *dev_scores, uint32_t *dev_sinks, uint32_t max_pattern_len,
+                                 uint32_t max_text_len, void *stream);
+int gasalx_nv_score_sinks_host(gasalx_engine *eng, const gasalx_nv_aligner *aligner, uint32_t n_pairs,
+                               const gasalx_nv_strings *patterns, uint64_t pattern_words,
+                               const gasalx_nv_strings *texts, uint64_t text_words, int32_t *scores,
+                               uint32_t *sinks);
+/* The kernel a gasalx_nv_score_sinks_* call with these bounds runs (e.g.
+ * "nvbio16_gotoh_local_shared_G8R19_sink"): the score-only plan's name with "_sink" appended,
+ * the packed or the int32 kernel by the same rule; arguments as gasalx_nv_describe_plan. */
+int gasalx_nv_describe_sinks_plan(const gasalx_nv_aligner *aligner, uint32_t max_pattern_len, uint32_t max_text_len,
+                                  int per_pair_texts, uint32_t text_bits, char *buf, uint32_t buf_len);
+
 /* nvbio's BatchedBandedAlignmentScore<band_len> (NvB/nvbio/alignment/batched.h:337,
  * batched_banded_inl.h:44-75): the banded DP of sw_banded_inl.h / gotoh_banded_inl.h /
  * ed_banded_inl.h over cells (i, i + j), 0 <= j < band_len (2..32): two pairs per lane in

@@ -22,7 +22,10 @@
  * the flags of every cell, in chunks of at most 4 GiB); enact() does not use the caller's
  * temp buffer.  The TextBlockingTag /
  * PatternBlockingTag score semantics are provided (both give the same scores), full and
- * banded.  Traceback: BatchedAlignmentTraceback<CHECKPOINTS, stream_type> (full DP) and
+ * banded.  The full-DP scorer also reports where the best score ends: AlignmentStream::set_sinks
+ * asks for nvbio's BestSink position (x = text, y = pattern) of every pair, exact to the
+ * TextBlockingTag report order on ties (nvbio_sink.hpp); PatternBlockingTag aligners, whose
+ * tied sinks differ, are refused at compile time.  Traceback: BatchedAlignmentTraceback<CHECKPOINTS, stream_type> (full DP) and
  * BatchedBandedAlignmentTraceback<BAND_LEN, CHECKPOINTS, stream_type> for the edit-distance,
  * Smith-Waterman and Gotoh aligners over a TracebackStream (nvtrace.hpp: one pair per thread,
  * as the reference's DeviceThreadScheduler runs it); the warp variants are not provided.
@@ -35,6 +38,8 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+
+#include <type_traits>
 
 #include "gasalx.h"
 
@@ -91,6 +96,7 @@ struct SimpleGotohScheme {   // utils.h:114-135
 template <AlignmentType T_TYPE, typename AlgorithmType = PatternBlockingTag>
 struct EditDistanceAligner {
     static const AlignmentType TYPE = T_TYPE;
+    typedef AlgorithmType algorithm_tag;
     gasalx_nv_aligner c_aligner() const {
         gasalx_nv_aligner a = {GASALX_NV_ED, (int32)TYPE, 0, -1, 0, 0, -1, -1};
         return a;
@@ -100,6 +106,7 @@ struct EditDistanceAligner {
 template <AlignmentType T_TYPE, typename scoring_scheme_type, typename AlgorithmType = PatternBlockingTag>
 struct SmithWatermanAligner {
     static const AlignmentType TYPE = T_TYPE;
+    typedef AlgorithmType algorithm_tag;
     SmithWatermanAligner() {}
     explicit SmithWatermanAligner(const scoring_scheme_type s) : scheme(s) {}
     gasalx_nv_aligner c_aligner() const {
@@ -113,6 +120,7 @@ struct SmithWatermanAligner {
 template <AlignmentType T_TYPE, typename scoring_scheme_type, typename AlgorithmType = PatternBlockingTag>
 struct GotohAligner {
     static const AlignmentType TYPE = T_TYPE;
+    typedef AlgorithmType algorithm_tag;
     GotohAligner() {}
     explicit GotohAligner(const scoring_scheme_type s) : scheme(s) {}
     gasalx_nv_aligner c_aligner() const {
@@ -162,11 +170,25 @@ struct AlignmentStream {
     uint32 size() const { return m_count; }
     uint64 cells() const { return uint64(m_total_pattern_len) * uint64(m_text_len); }
 
+    // Ask for the BestSink position of every pair beside its score (what nvbio's
+    // alignment_score(aligner, pattern, text, min_score, sink) leaves in the sink): a device
+    // array of 2 x count entries, sinks[2k] = x (text), sinks[2k + 1] = y (pattern), one-based.
+    // On ties BestSink keeps the last maximum in the aligner's report order, and the kernels
+    // follow the TextBlockingTag order (text stripes of 8 columns).
+    void set_sinks(uint32 *sinks) {
+        static_assert(std::is_same<typename aligner_type::algorithm_tag, TextBlockingTag>::value,
+                      "sinks are provided for TextBlockingTag aligners only: PatternBlockingTag reports cells in "
+                      "another order (pattern stripes), so its tied sinks differ; make the aligner with "
+                      "make_*_aligner<TYPE, TextBlockingTag>(...) or score without sinks");
+        m_sinks = sinks;
+    }
+
     aligner_type m_aligner;
     uint32 m_count, m_max_pattern_len, m_total_pattern_len, m_text_len;
     const uint32 *m_offsets, *m_patterns, *m_text;
     int16 *m_scores;
     int32 *m_scores32 = nullptr;            // optional int32 scores
+    uint32 *m_sinks = nullptr;              // optional BestSink positions, 2 x count: set_sinks()
     const uint32 *m_text_offsets = nullptr; // per-pattern texts instead of the shared one
     uint32 m_pattern_bits = 4, m_pattern_big_endian = 1;   // io::SequenceDataTraits<DNA_N>
     uint32 m_text_bits = 2, m_text_big_endian = 0;         // REF_BITS / REF_BIG_ENDIAN
@@ -206,9 +228,25 @@ struct BatchedAlignmentScore {
                                stream.m_pattern_big_endian};
         gasalx_nv_strings t = {stream.m_text, stream.m_text_offsets, stream.m_text_len, stream.m_text_bits,
                                stream.m_text_big_endian};
-        const int rc = gasalx_nv_score_device(engine(), &a, stream.size(), &p, &t, stream.m_scores32,
-                                              stream.m_scores, stream.max_pattern_length(),
-                                              stream.max_text_length(), hip_stream);
+        int rc;
+        if (stream.m_sinks) {
+            // set_sinks() refuses PatternBlockingTag at compile time; a pointer stored around it
+            // must not get TextBlockingTag sinks silently
+            if (!std::is_same<typename aligner_type::algorithm_tag, TextBlockingTag>::value) {
+                fprintf(stderr, "BatchedAlignmentScore::enact: sinks need a TextBlockingTag aligner\n");
+                exit(EXIT_FAILURE);
+            }
+            if (stream.m_scores) {
+                fprintf(stderr, "BatchedAlignmentScore::enact: with sinks the scores are int32, set m_scores32\n");
+                exit(EXIT_FAILURE);
+            }
+            rc = gasalx_nv_score_sinks_device(engine(), &a, stream.size(), &p, &t, stream.m_scores32, stream.m_sinks,
+                                              stream.max_pattern_length(), stream.max_text_length(), hip_stream);
+        } else {
+            rc = gasalx_nv_score_device(engine(), &a, stream.size(), &p, &t, stream.m_scores32,
+                                        stream.m_scores, stream.max_pattern_length(),
+                                        stream.max_text_length(), hip_stream);
+        }
         if (rc != GASALX_OK) {
             fprintf(stderr, "BatchedAlignmentScore::enact: %s\n", gasalx_last_error());
             exit(EXIT_FAILURE);

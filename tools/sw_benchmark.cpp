@@ -1,7 +1,7 @@
 // sw_benchmark.cpp — the nvbio sw-benchmark idiom over the second front-end
 // (include/nvbio_batched.h), as a client of that header and -lgasal only.
 //
-//   sw_benchmark [-tests gotoh:ed:sw] [-scores FILE] reads.{fa,fq} reference.fa
+//   sw_benchmark [-tests gotoh:ed:sw] [-scores FILE] [-sinks] reads.{fa,fq} reference.fa
 //
 // * Reads (FASTA or FASTQ) are packed as nvbio reads: DNA_N codes (A0 C1 G2 T3, other 4),
 //   4 bits per symbol, big-endian words; the reference FASTA is one text of 2-bit codes,
@@ -14,6 +14,9 @@
 //   Smith-Waterman (2, -1, -1, -1) local.
 // * -scores FILE writes every int16 score, one line per read and test, for parity
 //   checks (tests/test_gpu_nvbio.py).
+// * -sinks also times the sink form of every test (AlignmentStream::set_sinks: int32 scores
+//   and the BestSink position of every read): after the usual line, five timed enacts of the
+//   score-only and of the sink form, alternating, and the GCUPS of each.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -92,7 +95,7 @@ static void pack(const std::vector<uint32> &codes, uint32 bits, bool big, std::v
 template <typename aligner_type>
 static void profile(const char *name, const aligner_type aligner, uint32 n, const uint32 *d_off, const uint32 *d_pat,
                     uint32 max_len, uint32 total, const uint32 *d_ref, uint32 ref_len, int16 *d_scores,
-                    FILE *scores_out, const char *test) {
+                    FILE *scores_out, const char *test, int32 *d_scores32 = nullptr, uint32 *d_sinks = nullptr) {
     typedef aln::AlignmentStream<aligner_type> stream_type;
     stream_type stream(aligner, n, d_off, d_pat, max_len, total, d_ref, ref_len, d_scores);
     aln::BatchedAlignmentScore<stream_type, aln::DeviceThreadScheduler> batch;
@@ -103,6 +106,29 @@ static void profile(const char *name, const aligner_type aligner, uint32 n, cons
     HCK(hipDeviceSynchronize());
     const double dt = now() - t0;
     fprintf(stderr, "    %15s :   %7.1f GCUPS\n", name, 1.0e-9 * (double)stream.cells() / dt);
+    if (d_sinks) {   // -sinks: the same batch with int32 scores and the BestSink positions
+        stream_type with_sinks(aligner, n, d_off, d_pat, max_len, total, d_ref, ref_len, NULL);
+        with_sinks.m_scores32 = d_scores32;
+        with_sinks.set_sinks(d_sinks);
+        batch.enact(with_sinks, 0, NULL);   // warm-up of the sink kernel
+        HCK(hipDeviceSynchronize());
+        // both forms alternating in one process, kSinkReps timed enacts each
+        const int kSinkReps = 5;
+        double t_score = 0, t_sink = 0;
+        for (int r = 0; r < kSinkReps; r++) {
+            double t1 = now();
+            batch.enact(stream, 0, NULL);
+            HCK(hipDeviceSynchronize());
+            t_score += now() - t1;
+            t1 = now();
+            batch.enact(with_sinks, 0, NULL);
+            HCK(hipDeviceSynchronize());
+            t_sink += now() - t1;
+        }
+        const double gc = 1.0e-9 * (double)stream.cells() * kSinkReps;
+        fprintf(stderr, "    %15s :   %7.1f GCUPS (score only, %d enacts)\n", name, gc / t_score, kSinkReps);
+        fprintf(stderr, "    %15s :   %7.1f GCUPS (score + sink, %d enacts)\n", name, gc / t_sink, kSinkReps);
+    }
     if (scores_out) {
         std::vector<int16> h(n);
         HCK(hipMemcpy(h.data(), d_scores, n * sizeof(int16), hipMemcpyDeviceToHost));
@@ -113,8 +139,9 @@ static void profile(const char *name, const aligner_type aligner, uint32 n, cons
 int main(int argc, char **argv) {
     bool t_gotoh = true, t_ed = true, t_sw = false;
     const char *scores_path = nullptr;
+    bool sinks = false;
     if (argc < 3) {
-        fprintf(stderr, "usage: sw_benchmark [-tests gotoh:ed:sw] [-scores FILE] reads ref.fa\n");
+        fprintf(stderr, "usage: sw_benchmark [-tests gotoh:ed:sw] [-scores FILE] [-sinks] reads ref.fa\n");
         return 1;
     }
     for (int i = 1; i < argc - 2; i++) {
@@ -124,6 +151,7 @@ int main(int argc, char **argv) {
             t_ed = s.find("ed") != std::string::npos;
             t_sw = s.find("sw") != std::string::npos;
         } else if (!strcmp(argv[i], "-scores")) scores_path = argv[++i];
+        else if (!strcmp(argv[i], "-sinks")) sinks = true;
     }
     fprintf(stderr, "sw-benchmark... started\n");
     const std::vector<std::string> reads = read_sequences(argv[argc - 2]);
@@ -159,6 +187,12 @@ int main(int argc, char **argv) {
         HCK(hipMalloc(&d_pat, words.size() * 4));
         HCK(hipMalloc(&d_off, offs.size() * 4));
         HCK(hipMalloc(&d_scores, (size_t)n * 2 + 2));
+        int32 *d_s32 = nullptr;
+        uint32 *d_snk = nullptr;
+        if (sinks) {
+            HCK(hipMalloc(&d_s32, (size_t)n * 4 + 4));
+            HCK(hipMalloc(&d_snk, (size_t)n * 8 + 8));
+        }
         HCK(hipMemcpy(d_pat, words.data(), words.size() * 4, hipMemcpyHostToDevice));
         HCK(hipMemcpy(d_off, offs.data(), offs.size() * 4, hipMemcpyHostToDevice));
         if (t_gotoh) {
@@ -166,26 +200,28 @@ int main(int argc, char **argv) {
             scoring.m_match = 2; scoring.m_mismatch = -1; scoring.m_gap_open = -2; scoring.m_gap_ext = -1;
             fprintf(stderr, "  testing Gotoh scoring speed...\n");
             profile("global", aln::make_gotoh_aligner<aln::GLOBAL, aln::TextBlockingTag>(scoring), n, d_off, d_pat,
-                    max_len, total, d_ref, ref_len, d_scores, sout, "gotoh");
+                    max_len, total, d_ref, ref_len, d_scores, sout, "gotoh", d_s32, d_snk);
             profile("semi-global", aln::make_gotoh_aligner<aln::SEMI_GLOBAL, aln::TextBlockingTag>(scoring), n, d_off,
-                    d_pat, max_len, total, d_ref, ref_len, d_scores, sout, "gotoh");
+                    d_pat, max_len, total, d_ref, ref_len, d_scores, sout, "gotoh", d_s32, d_snk);
             profile("local", aln::make_gotoh_aligner<aln::LOCAL, aln::TextBlockingTag>(scoring), n, d_off, d_pat,
-                    max_len, total, d_ref, ref_len, d_scores, sout, "gotoh");
+                    max_len, total, d_ref, ref_len, d_scores, sout, "gotoh", d_s32, d_snk);
         }
         if (t_ed) {
             fprintf(stderr, "  testing Edit Distance scoring speed...\n");
             profile("semi-global", aln::make_edit_distance_aligner<aln::SEMI_GLOBAL, aln::TextBlockingTag>(), n, d_off,
-                    d_pat, max_len, total, d_ref, ref_len, d_scores, sout, "ed");
+                    d_pat, max_len, total, d_ref, ref_len, d_scores, sout, "ed", d_s32, d_snk);
         }
         if (t_sw) {
             fprintf(stderr, "  testing Smith-Waterman scoring speed...\n");
             profile("local", aln::make_smith_waterman_aligner<aln::LOCAL, aln::TextBlockingTag>(
                                  aln::SimpleSmithWatermanScheme(2, -1, -1, -1)),
-                    n, d_off, d_pat, max_len, total, d_ref, ref_len, d_scores, sout, "sw");
+                    n, d_off, d_pat, max_len, total, d_ref, ref_len, d_scores, sout, "sw", d_s32, d_snk);
         }
         HCK(hipFree(d_pat));
         HCK(hipFree(d_off));
         HCK(hipFree(d_scores));
+        if (d_s32) HCK(hipFree(d_s32));
+        if (d_snk) HCK(hipFree(d_snk));
     }
     if (sout) fclose(sout);
     HCK(hipFree(d_ref));
