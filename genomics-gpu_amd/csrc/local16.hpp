@@ -18,11 +18,14 @@
 // to cell and row to row.  Per row: x2 = (prev2 < maxHH) ? row : x2;
 // prev2 = max(max2, prev2) (:412-418, the reference compares prev2 with maxHH).
 //
-// N: the N rule (gasal_kernels.h:49-51) holds for pads: pad columns get tables
+// N: the N rule (gasal_kernels.h:49-51) holds for pads: N columns get tables
 // of the N score, pad rows (the last tile) a patched byte; pad cells can update
-// the second best (Q13), so they are computed exactly.  A real N or another
-// letter inside a sequence, or a second pair of another tile geometry, is
-// declined to gen_local_kernel (todo).
+// the second best (Q13), so they are computed exactly.  A target column is
+// scored by its code wherever it lies: a reverse op moves the pads of a slot to
+// its front and leaves real bases past tl (pack_rc_seqs.h:109-167), and the
+// reference sweeps the whole padded slot.  A real N or another letter inside a
+// query, a target code that is neither A/C/G/T nor N, or a second pair of
+// another tile geometry, is declined to gen_local_kernel (todo).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -73,7 +76,7 @@ __global__ __launch_bounds__(256, WAVES) void local2nd16_kernel(Local16Args A) {
         else A.todo[c] = 1;
     }
     const bool two = pb != pa;
-    const uint32_t qlb = A.qlen[pb], tlb = A.tlen[pb];
+    const uint32_t qlb = A.qlen[pb];
     const uint32_t *qwa = A.qw + (A.qoff[pa] >> 3), *qwb = A.qw + (A.qoff[pb] >> 3);
     const uint32_t *twa = A.tw + (A.toff[pa] >> 3), *twb = A.tw + (A.toff[pb] >> 3);
     const uint32_t BB = A.base * 0x10001u, OE2 = (uint32_t)A.oe * 0x10001u, EXT = (uint32_t)A.e * 0x10001u;
@@ -147,13 +150,14 @@ __global__ __launch_bounds__(256, WAVES) void local2nd16_kernel(Local16Args A) {
     for (int k = 0; k < 8; ++k) nx[k] = make_uint2(BB, BB);
     uint32_t nqa = qwa[0], nqb = qwb[0];
     for (uint32_t i = 0; i < TR; ++i) {
-        // substitution tables of the strip, byte l = s(l, t) + K; pad and N columns: the N score
+        // substitution tables of the strip, byte l = s(l, t) + K; N columns (the pads of an
+        // untouched slot among them): the N score.  By the code alone, not by col >= tl: after
+        // a reverse op the columns past tl hold real bases
         const uint32_t ga = twa[i], gb = twb[i];
 #pragma unroll
         for (int m = 0; m < 8; ++m) {
-            const uint32_t col = i * 8 + m;
             const uint32_t ca = (ga >> (28 - 4 * m)) & 15u, cb = (gb >> (28 - 4 * m)) & 15u;
-            const bool na = col >= tla || ca == (uint32_t)A.nval, nb = col >= tlb || cb == (uint32_t)A.nval;
+            const bool na = ca == (uint32_t)A.nval, nb = cb == (uint32_t)A.nval;
             ok_a &= na || ((0x9Au >> ca) & 1u);
             ok_b &= nb || ((0x9Au >> cb) & 1u);
             T0[m] = na ? BYTE_N * 0x01010101u : BYTE_X * 0x01010101u + ((BYTE_M - BYTE_X) << (8 * ((ca >> 1) & 3u)));

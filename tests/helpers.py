@@ -184,6 +184,115 @@ def random_pairs(rng, n, qmin, qmax, tmin, tmax, related=0.7, alphabet=b"ACGT"):
     return qs, ts
 
 
+# ------------------------------------------------ reverse / complement ops ----
+# query and target lengths of the edge batch: 1 to 5 words, odd and even word counts,
+# len % 8 in {0, 1, 7}
+OPS_EDGE_LENS = (1, 7, 8, 9, 15, 16, 17, 23, 24, 25, 33, 40)
+# letters whose low nibble is a base's code (1, 3, 4, 7) without being A/C/G/T, with IUPAC
+# letters of other codes beside them: the complement acts on nibbles, not on letters
+OPS_ODD_ALPHABET = b"ACGTSWDQacgtswdqRYKM"
+_NIB_COMP = {1: 4, 4: 1, 3: 7, 7: 3}
+_BASE_COMP = bytes.maketrans(b"ACGTacgt", b"TGCAtgca")
+_BASE_COMP = bytes(_BASE_COMP[c] if c in b"ACGTacgt" else (c & 0xF0) | _NIB_COMP.get(c & 15, c & 15) for c in range(256))
+
+
+def base_op(s: bytes, op: int) -> bytes:
+    """Op code 0..3 on the bases alone (no slot, no pads): its own inverse."""
+    if op & 1:
+        s = s[::-1]
+    if op & 2:
+        s = s.translate(_BASE_COMP)
+    return s
+
+
+def _fit(rng, s, n, alphabet):
+    return (s + random_seq(rng, max(0, n - len(s)), alphabet))[:n]
+
+
+def ops_batch(kind, alphabet=b"ACGT", seed=0x0B5):
+    """(queries, targets, q_ops, t_ops) for the reverse / complement tests.
+    kind "edges": all 16 (q_op, t_op) combinations, 19 pairs each; per combination the first
+      twelve pairs walk every query length of OPS_EDGE_LENS against a permutation of the
+      target lengths, the rest draw both independently.
+    kind "flagship": 300 pairs of 140..160 bases, ops uniform in 0..3.
+    About half the pairs are related *after* their ops: the post-op query is drawn, mutated
+    into the post-op target (10 % substitutions, a few indels), and the inverse op on the
+    bases gives the inputs.  The slot reversal moves the pads to the front, so the kernels
+    see these shifted by the pad count: still alignable, and far from the no-op answer."""
+    rng = np.random.default_rng(seed + 977 * len(alphabet) + (0 if kind == "edges" else 1))
+    L = OPS_EDGE_LENS
+    shape = []
+    if kind == "edges":
+        for c in range(15, -1, -1):         # pair 0: ops (3, 3) on a one-word query at word 0
+            for j in range(19):
+                ql, tl = (L[j], L[(5 * j + c) % 12]) if j < 12 else (int(rng.choice(L)), int(rng.choice(L)))
+                shape.append((c >> 2, c & 3, ql, tl))
+    else:
+        for _ in range(300):
+            shape.append((int(rng.integers(0, 4)), int(rng.integers(0, 4)), int(rng.integers(140, 161)),
+                          int(rng.integers(140, 161))))
+    qs, ts = [], []
+    for k, (qo, to, ql, tl) in enumerate(shape):
+        q = random_seq(rng, ql, alphabet)
+        if k % 2 == 0:
+            t = _fit(rng, mutate(rng, q, sub=0.10, indel=0.02), tl, alphabet)
+        else:
+            t = random_seq(rng, tl, alphabet)
+        qs.append(base_op(q, qo)); ts.append(base_op(t, to))
+    return qs, ts, np.array([s[0] for s in shape], np.uint8), np.array([s[1] for s in shape], np.uint8)
+
+
+OPS_CASES = [("edges", b"ACGT"), ("edges", b"ACGTN"), ("edges", OPS_ODD_ALPHABET), ("flagship", b"ACGT"),
+             ("flagship", b"ACGTN")]
+OPS_SCORES = [(1, 4, 6, 1), (2, 3, 5, 2)]
+_OPS_CASE = {}
+_OPS_REF = {}
+
+
+def ops_case(kind, alphabet):
+    """One ops batch, built once per process: dict(qs, ts, b: the gasal_ffi.Batch, qo, to: the
+    op arrays, ob: independent.apply_ops(b, qo, to), oq, ot: its sequences)."""
+    import gasal_ffi as G
+    import independent as I
+    key = (kind, alphabet)
+    if key not in _OPS_CASE:
+        qs, ts, qo, to = ops_batch(kind, alphabet)
+        b = G.Batch.from_pairs(qs, ts)
+        ob = I.apply_ops(b, qo, to)
+        oq, ot = I.op_sequences(ob)
+        _OPS_CASE[key] = dict(qs=qs, ts=ts, b=b, qo=qo, to=to, ob=ob, oq=oq, ot=ot)
+    return _OPS_CASE[key]
+
+
+def ops_ref(kind, alphabet, name, fn):
+    """fn(case) computed once per (batch, name) and shared by the tests that need it; the
+    result is handed out as is and never written to."""
+    key = (kind, alphabet, name)
+    if key not in _OPS_REF:
+        _OPS_REF[key] = fn(ops_case(kind, alphabet))
+    return _OPS_REF[key]
+
+
+def ops_dependence(case, sc=(1, 4, 6, 1)):
+    """Per algorithm, the share of the pairs with a nonzero op whose independent answer on the
+    op-transformed batch differs from the independent answer on the untouched batch (LOCAL and
+    SEMI_GLOBAL: score and ends, GLOBAL: score).  A batch whose answers do not depend on its
+    ops would pass with the ops ignored."""
+    import independent as I
+    b, ob = case["b"], case["ob"]
+    has = (case["qo"] != 0) | (case["to"] != 0)
+    out = {}
+    for name, fn, fields in (("local", I.local, ("score", "q_end", "t_end")), ("global", I.global_, ("score",)),
+                             ("semi", I.semi, ("score", "q_end", "t_end"))):
+        r0 = fn(b, **dict(zip("aboe", sc)))
+        r1 = fn(ob, **dict(zip("aboe", sc)))
+        diff = np.zeros(b.n, bool)
+        for f in fields:
+            diff |= r0[f] != r1[f]
+        out[name] = float(diff[has].mean())
+    return out
+
+
 # ------------------------------------------------------------------ KSW ----
 def _unlike(rng, n, avoid):
     """n bases that never equal the base at the same position of `avoid` (cycled)."""

@@ -30,6 +30,9 @@ Beyond the score kernels this module also restates, each in a form of its own:
   replay_cigar()    walks a forward CIGAR over the two sequences: consumed lengths, M/X
                     labels against the bases, the affine score of the path.
   global_textbook() plain affine global DP without any reference quirk, for rectangle checks.
+  apply_ops()       the reverse / complement pre-op (pack_rc_seqs.h:56-212) in base space: a
+                    slice reversal of the padded slot and a code table, no words; every function
+                    above runs unchanged on the batch it returns.
 
 What the WITH_START coordinates mean.  The reverse pass does not start at the
 end cell (q_end, t_end).  It starts at the last base of the 8-base *word* that holds each
@@ -98,6 +101,103 @@ def _codes(data, offs, lens, n_code):
     src = np.where(inside, np.minimum(idx, len(data) - 1), 0)
     c = (data[src].astype(np.int32) & 15)
     return np.where(inside, c, n_code & 15), pad
+
+
+OP_FORWARD, OP_REVERSE, OP_COMPLEMENT, OP_REVCOMP = 0, 1, 2, 3
+
+# complement of a 4-bit code: A (1) <-> T (4), C (3) <-> G (7), every other code kept
+_COMPLEMENT = np.arange(16, dtype=np.uint8)
+_COMPLEMENT[[1, 4, 3, 7]] = [4, 1, 7, 3]
+
+
+class OpBatch:
+    """What apply_ops returns: the six arrays of a batch, the data being 4-bit codes."""
+
+    def __init__(self, q_data, q_offsets, q_lens, t_data, t_offsets, t_lens):
+        self.q_data, self.q_offsets, self.q_lens = q_data, q_offsets, q_lens
+        self.t_data, self.t_offsets, self.t_lens = t_data, t_offsets, t_lens
+
+    @property
+    def n(self):
+        return len(self.q_lens)
+
+    @property
+    def q_bytes(self):
+        return len(self.q_data)
+
+    @property
+    def t_bytes(self):
+        return len(self.t_data)
+
+
+def apply_ops(batch, q_ops, t_ops, n_code=0x4E):
+    """The batch as gasal_reversecomplement_kernel (pack_rc_seqs.h:56-212) leaves it, in base
+    space: same offsets and lengths, every byte of a padded slot its 4-bit code (the pack
+    kernel's `& 15`, :24-31; every reader of this module masks the same way).  Op bit 0
+    reverses, bit 1 complements (:109,169); a pair whose two ops are both 0 is left alone (:62).
+
+    Closed form for n_code > 15, derived from the reverse branch (:109-167) with R = the
+    slot's words and S = ceil(R / 2) iterations (:72):
+      - nbr_N counts the nibbles of the last word that equal N_CODE (:113-116).  A nibble is
+        at most 15 and N_CODE is 0x4E, so the count is 0 and nbr_N << 2 is 0 (:121).
+      - rpac_2 = (W[R-2-i] << 32) | (W[R-1-i] >> 0) (:136).  A 32-bit shift by 32 gives 0 on
+        the device, so rpac_2 = W[R-1-i]: the word before the sequence, which a one-word
+        sequence reads as W[-1], never reaches the result.
+      - to_queue_1 = (rev(W[i]) << 0) | (W[R-1-i] & 0) = rev(W[i]) (:152), rev being the word's
+        eight nibbles in opposite order (:144-148).  Stores :160-161 therefore exchange words i
+        and R-1-i, each nibble-reversed.
+      - to_queue_2 = (W[R-2-i] & 0xFFFFFFFF) | (rev(W[i]) >> 32) = W[R-2-i] as read before the
+        stores (:153).  It is stored only for i < S-1 (:162), where R-2-i differs from both
+        i and R-1-i (R-2-i == i needs i = R/2 - 1 = S-1): the third store writes back what
+        it read.
+      - odd R: the last iteration has i == R-1-i, both stores write rev of the word read
+        before them: the middle word is reversed in place.
+    Exchanging words i <-> R-1-i with each word's nibbles reversed is the reversal of the whole
+    slot of pad8(len) nibbles, pads included: after a reverse the slot *begins* with its pads.
+    The complement branch (:169-205) maps A_PAK <-> T_PAK and C_PAK <-> G_PAK (1 <-> 4, 3 <-> 7,
+    :5-8,182-193) on every nibble of the slot's words and leaves any other code, the pad's
+    0xE included, alone.  It runs after the reverse; a per-nibble map and a permutation of
+    the nibbles commute, so the order does not show in the result.
+
+    n_code <= 15 is out of scope (ValueError): that branch counts N nibbles anywhere in the
+    last word, shifts by the count, and for a one-word sequence reads the neighbouring pair's
+    word while another thread may be rewriting it.  The reference is never compiled that way.
+
+    Written per slot as a slice reversal and a table lookup; a zero-length sequence has no
+    slot and is left alone."""
+    if n_code <= 15:
+        raise ValueError("apply_ops: n_code <= 15 is out of scope (see the docstring)")
+    q_ops = np.asarray(q_ops, np.uint8); t_ops = np.asarray(t_ops, np.uint8)
+    touched = (q_ops != 0) | (t_ops != 0)                       # :62
+
+    def side(data, offs, lens, ops):
+        out = np.asarray(data, np.uint8) & 15
+        for k in np.flatnonzero(touched & (ops != 0)):
+            lo = int(offs[k]); hi = lo + (int(lens[k]) + 7) // 8 * 8
+            slot = out[lo:hi].copy()
+            if ops[k] & OP_REVERSE:
+                slot = slot[::-1]
+            if ops[k] & OP_COMPLEMENT:
+                slot = _COMPLEMENT[slot]
+            out[lo:hi] = slot
+        return out
+
+    arrays = (side(batch.q_data, batch.q_offsets, batch.q_lens, q_ops), batch.q_offsets, batch.q_lens,
+              side(batch.t_data, batch.t_offsets, batch.t_lens, t_ops), batch.t_offsets, batch.t_lens)
+    try:
+        return type(batch)(*arrays)                 # a gasal_ffi.Batch stays one
+    except TypeError:
+        return OpBatch(*arrays)
+
+
+def op_sequences(opb):
+    """Every whole slot (pad8(len) codes) of an apply_ops batch, as bytes, for replay_batch in
+    LOCAL mode.  After a reverse the slot begins with its pads and real bases sit past
+    position len - 1; the LOCAL kernels sweep the whole padded slot, so an end (and a CIGAR)
+    may lie there."""
+    def side(data, offs, lens):
+        return [bytes(data[int(o):int(o) + (int(n) + 7) // 8 * 8]) for o, n in zip(offs, lens)]
+    return side(opb.q_data, opb.q_offsets, opb.q_lens), side(opb.t_data, opb.t_offsets, opb.t_lens)
 
 
 def _sub(rb, gb, a, b, nval, npen, n_rule):
@@ -664,4 +764,55 @@ def replay_batch(qs, ts, batch, res, scores, mode, decode, keep, rect=True):
             g = global_textbook(q, t, scores, n_rule=True)
             if g != sc:
                 fail(k, "rectangle", f"global alignment of the rectangle {g}, score {sc}")
+    return out
+
+
+def replay_global_slots(opb, res, scores, decode, keep):
+    """replay_cigar over the GLOBAL + TB CIGARs of an apply_ops batch.  The score is H(ql-1, tl-1)
+    over the first ql and tl codes of the slots, but the walk starts at the pad cell (tl, ql)
+    (rule G1).  Without ops that cell holds two pads, which match, and the walk leaves it
+    through its diagonal.  After a reverse the codes at positions ql and tl are real bases:
+      - ql % 8 and tl % 8 both non-zero: (tl, ql) is a cell the sweep computed, with a
+        direction of its own, possibly a gap that never passes through (ql-1, tl-1).  The
+        CIGAR is then a global path over the sequences one code longer, and its score is that
+        cell's H: global_() of the same slots with both lengths one larger (the padded slots
+        are the same, so is the sweep).  Checked as such: replay_cigar over q[:ql+1], t[:tl+1]
+        with a closing M for rule G1's unscored pair.  Where the CIGAR leaves the cell through
+        its diagonal, the path without that pair must be worth the reported score.
+      - otherwise the cell lies past the swept matrix, its direction word reads 0 and the
+        walk writes M whatever the codes: replay_cigar's own G1.
+    Returns dict(checked, through: pairs whose pad cell was left through its diagonal,
+    failures)."""
+    a, b, o, e = scores
+    ql, tl = np.asarray(opb.q_lens, np.int64), np.asarray(opb.t_lens, np.int64)
+    inner = (ql % 8 != 0) & (tl % 8 != 0)
+    ext = OpBatch(opb.q_data, opb.q_offsets, (ql + inner).astype(np.uint32),
+                  opb.t_data, opb.t_offsets, (tl + inner).astype(np.uint32))
+    pad_h = global_(ext, a, b, o, e)["score"]
+    out = dict(checked=0, through=0, failures=[])
+    fail = lambda k, what, d: out["failures"].append((int(k), what, d))
+    for k in np.flatnonzero(keep):
+        cig = decode(res["cigar"], int(opb.q_offsets[k]), int(res["n_ops"][k]))
+        sc = int(res["score"][k])
+        x = int(inner[k])
+        q = bytes(opb.q_data[int(opb.q_offsets[k]):int(opb.q_offsets[k]) + int(ql[k]) + x])
+        t = bytes(opb.t_data[int(opb.t_offsets[k]):int(opb.t_offsets[k]) + int(tl[k]) + x])
+        qu, tu, s, bad, _ = replay_cigar(q, t, cig + "1M" * x, scores, GLOBAL_MODE)
+        out["checked"] += 1
+        if (qu, tu) != (len(q) + 1, len(t) + 1):
+            fail(k, "lengths", f"consumed {(qu, tu)} of {(len(q) + 1, len(t) + 1)}: {cig}")
+        if bad is not None:
+            fail(k, "label", f"{bad}: {cig}")
+        if x:
+            if s != int(pad_h[k]):
+                fail(k, "pad cell", f"replayed {s}, H at the pad cell {int(pad_h[k])}: {cig}")
+            if cig[-1] in "MX":
+                out["through"] += 1
+                s -= a if q[-1] & 15 == t[-1] & 15 else -b
+            else:
+                continue
+        else:
+            out["through"] += 1
+        if s != sc:
+            fail(k, "score", f"replayed {s}, reported {sc}: {cig}")
     return out

@@ -337,3 +337,277 @@ def test_ksw(engine, monkeypatch, form, alphabet, sc):
             assert sc[2] < 0 and (r["level"] == 2).all()
     _exact(engine.align_host(b, G.make_params(**kw), seed_scores=seed), ref, ("score", "q_end", "t_end"),
            f"KSW {form} {sc} {alphabet}")
+
+
+# ----------------------------------------------------- reverse / complement ----
+# Per-pair q_ops / t_ops (0 forward, 1 reverse, 2 complement, 3 both) on every kernel path,
+# against the independent functions run on independent.apply_ops(batch): the op model is
+# written in base space from pack_rc_seqs.h, not from the engine's or the oracle's word-swap
+# loop.  Ops also switch the 16-bit wavefront kernels to their packed-load form, which the
+# plan name does not show; so every test runs its batch once more with all ops 0 passed as
+# arrays (the packed path: has_ops tests the pointers), which must equal the run without op
+# arrays on every field.  That tells a packed-load bug from an op bug.
+OPS_EDGES_N = ("edges", b"ACGTN")
+OPS_EDGES_ODD = ("edges", helpers.OPS_ODD_ALPHABET)
+OPS_FLAG = ("flagship", b"ACGT")
+OPS_FLAG_N = ("flagship", b"ACGTN")
+END_FIELDS = ("score", "q_end", "t_end")
+
+
+def _ops_plan(kw, c, *families):
+    return _plan(kw, (0, int(c["b"].q_lens.max()), 0, int(c["b"].t_lens.max())), *families)
+
+
+def _ops_run(engine, c, kw, ref, fields, what, tb=False, **extra):
+    """The run with ops against ref, and the all-zero-ops run against the run without ops."""
+    p = G.make_params(**kw)
+    b = c["b"]
+    g = engine.align_host(b, p, q_ops=c["qo"], t_ops=c["to"], **extra)
+    _exact(g, ref, fields, what)
+    zero = np.zeros(b.n, np.uint8)
+    gz = engine.align_host(b, p, q_ops=zero, t_ops=zero, **extra)
+    gn = engine.align_host(b, p, **extra)
+    _exact(gz, gn, G.OUT_FIELDS + (("n_ops",) if tb else ()), what + ", ops all 0 against no ops:")
+    if tb:
+        # CIGAR bytes of the slots that hold their own CIGAR; a CIGAR longer than its slot runs
+        # into the next one, where two threads write the same bytes in no fixed order (Q14)
+        keep = helpers.cigar_slots_kept(b.q_offsets, b.q_lens, gn["n_ops"])
+        for k in np.flatnonzero(keep):
+            lo, m = int(b.q_offsets[k]), int(gn["n_ops"][k])
+            assert np.array_equal(gz["cigar"][lo:lo + m], gn["cigar"][lo:lo + m]), f"{what}, ops all 0 against no ops: CIGAR of pair {k}"
+    return g, gn
+
+
+def _ops_ref(case, name, fn):
+    return helpers.ops_ref(*case, name, fn)
+
+
+@pytest.mark.parametrize("case", [OPS_EDGES_N, OPS_EDGES_ODD, OPS_FLAG, OPS_FLAG_N], ids=lambda c: c[0] + "-" + c[1].decode())
+def test_ops_local_and_second_best(engine, case):
+    c = helpers.ops_case(*case)
+    for sc in SCORES:
+        ref = _ops_ref(case, ("local2", sc), lambda c: I.local(c["ob"], *sc, second=True))
+        kw = dict(algo=G.LOCAL, **_kw(sc))
+        _ops_plan(kw, c, "wavefront16_local")
+        _ops_run(engine, c, kw, ref, END_FIELDS, f"LOCAL ops {case} {sc}")
+        kw["second_best"] = 1
+        _ops_plan(kw, c, "local16_second")
+        _ops_run(engine, c, kw, ref, END_FIELDS + ("score2", "q_end2", "t_end2"), f"LOCAL second ops {case} {sc}")
+
+
+@pytest.mark.parametrize("case", [OPS_EDGES_N, OPS_EDGES_ODD, OPS_FLAG, OPS_FLAG_N], ids=lambda c: c[0] + "-" + c[1].decode())
+def test_ops_global(engine, case):
+    c = helpers.ops_case(*case)
+    for sc in SCORES:
+        kw = dict(algo=G.GLOBAL, **_kw(sc))
+        _ops_plan(kw, c, "wavefront16_global_G")
+        ref = _ops_ref(case, ("global", sc), lambda c: I.global_(c["ob"], *sc))
+        _ops_run(engine, c, kw, ref, ("score",), f"GLOBAL ops {case} {sc}")
+
+
+@pytest.mark.parametrize("head,tail", [(G.TARGET, G.TARGET), (G.NONE, G.TARGET), (G.QUERY, G.QUERY), (G.TARGET, G.QUERY),
+                                       (G.TARGET, G.BOTH), (G.NONE, G.BOTH), (G.TARGET, G.NONE), (G.QUERY, G.NONE)])
+def test_ops_semiglobal(engine, head, tail):
+    """SEMI_GLOBAL (the kernel runs transposed: the op-transformed target is the lanes' side).
+    Tail NONE is the constant answer: ops must neither change it nor fault."""
+    for case in (OPS_EDGES_N, OPS_FLAG):
+        c = helpers.ops_case(*case)
+        for sc in SCORES:
+            kw = dict(algo=G.SEMI_GLOBAL, head=head, tail=tail, **_kw(sc))
+            _ops_plan(kw, c, *SEMI_FAMILY[tail])
+            ref = _ops_ref(case, ("semi", head, tail, sc), lambda c: I.semi(c["ob"], head, tail, *sc))
+            g, gn = _ops_run(engine, c, kw, ref, END_FIELDS, f"SEMI ops {head}/{tail} {case} {sc}")
+            if tail == G.NONE:
+                _exact(g, gn, G.OUT_FIELDS, "SEMI tail NONE with ops against no ops")
+
+
+@pytest.mark.parametrize("head", [G.TARGET, G.NONE])
+def test_ops_semiglobal_with_start(engine, head):
+    """SEMI_GLOBAL WITH_START, tail TARGET: score and ends against independent.semi on the
+    transformed batch; independent has no model of the SEMI reverse pass, so the two start
+    fields are held against the oracle run with the same ops."""
+    for case in (OPS_EDGES_N, OPS_FLAG):
+        c = helpers.ops_case(*case)
+        for sc in SCORES:
+            kw = dict(algo=G.SEMI_GLOBAL, head=head, tail=G.TARGET, start_pos=G.WITH_START, **_kw(sc))
+            _ops_plan(kw, c, "wavefront16_semi_start")
+            ref = _ops_ref(case, ("semi", head, G.TARGET, sc), lambda c: I.semi(c["ob"], head, G.TARGET, *sc))
+            g, _ = _ops_run(engine, c, kw, ref, END_FIELDS, f"SEMI WITH_START ops {head} {case} {sc}")
+            _exact(g, O.align(c["b"], O.make_params(**kw), q_ops=c["qo"], t_ops=c["to"]), ("q_start", "t_start"),
+                   f"SEMI WITH_START ops {head} {case} {sc} (oracle)")
+
+
+@pytest.mark.parametrize("k_band", [4, 16])
+def test_ops_banded(engine, k_band):
+    for case in (OPS_EDGES_N, OPS_FLAG):
+        c = helpers.ops_case(*case)
+        for sc in SCORES:
+            kw = dict(algo=G.BANDED, k_band=k_band, **_kw(sc))
+            _ops_plan(kw, c, "banded16")
+            ref = _ops_ref(case, ("banded", k_band, sc), lambda c: I.banded(c["ob"], k_band, *sc))
+            _ops_run(engine, c, kw, ref, END_FIELDS, f"BANDED {k_band} ops {case} {sc}")
+
+
+_CODE_LETTER = bytes(b"NANCTNNGNNNNNNNN")        # 1 A, 3 C, 4 T, 7 G; anything else stands as N
+
+
+def _ops_seeds(n):
+    return np.random.default_rng(0x5EED).integers(0, 41, n).astype(np.uint32)
+
+
+@pytest.mark.parametrize("form,env", [("ksw16_64", {}), ("level0_lds", {"GASALX_KSW16": "0"})])
+def test_ops_ksw(engine, monkeypatch, form, env):
+    """KSW with ops on the 16-bit form and on the generic form, forced as test_ksw forces them.
+    ksw16 takes a pair by its *op-transformed* query (A/C/G/T only): a reversed query whose
+    length is no multiple of 8 begins with pads and stays with the generic kernel, so the
+    routing is asserted from the transformed codes."""
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    case = ("edges", b"ACGT")
+    c = helpers.ops_case(*case)
+    b, ob = c["b"], c["ob"]
+    seed = _ops_seeds(b.n)
+    letters = lambda data, offs, lens: [bytes(data[int(o):int(o) + int(n)]).translate(_CODE_LETTER + bytes(240))
+                                        for o, n in zip(offs, lens)]
+    for sc in SCORES:
+        kw = dict(algo=G.KSW, **_kw(sc))
+        assert G.describe_plan(G.make_params(**kw), int(b.q_lens.max()), int(b.t_lens.max())) == "generic_ksw"
+        r = helpers.ksw_routing(letters(ob.q_data, ob.q_offsets, ob.q_lens), letters(ob.t_data, ob.t_offsets, ob.t_lens),
+                                seed, sc, env)
+        if form == "ksw16_64":
+            assert r["inst"] == 64 and b.n // 4 <= r["taken"].sum() < b.n, int(r["taken"].sum())
+            assert r["taken"][(c["qo"] != 0) | (c["to"] != 0)].sum() >= b.n // 8
+        else:
+            assert not r["taken"].any() and (r["level"] == 0).all() and r["tpb"] == 256
+        ref = _ops_ref(case, ("ksw", sc), lambda c: I.ksw(c["ob"], seed, *sc))
+        _ops_run(engine, c, kw, ref, END_FIELDS, f"KSW {form} ops {sc}", seed_scores=seed)
+
+
+@pytest.mark.parametrize("case", [OPS_EDGES_N, OPS_EDGES_ODD, OPS_FLAG, OPS_FLAG_N], ids=lambda c: c[0] + "-" + c[1].decode())
+def test_ops_local_with_start(engine, case):
+    """The WITH_START reverse pass: reversed loads of packed words that the op already reversed."""
+    c = helpers.ops_case(*case)
+    for sc in SCORES:
+        kw = dict(algo=G.LOCAL, start_pos=G.WITH_START, **_kw(sc))
+        _ops_plan(kw, c, "wavefront16_local_start")
+        fwd = _ops_ref(case, ("local2", sc), lambda c: I.local(c["ob"], *sc, second=True))
+        st = _ops_ref(case, ("local_start", sc), lambda c: I.local_start(c["ob"], *sc, fwd=fwd))
+        ref = dict(fwd, **st)
+        _ops_run(engine, c, kw, ref, END_FIELDS + ("q_start", "t_start"), f"LOCAL WITH_START ops {case} {sc}")
+
+
+@pytest.mark.parametrize("case", [OPS_EDGES_N, OPS_EDGES_ODD, OPS_FLAG], ids=lambda c: c[0] + "-" + c[1].decode())
+def test_ops_global_tb_replay(engine, case):
+    """GLOBAL + traceback with ops: the GPU's CIGARs replayed over the op-transformed slots
+    (independent.replay_global_slots: the walk starts at the pad cell, whose codes are real
+    bases after a reverse), the score against independent.global_()."""
+    c = helpers.ops_case(*case)
+    b = c["b"]
+    for sc in SCORES:
+        kw = dict(algo=G.GLOBAL, start_pos=G.WITH_TB, **_kw(sc))
+        _ops_plan(kw, c, "wavefront16_global_tb")
+        ref = _ops_ref(case, ("global", sc), lambda c: I.global_(c["ob"], *sc))
+        g, _ = _ops_run(engine, c, kw, ref, ("score",), f"GLOBAL+TB ops {case} {sc}", tb=True)
+        keep = helpers.cigar_slots_kept(b.q_offsets, b.q_lens, g["n_ops"])
+        assert 1 - keep.mean() <= 0.04
+        st = I.replay_global_slots(c["ob"], g, sc, G.decode_cigar, keep)
+        assert not st["failures"], (len(st["failures"]), st["failures"][:3])
+        assert st["checked"] == keep.sum() and st["through"] >= keep.sum() // 2
+
+
+@pytest.mark.parametrize("case,sc,family", [
+    (OPS_EDGES_ODD, (1, 4, 6, 1), "wavefront16_local_tb"),
+    (OPS_EDGES_N, (1, 4, 6, 1), "wavefront16_local_tb"),
+    (OPS_FLAG, (1, 4, 6, 1), "wavefront16_local_tb"),
+    (OPS_FLAG, (2, 3, 5, 2), "wavefront_local_tb_keys"),
+], ids=["edges-odd", "edges-N", "flagship", "flagship-int32"])
+def test_ops_local_tb_replay_and_rectangle(engine, case, sc, family):
+    """LOCAL + traceback with ops: CIGAR replay over the transformed slots (lengths, M/X labels
+    against the post-op codes, the moved pads included), path score == score ==
+    independent.local(), and the rectangle from start to end worth `score` by global_textbook."""
+    c = helpers.ops_case(*case)
+    b = c["b"]
+    kw = dict(algo=G.LOCAL, start_pos=G.WITH_TB, **_kw(sc))
+    _ops_plan(kw, c, family)
+    ref = _ops_ref(case, ("local2", sc), lambda c: I.local(c["ob"], *sc, second=True))
+    g, _ = _ops_run(engine, c, kw, ref, END_FIELDS, f"LOCAL+TB ops {case} {sc}", tb=True)
+    keep = helpers.cigar_slots_kept(b.q_offsets, b.q_lens, g["n_ops"])
+    assert 1 - keep.mean() <= 0.02
+    st = I.replay_batch(c["oq"], c["ot"], b, g, sc, I.LOCAL_MODE, G.decode_cigar, keep)
+    assert not st["failures"], (len(st["failures"]), st["failures"][:3])
+    assert st["stepped"] == 0 and st["checked"] >= keep.sum() * 9 // 10
+    if case != OPS_EDGES_N:
+        # the moved pads carry the N code: alignments that run into them are on the path
+        assert st["n_path"] <= keep.sum() // 10
+
+
+@pytest.mark.parametrize("algo", [G.LOCAL, G.GLOBAL, G.SEMI_GLOBAL])
+def test_ops_int32_kernels(engine, monkeypatch, algo):
+    """The int32 wavefront kernels (GASALX_PACKED16=0, read per call) on the packed workspace."""
+    monkeypatch.setenv("GASALX_PACKED16", "0")
+    for case in (OPS_EDGES_N, OPS_FLAG):
+        c = helpers.ops_case(*case)
+        for sc in SCORES:
+            kw = dict(algo=algo, **_kw(sc))
+            _ops_plan(kw, c, "wavefront_")
+            if algo == G.LOCAL:
+                ref = _ops_ref(case, ("local2", sc), lambda c: I.local(c["ob"], *sc, second=True))
+            elif algo == G.GLOBAL:
+                ref = _ops_ref(case, ("global", sc), lambda c: I.global_(c["ob"], *sc))
+            else:
+                ref = _ops_ref(case, ("semi", G.TARGET, G.TARGET, sc), lambda c: I.semi(c["ob"], G.TARGET, G.TARGET, *sc))
+            _ops_run(engine, c, kw, ref, ("score",) if algo == G.GLOBAL else END_FIELDS, f"int32 {algo} ops {case} {sc}")
+
+
+def test_ops_generic_thread_per_pair(engine):
+    """One generic thread-per-pair plan: SEMI_GLOBAL with second_best = 1, its first-best
+    fields against independent.semi."""
+    case = OPS_EDGES_N
+    c = helpers.ops_case(*case)
+    for head, tail in ((G.TARGET, G.TARGET), (G.QUERY, G.BOTH)):
+        for sc in SCORES:
+            kw = dict(algo=G.SEMI_GLOBAL, head=head, tail=tail, second_best=1, **_kw(sc))
+            _ops_plan(kw, c, "generic_semi")
+            ref = _ops_ref(case, ("semi", head, tail, sc), lambda c: I.semi(c["ob"], head, tail, *sc))
+            _ops_run(engine, c, kw, ref, END_FIELDS, f"generic SEMI ops {head}/{tail} {sc}")
+
+
+def _pack_codes(codes):
+    """4-bit codes, eight per word, first in bits 31:28, as the bytes of the words."""
+    w = (codes.reshape(-1, 8).astype(np.uint32) << (28 - 4 * np.arange(8, dtype=np.uint32))).sum(axis=1, dtype=np.uint32)
+    return w.view(np.uint8)
+
+
+def test_ops_packed_input(engine):
+    """is_packed = 1 together with ops: the input packed with orc_pack as test_packed_input
+    does; scores and ends against independent on the ASCII batch.  With start_pos = WITH_TB
+    and a CIGAR buffer the reference's packed buffer aliases the unpacked one, so the buffer
+    begins with the op-transformed packed query words (SEMI_GLOBAL: no walk writes over them)."""
+    import ctypes
+    case = OPS_EDGES_N
+    c = helpers.ops_case(*case)
+    b, ob = c["b"], c["ob"]
+    qd = np.zeros(b.q_bytes, np.uint8); td = np.zeros(b.t_bytes, np.uint8)
+    pq = np.zeros(b.q_bytes // 8, np.uint32); pt = np.zeros(b.t_bytes // 8, np.uint32)
+    O.lib().orc_pack(O._ptr(b.q_data), ctypes.c_uint32(b.q_bytes), O._ptr(pq))
+    O.lib().orc_pack(O._ptr(b.t_data), ctypes.c_uint32(b.t_bytes), O._ptr(pt))
+    qd[:b.q_bytes // 2] = pq.view(np.uint8); td[:b.t_bytes // 2] = pt.view(np.uint8)
+    assert np.array_equal(qd[:b.q_bytes // 2], _pack_codes(b.q_data & 15))
+    cp = dict(c, b=G.Batch(qd, b.q_offsets, b.q_lens, td, b.t_offsets, b.t_lens))
+    sc = SCORES[0]
+    kw = dict(algo=G.LOCAL, is_packed=1, **_kw(sc))
+    _ops_plan(kw, c, "wavefront16_local")
+    ref = _ops_ref(case, ("local2", sc), lambda c: I.local(c["ob"], *sc, second=True))
+    _ops_run(engine, cp, kw, ref, END_FIELDS, "is_packed LOCAL ops")
+    kw = dict(algo=G.GLOBAL, is_packed=1, **_kw(sc))
+    _ops_run(engine, cp, kw, _ops_ref(case, ("global", sc), lambda c: I.global_(c["ob"], *sc)), ("score",), "is_packed GLOBAL ops")
+    kw = dict(algo=G.SEMI_GLOBAL, start_pos=G.WITH_TB, is_packed=1, **_kw(sc))
+    _ops_plan(kw, c, "wavefront_semi_keys_G")
+    ref = _ops_ref(case, ("semi", G.TARGET, G.TARGET, sc), lambda c: I.semi(c["ob"], G.TARGET, G.TARGET, *sc))
+    g = engine.align_host(cp["b"], G.make_params(**kw), q_ops=c["qo"], t_ops=c["to"])
+    _exact(g, ref, END_FIELDS, "is_packed SEMI WITH_TB ops")
+    want = _pack_codes(ob.q_data)
+    assert not np.array_equal(want, qd[:b.q_bytes // 2])
+    assert np.array_equal(g["cigar"][:b.q_bytes // 2], want), "the CIGAR buffer must begin with the op-transformed packed query"
+    assert np.array_equal(g["cigar"][b.q_bytes // 2:], qd[b.q_bytes // 2:])
+    assert np.array_equal(g["n_ops"], b.q_lens)

@@ -80,6 +80,31 @@ def test_multi_align_traceback_and_start():
     m.close()
 
 
+def test_multi_align_ops_follow_their_shard(engine):
+    # q_ops / t_ops are split with the pairs (multi.cpp: at(hb->q_ops, s)): all 0 in the first
+    # quarter and a repeating 1, 2, 3 pattern after it, so a shard that read the ops from pair 0
+    # would answer differently; bit-exact against one engine over the whole batch
+    n = 20_000
+    b = G.Batch.synth(2, n, 0x5EED0002)
+    i = np.arange(n)
+    qo = np.where(i < n // 4, 0, 1 + i % 3).astype(np.uint8)
+    to = np.where(i < n // 4, 0, 3 - i % 3).astype(np.uint8)
+    (s0, e0), (s1, e1) = G.shard_bounds(b.q_lens, b.t_lens, 2)
+    assert s0 == 0 and e0 == s1 and e1 == n and n // 4 < s1
+    assert not np.array_equal(qo[s1:s1 + 64], qo[:64])
+    one = None
+    for kw in (dict(algo=G.LOCAL), dict(algo=G.LOCAL, start_pos=G.WITH_START), dict(algo=G.GLOBAL)):
+        m = G.Multi([0, 0])
+        g = m.align_host(b, G.make_params(**kw), q_ops=qo, t_ops=to)
+        m.close()
+        one = engine.align_host(b, G.make_params(**kw), q_ops=qo, t_ops=to)
+        _check_all(g, one, G.OUT_FIELDS)
+        plain = engine.align_host(b, G.make_params(**kw))
+        assert (one["score"][s1:] != plain["score"][s1:]).mean() > 0.5      # the ops decide the answers
+    o = O.align(b.slice(s1 - 500, s1 + 500), O.make_params(algo=G.GLOBAL), q_ops=qo[s1 - 500:s1 + 500], t_ops=to[s1 - 500:s1 + 500])
+    assert np.array_equal(one["score"][s1 - 500:s1 + 500], o["score"])
+
+
 def test_multi_align_one_to_many_traceback_rejected():
     # WITH_TB with shards sharing query bytes (every pair uses query 0) is refused, not raced
     b = G.Batch.synth(3, 64, 0x5EED0003)

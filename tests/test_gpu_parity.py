@@ -645,6 +645,32 @@ def test_packed_input_pipelined_host_path(engine, algo, kw):
         assert np.array_equal(g1[f][:4000], o[f][:4000]), f
 
 
+@pytest.mark.parametrize("algo,kw", [(G.LOCAL, {}), (G.SEMI_GLOBAL, dict(head=G.TARGET, tail=G.TARGET))])
+def test_ops_pipelined_host_path(engine, algo, kw):
+    """q_ops / t_ops through the two-stream host pipeline, which copies each chunk's ops from
+    q_ops + i0 (capi.cpp): 40 000 pairs run as chunks of max(16384, ceil(n / 8)) pairs.  The ops
+    are all 0 up to pair 20 000 and a repeating 1, 2, 3 pattern after it, so a chunk that read
+    another chunk's ops (or none) answers differently on either side of each chunk boundary.
+    Pairs around both boundaries, around the change of pattern, and the last pairs against the
+    oracle (whose op handling tests/test_independent.py holds against independent.apply_ops)."""
+    n = 40000
+    b = G.Batch.synth(4 if algo == G.SEMI_GLOBAL else 2, n, 0x5EED0002)
+    chunk = max(16384, (n + 7) // 8)
+    assert n >= 2 * chunk and n % chunk
+    i = np.arange(n)
+    qo = np.where(i < 20000, 0, 1 + i % 3).astype(np.uint8)
+    to = np.where(i < 20000, 0, 3 - i % 3).astype(np.uint8)
+    g = engine.align_host(b, G.make_params(algo=algo, **kw), q_ops=qo, t_ops=to)
+    plain = engine.align_host(b, G.make_params(algo=algo, **kw))
+    for s, e in ((chunk - 1000, chunk + 1000), (19500, 20500), (2 * chunk - 1000, 2 * chunk + 1000), (n - 500, n)):
+        o = O.align(b.slice(s, e), O.make_params(algo=algo, **kw), q_ops=qo[s:e], t_ops=to[s:e])
+        for f in ("score", "q_end", "t_end"):
+            bad = np.flatnonzero(g[f][s:e] != o[f])
+            assert bad.size == 0, f"{f}: {bad.size} differ in [{s}, {e}), first pair {s + bad[0]}"
+        if s >= 20000:      # the ops decide these answers
+            assert (g["score"][s:e] != plain["score"][s:e]).mean() > 0.5
+
+
 # ----------------------------------------------------- full-size configs ----
 def test_plan_is_wavefront_for_bench_configs():
     assert G.describe_plan(G.make_params(algo=G.LOCAL), 150, 150).startswith("wavefront16_local")

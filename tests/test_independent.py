@@ -313,3 +313,152 @@ def test_ksw_constructed_rules(name):
         assert np.all(r["q_end"][(r["margin"] == 4) & (r["score"] > 4)] == b.q_lens[(r["margin"] == 4) & (r["score"] > 4)])
     if name == "seed0":
         assert not r["score"].any() and not r["q_end"].any() and not r["t_end"].any()
+
+
+# --------------------------------------------------- reverse / complement ----
+OPS_FIELDS = ("score", "q_end", "t_end")
+
+
+def _nibbles(words):
+    """Packed words as one code per base, first base in bits 31:28 (the pack kernel's order)."""
+    return ((words[:, None] >> (28 - 4 * np.arange(8, dtype=np.uint32))[None, :]) & 15).astype(np.uint8).ravel()
+
+
+@pytest.mark.parametrize("kind,alphabet", helpers.OPS_CASES)
+def test_ops_slots_against_apply_ops(kind, alphabet):
+    """orc_pack, then orc_revcomp_one pair by pair as orc_aln_batch calls it, against
+    independent.apply_ops nibble for nibble.  The edge batch holds every op on sequences of one
+    to five words; its pair 0 reverses a one-word query at word 0 (the read of the word before
+    the sequence takes the base + idx < 0 guard), and later one-word pairs read a
+    predecessor's last word whose nibbles are all non-zero."""
+    import ctypes
+    c = helpers.ops_case(kind, alphabet)
+    b, qo, to = c["b"], c["qo"], c["to"]
+    L = O.lib()
+    L.orc_revcomp_one.restype = None
+    for data, offs, lens, ops, other, want in ((b.q_data, b.q_offsets, b.q_lens, qo, to, c["ob"].q_data),
+                                               (b.t_data, b.t_offsets, b.t_lens, to, qo, c["ob"].t_data)):
+        w = np.zeros(len(data) // 8, np.uint32)
+        L.orc_pack(O._ptr(data), ctypes.c_uint32(len(data)), O._ptr(w))
+        plain = _nibbles(w)
+        assert np.array_equal(plain, data & 15)
+        for k in range(b.n):
+            if ops[k] == 0 and other[k] == 0:
+                continue
+            L.orc_revcomp_one(O._ptr(w), ctypes.c_uint32(int(offs[k]) >> 3), ctypes.c_uint32(int(lens[k])),
+                              ctypes.c_uint8(int(ops[k])), ctypes.c_int32(0x4E))
+        got = _nibbles(w)
+        bad = np.flatnonzero(got != want)
+        assert bad.size == 0, f"{bad.size} nibbles differ, first at byte {bad[0]}: oracle {got[bad[0]]} apply_ops {want[bad[0]]}"
+        moved = np.array([not np.array_equal(plain[int(o):int(o) + 8], want[int(o):int(o) + 8]) for o in offs])
+        assert moved[ops != 0].mean() > 0.5
+    if kind == "edges":
+        words = (b.q_lens.astype(np.int64) + 7) // 8
+        for op in (1, 2, 3):
+            assert set(words[qo == op]) == {1, 2, 3, 4, 5}, op
+            assert set(((b.t_lens.astype(np.int64) + 7) // 8)[to == op]) == {1, 2, 3, 4, 5}, op
+        assert set(zip(qo.tolist(), to.tolist())) == {(x, y) for x in range(4) for y in range(4)}
+        assert qo[0] & 1 and b.q_offsets[0] == 0 and words[0] == 1
+        later = np.flatnonzero((qo & 1 == 1) & (words == 1) & (np.arange(b.n) > 0))
+        assert later.size >= 3
+        prev_last = np.array([b.q_data[int(b.q_offsets[k]) - 8:int(b.q_offsets[k])] for k in later])
+        assert np.all(prev_last & 15 != 0)
+        assert {int(x) % 8 for x in b.q_lens} == {0, 1, 7} and {int(x) % 8 for x in b.t_lens} == {0, 1, 7}
+    else:
+        assert b.n == 300 and b.q_lens.min() >= 140 and b.q_lens.max() <= 160
+    if alphabet == helpers.OPS_ODD_ALPHABET:
+        # bytes that are not A/C/G/T but carry a base's code: the complement must move them
+        odd = np.isin(b.q_data, np.frombuffer(b"SWDQswdq", np.uint8))
+        assert odd.sum() > 100 and np.all(np.isin(b.q_data[odd] & 15, [1, 3, 4, 7]))
+
+
+def test_apply_ops_by_hand():
+    # AACCC, reversed: the three pads move to the front (hand KAT 4); complement maps codes
+    # 1 <-> 4 and 3 <-> 7 and leaves the pad's 0xE and any other code alone
+    b = G.Batch.from_pairs([b"AACCC", b"ACGTNRYA"], [b"ACGTACGTA", b"T"])
+    r = I.apply_ops(b, [1, 2], [3, 0])
+    assert list(r.q_data[:8]) == [0xE, 0xE, 0xE, 3, 3, 3, 1, 1]
+    assert list(r.q_data[8:16]) == [4, 7, 3, 1, 0xE, 2, 9, 4]
+    assert list(r.t_data[:16]) == [0xE] * 7 + [4, 1, 3, 7, 4, 1, 3, 7, 4]
+    assert list(r.t_data[16:24]) == [4] + [0xE] * 7
+    # both ops 0: the pair is left alone whatever its neighbours do
+    r = I.apply_ops(b, [0, 3], [0, 3])
+    assert np.array_equal(r.q_data[:8], b.q_data[:8] & 15) and np.array_equal(r.t_data[:16], b.t_data[:16] & 15)
+    with pytest.raises(ValueError):
+        I.apply_ops(b, [1, 0], [0, 0], n_code=0xE)
+
+
+@pytest.mark.parametrize("kind,alphabet", helpers.OPS_CASES)
+def test_ops_batches_answers_depend_on_the_ops(kind, alphabet):
+    """The condition on the inputs: among the pairs with a nonzero op at least half have an
+    independent answer that differs from the same pair's answer without ops, for LOCAL,
+    GLOBAL (score) and SEMI_GLOBAL.  On the reference alone: if a batch falls short, the
+    batch changes (helpers.ops_batch), not the threshold."""
+    dep = helpers.ops_dependence(helpers.ops_case(kind, alphabet))
+    print(f"{kind} {alphabet.decode()}: answers that depend on the ops: {dep}")
+    for name, share in dep.items():
+        assert share >= 0.5, (name, share)
+
+
+def _ops_oracle(c, **kw):
+    return O.align(c["b"], O.make_params(**kw), q_ops=c["qo"], t_ops=c["to"])
+
+
+@pytest.mark.parametrize("sc", helpers.OPS_SCORES)
+@pytest.mark.parametrize("kind,alphabet", helpers.OPS_CASES)
+def test_ops_oracle_local_global(kind, alphabet, sc):
+    """O.align with ops against the independent functions on apply_ops(batch): LOCAL with and
+    without second best, GLOBAL."""
+    a, bb, o, e = sc
+    c = helpers.ops_case(kind, alphabet)
+    kw = dict(match=a, mismatch=bb, gap_open=o, gap_extend=e)
+    ref = I.local(c["ob"], a, bb, o, e, second=True)
+    _same(ref, _ops_oracle(c, algo=O.LOCAL, second_best=1, **kw), OPS_FIELDS + ("score2", "q_end2", "t_end2"))
+    _same(ref, _ops_oracle(c, algo=O.LOCAL, **kw), OPS_FIELDS)
+    _same(I.global_(c["ob"], a, bb, o, e), _ops_oracle(c, algo=O.GLOBAL, **kw), ("score",))
+
+
+@pytest.mark.parametrize("head,tail", [(O.TARGET, O.TARGET), (O.NONE, O.TARGET), (O.QUERY, O.QUERY), (O.TARGET, O.BOTH),
+                                       (O.BOTH, O.QUERY), (O.NONE, O.BOTH)])
+@pytest.mark.parametrize("kind,alphabet", [helpers.OPS_CASES[1], helpers.OPS_CASES[2], helpers.OPS_CASES[3]])
+def test_ops_oracle_semiglobal(kind, alphabet, head, tail):
+    c = helpers.ops_case(kind, alphabet)
+    for a, bb, o, e in helpers.OPS_SCORES:
+        ref = _ops_oracle(c, algo=O.SEMI_GLOBAL, head=head, tail=tail, match=a, mismatch=bb, gap_open=o, gap_extend=e)
+        _same(I.semi(c["ob"], head, tail, a, bb, o, e), ref, OPS_FIELDS)
+
+
+@pytest.mark.parametrize("k_band", [4, 16])
+@pytest.mark.parametrize("kind,alphabet", [helpers.OPS_CASES[1], helpers.OPS_CASES[3]])
+def test_ops_oracle_banded(kind, alphabet, k_band):
+    c = helpers.ops_case(kind, alphabet)
+    for a, bb, o, e in helpers.OPS_SCORES:
+        ref = _ops_oracle(c, algo=O.BANDED, k_band=k_band, match=a, mismatch=bb, gap_open=o, gap_extend=e)
+        _same(I.banded(c["ob"], k_band, a, bb, o, e), ref, OPS_FIELDS)
+
+
+def ops_seeds(n):
+    return np.random.default_rng(0x5EED).integers(0, 41, n).astype(np.uint32)
+
+
+@pytest.mark.parametrize("kind,alphabet", [helpers.OPS_CASES[1], helpers.OPS_CASES[3]])
+def test_ops_oracle_ksw(kind, alphabet):
+    c = helpers.ops_case(kind, alphabet)
+    seed = ops_seeds(c["b"].n)
+    for a, bb, o, e in helpers.OPS_SCORES:
+        ref = O.align(c["b"], O.make_params(algo=O.KSW, match=a, mismatch=bb, gap_open=o, gap_extend=e),
+                      q_ops=c["qo"], t_ops=c["to"], seed_scores=seed)
+        _same(I.ksw(c["ob"], seed, a, bb, o, e), ref, OPS_FIELDS)
+
+
+@pytest.mark.parametrize("sc", helpers.OPS_SCORES)
+@pytest.mark.parametrize("kind,alphabet", helpers.OPS_CASES)
+def test_ops_oracle_local_with_start(kind, alphabet, sc):
+    """The WITH_START reverse pass over op-transformed slots: reversed loads of words that the
+    op already reversed, with the moved pads inside the word-aligned prefixes."""
+    a, bb, o, e = sc
+    c = helpers.ops_case(kind, alphabet)
+    r = _ops_oracle(c, algo=O.LOCAL, start_pos=O.WITH_START, match=a, mismatch=bb, gap_open=o, gap_extend=e)
+    fwd = I.local(c["ob"], a, bb, o, e)
+    _same(fwd, r, OPS_FIELDS)
+    _same(I.local_start(c["ob"], a, bb, o, e, fwd=fwd), r, ("q_start", "t_start"))
