@@ -5,8 +5,11 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cstdlib>
 #include <string>
+#include <type_traits>
+#include <utility>
 
 #include "engine.hpp"
 #include "nvbio.hpp"
@@ -22,137 +25,246 @@ namespace {
 struct NvShape { int G, R; };
 // the smallest G*R >= the longest pattern: 150-bp reads take (8, 19), 152 rows
 constexpr NvShape kNvShapes[] = {{8, 8}, {8, 12}, {8, 16}, {8, 19}, {8, 24}, {16, 16}, {16, 20}, {32, 16}, {64, 16}};
+constexpr size_t kNvShapeCount = sizeof(kNvShapes) / sizeof(kNvShapes[0]);
+
+// ---- run-time values as template arguments: every kernel lookup goes through these ----
+template <int V> using ic = std::integral_constant<int, V>;
+
+// f(ic<ALN>, ic<TYPE>, bool_constant<FLAG>) for the aligner kind (Gotoh, or linear gaps: ED runs
+// as SW), the alignment type and one flag
+template <class F>
+auto nv_static(int aligner, int type, bool flag, F f) {
+    auto by_type = [&](auto a, auto fl) {
+        return type == NV_GLOBAL ? f(a, ic<NV_GLOBAL>{}, fl)
+             : type == NV_SEMI ? f(a, ic<NV_SEMI>{}, fl) : f(a, ic<NV_LOCAL>{}, fl);
+    };
+    auto by_aligner = [&](auto fl) {
+        return aligner == NV_GOTOH ? by_type(ic<NV_GOTOH>{}, fl) : by_type(ic<NV_SW>{}, fl);
+    };
+    return flag ? by_aligner(std::true_type{}) : by_aligner(std::false_type{});
+}
+template <class F, size_t... I>
+auto nv_shape_table(F f, std::index_sequence<I...>) {
+    return std::array{f(ic<kNvShapes[I].G>{}, ic<kNvShapes[I].R>{})...};
+}
+// f(ic<ALN>, ic<TYPE>, bool_constant<FLAG>, ic<G>, ic<R>) at shape kNvShapes[shape].  The table is
+// built from the shape list itself, so every shape the planner can choose has its instance of
+// every kernel family: no lookup returns null.
+template <class F>
+auto nv_instance(int aligner, int type, bool flag, int shape, F f) {
+    return nv_static(aligner, type, flag, [&](auto a, auto t, auto fl) {
+        return nv_shape_table([&](auto g, auto r) { return f(a, t, fl, g, r); },
+                              std::make_index_sequence<kNvShapeCount>{})[shape];
+    });
+}
 
 using NvFn = void (*)(NvArgs);
-
-template <int ALN, int TYPE, bool MASK>
-NvFn nv_pick(int G, int R) {
-#define GX_CASE(g, r) if (G == g && R == r) return &nv_kernel<ALN, TYPE, g, r, MASK>;
-    GX_CASE(8, 8) GX_CASE(8, 12) GX_CASE(8, 16) GX_CASE(8, 19) GX_CASE(8, 24) GX_CASE(16, 16) GX_CASE(16, 20)
-    GX_CASE(32, 16) GX_CASE(64, 16)
-#undef GX_CASE
-    return nullptr;
-}
-
-// the sink-tracking form (nvbio_sink.hpp): one instance per aligner kind, type and shape
-using NvSinkFn = void (*)(NvSinkArgs);
-template <int ALN, int TYPE>
-NvSinkFn nv_sink_pick(int G, int R) {
-#define GX_CASE(g, r) if (G == g && R == r) return &nv_sink_kernel<ALN, TYPE, g, r>;
-    GX_CASE(8, 8) GX_CASE(8, 12) GX_CASE(8, 16) GX_CASE(8, 19) GX_CASE(8, 24) GX_CASE(16, 16) GX_CASE(16, 20)
-    GX_CASE(32, 16) GX_CASE(64, 16)
-#undef GX_CASE
-    return nullptr;
-}
-template <int ALN>
-NvSinkFn nv_sink_lookup_t(int type, int G, int R) {
-    return type == NV_GLOBAL ? nv_sink_pick<ALN, NV_GLOBAL>(G, R)
-         : type == NV_SEMI ? nv_sink_pick<ALN, NV_SEMI>(G, R) : nv_sink_pick<ALN, NV_LOCAL>(G, R);
-}
-
-using Nv16SinkFn = void (*)(Nv16SinkArgs);
-template <int ALN, int TYPE, bool SHARED>
-Nv16SinkFn nv16_sink_pick(int G, int R) {
-#define GX_CASE(g, r) if (G == g && R == r) return &nv16_sink_kernel<ALN, TYPE, g, r, SHARED>;
-    GX_CASE(8, 8) GX_CASE(8, 12) GX_CASE(8, 16) GX_CASE(8, 19) GX_CASE(8, 24) GX_CASE(16, 16) GX_CASE(16, 20)
-    GX_CASE(32, 16) GX_CASE(64, 16)
-#undef GX_CASE
-    return nullptr;
-}
-template <int ALN, bool SHARED>
-Nv16SinkFn nv16_sink_lookup_t(int type, int G, int R) {
-    return type == NV_GLOBAL ? nv16_sink_pick<ALN, NV_GLOBAL, SHARED>(G, R)
-         : type == NV_SEMI ? nv16_sink_pick<ALN, NV_SEMI, SHARED>(G, R) : nv16_sink_pick<ALN, NV_LOCAL, SHARED>(G, R);
-}
-Nv16SinkFn nv16_sink_lookup(int aln, int type, bool shared, int G, int R) {
-    if (shared)
-        return aln == NV_GOTOH ? nv16_sink_lookup_t<NV_GOTOH, true>(type, G, R)
-                               : nv16_sink_lookup_t<NV_SW, true>(type, G, R);
-    return aln == NV_GOTOH ? nv16_sink_lookup_t<NV_GOTOH, false>(type, G, R) : nv16_sink_lookup_t<NV_SW, false>(type, G, R);
-}
-
 using Nv16Fn = void (*)(Nv16Args);
-template <int ALN, int TYPE, bool SHARED>
-Nv16Fn nv16_pick(int G, int R) {
-#define GX_CASE(g, r) if (G == g && R == r) return &nv16_kernel<ALN, TYPE, g, r, SHARED>;
-    GX_CASE(8, 8) GX_CASE(8, 12) GX_CASE(8, 16) GX_CASE(8, 19) GX_CASE(8, 24) GX_CASE(16, 16) GX_CASE(16, 20)
-    GX_CASE(32, 16) GX_CASE(64, 16)
-#undef GX_CASE
-    return nullptr;
+// the sink-tracking forms (nvbio_sink.hpp): one instance per score-only instance, MASK apart
+using NvSinkFn = void (*)(NvSinkArgs);
+using Nv16SinkFn = void (*)(Nv16SinkArgs);
+NvFn nv_lookup(int aligner, int type, bool mask, int shape) {   // MASK exists for LOCAL only
+    return nv_instance(aligner, type, mask, shape, [](auto a, auto t, auto m, auto g, auto r) -> NvFn {
+        return &nv_kernel<a, t, g, r, m && t == NV_LOCAL>; });
 }
-template <int ALN, bool SHARED>
-Nv16Fn nv16_lookup_t(int type, int G, int R) {
-    return type == NV_GLOBAL ? nv16_pick<ALN, NV_GLOBAL, SHARED>(G, R)
-         : type == NV_SEMI ? nv16_pick<ALN, NV_SEMI, SHARED>(G, R) : nv16_pick<ALN, NV_LOCAL, SHARED>(G, R);
+NvSinkFn nv_sink_lookup(int aligner, int type, int shape) {
+    return nv_instance(aligner, type, false, shape, [](auto a, auto t, auto, auto g, auto r) -> NvSinkFn {
+        return &nv_sink_kernel<a, t, g, r>; });
 }
-Nv16Fn nv16_lookup(int aln, int type, bool shared, int G, int R) {
-    if (shared)
-        return aln == NV_GOTOH ? nv16_lookup_t<NV_GOTOH, true>(type, G, R) : nv16_lookup_t<NV_SW, true>(type, G, R);
-    return aln == NV_GOTOH ? nv16_lookup_t<NV_GOTOH, false>(type, G, R) : nv16_lookup_t<NV_SW, false>(type, G, R);
+Nv16Fn nv16_lookup(int aligner, int type, bool shared, int shape) {
+    return nv_instance(aligner, type, shared, shape, [](auto a, auto t, auto s, auto g, auto r) -> Nv16Fn {
+        return &nv16_kernel<a, t, g, r, s>; });
 }
-// LDS of the packed kernel: one table per column of the shared text, or of every
-// pair's text (two pairs per lane group, 4 waves per block)
-uint32_t nv16_cols(bool shared, uint32_t max_t, int G) { return shared ? (max_t + G + 63u) & ~63u : (max_t + 3u) & ~3u; }
-size_t nv16_lds(bool shared, uint32_t max_t, int G) {
-    return (size_t)nv16_cols(shared, max_t, G) * 4 * (shared ? 1 : 4 * 2 * (64 / G));
+Nv16SinkFn nv16_sink_lookup(int aligner, int type, bool shared, int shape) {
+    return nv_instance(aligner, type, shared, shape, [](auto a, auto t, auto s, auto g, auto r) -> Nv16SinkFn {
+        return &nv16_sink_kernel<a, t, g, r, s>; });
 }
 
-// The packed kernel (nvbio16.hpp): 2-bit texts, gaps and (LOCAL) mismatches <= 0,
-// match - mismatch in a byte, and every value (bounded by (M + N + 2) * the largest
-// score magnitude) inside the 16-bit f16 window.  GASALX_NV16=0: int32 only.
-bool nv16_ok(int aligner, int type, int32_t match, int32_t mismatch, int32_t go, int32_t ge, int32_t del, int32_t ins,
-             bool shared_text, uint32_t text_bits, uint32_t max_p, uint32_t max_t, uint32_t *base) {
-    if (!env_flag("GASALX_NV16", true)) return false;
-    (void)shared_text;
-    if (text_bits != 2) return false;
-    if (match < mismatch || match - mismatch > 255) return false;
-    if (aligner == NV_GOTOH ? (go > 0 || ge > 0) : (del > 0 || ins > 0)) return false;
-    if (mismatch > 0 || mismatch < -255) return false;   // virtual rows score the byte |mismatch|
-    const int64_t mag = std::max<int64_t>({std::abs((int64_t)match), std::abs((int64_t)mismatch), std::abs((int64_t)go),
-                                           std::abs((int64_t)ge), std::abs((int64_t)del), std::abs((int64_t)ins), 1});
-    if (mag > 0x200) return false;   // a gap subtracted from NEG must not borrow across the halves
-    const int64_t vabs = ((int64_t)max_p + max_t + 2) * mag * 2;
-    if (aligner == NV_GOTOH && type != NV_LOCAL) {
-        // the drift frame (nvbio16.hpp FR): values + g*(r+c) + (go - ge) lie within the
-        // all-gap path below and the diagonal above; virtual rows (r >= -G*R, G*R <=
-        // 2*max_p + 64) fall by g per row, sink keys add up to g*max_t
-        const int64_t g = -(int64_t)ge, gr = 2 * (int64_t)max_p + 64;
-        const int64_t b = 0x400 + g * (gr + 2) + 4 * (std::abs((int64_t)go) + g) + 64;
-        const int64_t top = b + std::abs((int64_t)go - ge) + std::max<int64_t>(match, 0) * max_p +
-                            g * ((int64_t)max_p + 2 * (int64_t)max_t + 4) + 512;
-        if (top > 0x7BFF) return false;
-        *base = (uint32_t)b;
-        return true;
-    }
-    const int64_t b = 0x400 + 2 * (std::abs((int64_t)go) + std::abs((int64_t)ge) + std::abs((int64_t)del) +
-                                   std::abs((int64_t)ins)) + vabs + 64;
+// ---- the scheme, the kernel arguments, checks and the launch, each written once ----
+struct NvScheme { int32_t match, mismatch, go, ge, del, ins; };
+// ED runs as SW with EditDistanceSWScheme's scores (ed_utils.h:45-52, ed_banded_inl.h:63-78,
+// ed_inl.h:347-365); gap_open / gap_ext are passed on as given
+NvScheme nv_scheme(const gasalx_nv_aligner &al) {
+    if (al.aligner == NV_ED) return {0, -1, al.gap_open, al.gap_ext, -1, -1};
+    return {al.match, al.mismatch, al.gap_open, al.gap_ext, al.deletion, al.insertion};
+}
+// The largest score magnitude.  Not capi.cpp's nv_score_mag, which is 1 for ED: here an ED aligner's
+// gap_open / gap_ext count although no ED kernel reads them (tests/golden/nv_plan_names.json pins it).
+int64_t nv_score_mag(const NvScheme &s) {
+    return std::max<int64_t>({std::abs((int64_t)s.match), std::abs((int64_t)s.mismatch), std::abs((int64_t)s.go),
+                              std::abs((int64_t)s.ge), std::abs((int64_t)s.del), std::abs((int64_t)s.ins), 1});
+}
+int64_t nv_gap_sum(const NvScheme &s) {
+    return std::abs((int64_t)s.go) + std::abs((int64_t)s.ge) + std::abs((int64_t)s.del) + std::abs((int64_t)s.ins);
+}
+
+template <class Args, class = void> struct has_tbits : std::false_type {};
+template <class Args> struct has_tbits<Args, std::void_t<decltype(Args::tbits)>> : std::true_type {};
+// the string sets, the scheme and the pair count of any kernel argument struct (the packed
+// kernels' have no tbits: their texts are 2-bit)
+template <class Args>
+void nv_fill(Args &A, const gasalx_nv_strings &pat, const gasalx_nv_strings &txt, const NvScheme &s, uint32_t n) {
+    A.pw = pat.words; A.poff = pat.offsets; A.pbits = pat.bits; A.pbig = pat.big_endian;
+    A.tw = txt.words; A.toff = txt.offsets; A.tbig = txt.big_endian; A.tlen0 = txt.offsets ? 0 : txt.length;
+    if constexpr (has_tbits<Args>::value) A.tbits = txt.bits;
+    A.match = s.match; A.mismatch = s.mismatch; A.go = s.go; A.ge = s.ge; A.del = s.del; A.ins = s.ins;
+    A.n = n;
+}
+
+int nv_fail(int rc, const std::string &msg) { set_error(msg); return rc; }
+// Aligner, type, band (where there is one) and symbol bits, in the order every entry point checks
+// them; the traceback forms have a text of their own for the aligner and one for the type.
+int nv_check(const gasalx_nv_aligner &al, const char *aligner_msg, const char *type_msg, const uint32_t *band,
+             const gasalx_nv_strings &pat, const gasalx_nv_strings &txt) {
+    if (al.aligner < 0 || al.aligner > 2) return nv_fail(GASALX_EINVAL, aligner_msg);
+    if (al.type < 0 || al.type > 2) return nv_fail(GASALX_EINVAL, type_msg);
+    if (band && (*band < 2 || *band > 32)) return nv_fail(GASALX_EINVAL, "band length must be 2..32");
+    for (uint32_t b : {pat.bits, txt.bits})
+        if (b != 2 && b != 4 && b != 8) return nv_fail(GASALX_EINVAL, "symbol bits must be 2, 4 or 8");
+    return GASALX_OK;
+}
+int nv_check_ptrs(const gasalx_nv_strings &pat, const gasalx_nv_strings &txt, bool outputs) {
+    if (!pat.words || !pat.offsets || !txt.words || !outputs) return nv_fail(GASALX_EINVAL, "null argument");
+    return GASALX_OK;
+}
+
+int nv_launched(hipError_t e) { return e == hipSuccess ? GASALX_OK : nv_fail(GASALX_EDEVICE, hipGetErrorString(e)); }
+// 256-thread blocks; with dynamic LDS through launch_lds, without as a plain launch
+template <class Args>
+int launch_checked(void (*fn)(Args), uint32_t blocks, size_t lds, hipStream_t st, const Args &A) {
+    return nv_launched(launch_lds(fn, dim3(blocks), dim3(256), lds, st, A));
+}
+template <class Args>
+int launch_checked(void (*fn)(Args), uint32_t blocks, hipStream_t st, const Args &A) {
+    hipLaunchKernelGGL(fn, dim3(blocks), dim3(256), 0, st, A);
+    return nv_launched(hipGetLastError());
+}
+
+// ---- the packed kernels' 16-bit window ----
+// Values within +-vabs = span * mag * 2 of the stored zero `base`, and the gap scores below it,
+// inside f16's integer range (nvbio16.hpp, nvbanded.hpp).
+bool nv_f16_window(int64_t span, int64_t mag, int64_t gap_sum, uint32_t *base) {
+    const int64_t vabs = span * mag * 2;
+    const int64_t b = 0x400 + 2 * gap_sum + vabs + 64;
     if (b + vabs + 512 > 0x7BFF) return false;
     *base = (uint32_t)b;
     return true;
 }
 
-NvFn nv_lookup(bool gotoh, int type, bool mask, int G, int R) {
-    if (gotoh) {
-        if (type == NV_GLOBAL) return nv_pick<NV_GOTOH, NV_GLOBAL, false>(G, R);
-        if (type == NV_SEMI) return nv_pick<NV_GOTOH, NV_SEMI, false>(G, R);
-        return mask ? nv_pick<NV_GOTOH, NV_LOCAL, true>(G, R) : nv_pick<NV_GOTOH, NV_LOCAL, false>(G, R);
+// The packed kernel (nvbio16.hpp): 2-bit texts, gaps and mismatches <= 0, match - mismatch in a
+// byte, and every value (bounded by (M + N + 2) * the largest score magnitude) inside the 16-bit
+// f16 window.  GASALX_NV16=0: int32 only.
+bool nv16_ok(const NvScheme &s, bool gotoh, int type, uint32_t text_bits, uint32_t max_p, uint32_t max_t,
+             uint32_t *base) {
+    if (!env_flag("GASALX_NV16", true)) return false;
+    if (text_bits != 2) return false;
+    if (s.match < s.mismatch || s.match - s.mismatch > 255) return false;
+    // only the gap scores the aligner reads, and the mismatch: deliberately not nvb16_ok's rule (pinned)
+    if (gotoh ? (s.go > 0 || s.ge > 0) : (s.del > 0 || s.ins > 0)) return false;
+    if (s.mismatch > 0 || s.mismatch < -255) return false;   // virtual rows score the byte |mismatch|
+    const int64_t mag = nv_score_mag(s);
+    if (mag > 0x200) return false;   // a gap subtracted from NEG must not borrow across the halves
+    if (gotoh && type != NV_LOCAL) {
+        // the drift frame (nvbio16.hpp FR): values + g*(r+c) + (go - ge) lie within the
+        // all-gap path below and the diagonal above; virtual rows (r >= -G*R, G*R <=
+        // 2*max_p + 64) fall by g per row, sink keys add up to g*max_t
+        const int64_t g = -(int64_t)s.ge, gr = 2 * (int64_t)max_p + 64;
+        const int64_t b = 0x400 + g * (gr + 2) + 4 * (std::abs((int64_t)s.go) + g) + 64;
+        const int64_t top = b + std::abs((int64_t)s.go - s.ge) + std::max<int64_t>(s.match, 0) * max_p +
+                            g * ((int64_t)max_p + 2 * (int64_t)max_t + 4) + 512;
+        if (top > 0x7BFF) return false;
+        *base = (uint32_t)b;
+        return true;
     }
-    if (type == NV_GLOBAL) return nv_pick<NV_SW, NV_GLOBAL, false>(G, R);
-    if (type == NV_SEMI) return nv_pick<NV_SW, NV_SEMI, false>(G, R);
-    return mask ? nv_pick<NV_SW, NV_LOCAL, true>(G, R) : nv_pick<NV_SW, NV_LOCAL, false>(G, R);
+    return nv_f16_window((int64_t)max_p + max_t + 2, mag, nv_gap_sum(s), base);
 }
 
-// the lane-group shape for patterns up to max_p: the smallest G*R that covers them
-// whose text slots fit in LDS (one shared slot, or one per pair)
-const NvShape *nv_shape(uint32_t max_p, uint32_t stride, bool per_pair_text, size_t *lds_out) {
-    for (const NvShape &sh : kNvShapes) {
-        if ((uint32_t)(sh.G * sh.R) < max_p) continue;
-        const size_t lds = per_pair_text ? (size_t)4 * (64 / sh.G) * stride * 2 : (size_t)stride * 2;
-        if (lds > 160 * 1024) continue;
-        *lds_out = lds;
-        return &sh;
+// the packed banded kernel: as nv16_ok over (M + band + 2); GASALX_NVB16=0: int32 only
+bool nvb16_ok(const NvScheme &s, uint32_t text_bits, uint32_t max_p, uint32_t band, uint32_t *base) {
+    if (!env_flag("GASALX_NVB16", true)) return false;
+    if (text_bits != 2) return false;
+    if (s.match < s.mismatch || s.match - s.mismatch > 255) return false;
+    // all four gap scores whatever the aligner, no mismatch test: deliberately not nv16_ok's rule (pinned)
+    if (s.go > 0 || s.ge > 0 || s.del > 0 || s.ins > 0) return false;
+    const int64_t mag = nv_score_mag(s);
+    if (mag > 0x200) return false;
+    return nv_f16_window((int64_t)max_p + band + 2, mag, nv_gap_sum(s), base);
+}
+
+// ---- the plan of a scoring call: nv_plan_name formats it, the entry points launch from it ----
+enum NvFamily { NV_FAMILY_NONE, NV_FAMILY_INT32, NV_FAMILY_PACKED };
+struct NvPlan {
+    NvFamily family = NV_FAMILY_NONE;
+    int shape = 0;                      // index into kNvShapes
+    size_t lds = 0;                     // dynamic LDS bytes of the family's kernel
+    uint32_t per_block = 0;             // pairs per block (packed: two per lane group)
+    uint32_t lds_stride = 0;            // int32: 16-bit codes per text slot
+    uint32_t base = 0, lds_cols = 0;    // packed: the stored zero, table entries per staged text
+    bool mask = false;                  // int32 LOCAL: mask the pad cells
+};
+constexpr size_t kNvLdsMax = 160 * 1024;
+
+// The lane-group shape is the smallest G*R that covers the patterns whose int32 text slots fit in
+// LDS (one shared slot, or one per pair); the packed kernel runs at that shape inside its window
+// (nv16_ok) while its tables fit: one per column of the shared text, or of every pair's text
+// (two pairs per lane group, 4 waves per block).
+NvPlan nv_make_plan(const gasalx_nv_aligner &al, uint32_t max_p, uint32_t max_t, bool per_pair_text,
+                    uint32_t text_bits) {
+    NvPlan P;
+    if (al.aligner < 0 || al.aligner > 2 || al.type < 0 || al.type > 2) return P;
+    P.lds_stride = (std::max<uint32_t>(max_t, 1) + 7u) & ~7u;
+    for (; P.shape < (int)kNvShapeCount; P.shape++) {
+        const NvShape &sh = kNvShapes[P.shape];
+        P.per_block = 4 * (64 / sh.G);
+        P.lds = per_pair_text ? (size_t)P.per_block * P.lds_stride * 2 : (size_t)P.lds_stride * 2;
+        if ((uint32_t)(sh.G * sh.R) >= max_p && P.lds <= kNvLdsMax) break;
     }
-    return nullptr;
+    if (P.shape == (int)kNvShapeCount) return P;
+    const int G = kNvShapes[P.shape].G;
+    const NvScheme s = nv_scheme(al);
+    const bool gotoh = al.aligner == NV_GOTOH;
+    // LOCAL pads (pattern rows >= M, text columns >= N) never exceed a real cell when no
+    // step can raise a score without a match; otherwise mask them
+    P.mask = al.type == NV_LOCAL && (s.mismatch > 0 || (gotoh ? (s.go > 0 || s.ge > 0) : (s.del > 0 || s.ins > 0)));
+    P.family = NV_FAMILY_INT32;
+    const uint32_t cols = per_pair_text ? (max_t + 3u) & ~3u : (max_t + G + 63u) & ~63u;
+    const size_t lds16 = (size_t)cols * 4 * (per_pair_text ? 2 * P.per_block : 1);
+    if (lds16 <= kNvLdsMax && nv16_ok(s, gotoh, al.type, text_bits, max_p, max_t, &P.base)) {
+        P.family = NV_FAMILY_PACKED;
+        P.lds = lds16; P.per_block *= 2; P.lds_cols = cols;
+    }
+    return P;
+}
+
+// The checks and the plan both scoring entry points share (outputs apart); a shared text sets max_t.
+int nv_score_plan(const gasalx_nv_aligner &al, const gasalx_nv_strings &pat, const gasalx_nv_strings &txt,
+                  bool outputs, uint32_t max_p, uint32_t max_t, NvPlan &P) {
+    if (int rc = nv_check(al, "bad aligner", "bad aligner", nullptr, pat, txt)) return rc;
+    if (int rc = nv_check_ptrs(pat, txt, outputs)) return rc;
+    if (!txt.offsets) max_t = txt.length;
+    // |values| stay far from the -inf stand-in (nvbio's infimum never wins either)
+    if ((int64_t)(max_p + max_t + 2) * nv_score_mag(nv_scheme(al)) * 2 >= (1ll << 28))
+        return nv_fail(GASALX_ERANGE, "scores out of the exact range");
+    P = nv_make_plan(al, max_p, max_t, txt.offsets != nullptr, txt.bits);
+    if (P.family == NV_FAMILY_NONE)
+        return nv_fail(GASALX_ERANGE, "pattern longer than 1024 or text too long for LDS (" + std::to_string(max_p) +
+                                          ", " + std::to_string(max_t) + ")");
+    return GASALX_OK;
+}
+
+NvArgs nv_args(const gasalx_nv_aligner &al, uint32_t n, const gasalx_nv_strings &pat, const gasalx_nv_strings &txt,
+               const NvPlan &P, int32_t *scores, int16_t *scores16) {
+    NvArgs A;
+    nv_fill(A, pat, txt, nv_scheme(al), n);
+    A.score = scores; A.score16 = scores16; A.lds_stride = P.lds_stride;
+    return A;
+}
+Nv16Args nv16_args(const gasalx_nv_aligner &al, uint32_t n, const gasalx_nv_strings &pat, const gasalx_nv_strings &txt,
+                   const NvPlan &P, int32_t *scores, int16_t *scores16) {
+    Nv16Args D;
+    nv_fill(D, pat, txt, nv_scheme(al), n);
+    D.score = scores; D.score16 = scores16; D.base = P.base; D.lds_cols = P.lds_cols;
+    return D;
 }
 
 }  // namespace
@@ -160,107 +272,30 @@ const NvShape *nv_shape(uint32_t max_p, uint32_t stride, bool per_pair_text, siz
 std::string nv_plan_name(const gasalx_nv_aligner &al, uint32_t max_p, uint32_t max_t, bool per_pair_text,
                          uint32_t text_bits) {
     static const char *an[] = {"ed", "sw", "gotoh"}, *tn[] = {"global", "local", "semi"};
-    if (al.aligner < 0 || al.aligner > 2 || al.type < 0 || al.type > 2) return "none";
-    size_t lds = 0;
-    const NvShape *sh = nv_shape(max_p, (std::max<uint32_t>(max_t, 1) + 7u) & ~7u, per_pair_text, &lds);
-    if (!sh) return "none";
-    const bool ed = al.aligner == NV_ED;
-    uint32_t base = 0;
-    const bool pk = nv16_ok(ed ? NV_SW : al.aligner, al.type, ed ? 0 : al.match, ed ? -1 : al.mismatch, al.gap_open,
-                            al.gap_ext, ed ? -1 : al.deletion, ed ? -1 : al.insertion, !per_pair_text, text_bits, max_p,
-                            max_t, &base);
-    const bool fits = nv16_lds(!per_pair_text, max_t, sh->G) <= 160 * 1024;
-    return std::string(pk && fits ? "nvbio16_" : "nvbio_") + an[al.aligner] + "_" + tn[al.type] + (per_pair_text ? "" : "_shared") +
-           "_G" + std::to_string(sh->G) + "R" + std::to_string(sh->R);
-}
-
-// The checks and the kernel arguments both scoring entry points share (outputs apart): ED
-// runs as SW with EditDistanceSWScheme's scores, a shared text sets max_t.
-static int nv_score_args(const gasalx_nv_aligner &al, uint32_t n, const gasalx_nv_strings &pat,
-                         const gasalx_nv_strings &txt, bool have_out, uint32_t max_p, uint32_t &max_t, NvArgs &A) {
-    if (al.aligner < 0 || al.aligner > 2 || al.type < 0 || al.type > 2) { set_error("bad aligner"); return GASALX_EINVAL; }
-    for (uint32_t b : {pat.bits, txt.bits})
-        if (b != 2 && b != 4 && b != 8) { set_error("symbol bits must be 2, 4 or 8"); return GASALX_EINVAL; }
-    if (!pat.words || !pat.offsets || !txt.words || !have_out) { set_error("null argument"); return GASALX_EINVAL; }
-    A.pw = pat.words; A.poff = pat.offsets; A.pbits = pat.bits; A.pbig = pat.big_endian;
-    A.tw = txt.words; A.toff = txt.offsets; A.tbits = txt.bits; A.tbig = txt.big_endian;
-    A.tlen0 = txt.offsets ? 0 : txt.length;
-    if (!txt.offsets) max_t = txt.length;
-    A.score = nullptr; A.score16 = nullptr; A.n = n; A.lds_stride = 0;
-    if (al.aligner == NV_ED) { A.match = 0; A.mismatch = -1; A.del = -1; A.ins = -1; }   // ed_utils.h:45-52
-    else { A.match = al.match; A.mismatch = al.mismatch; A.del = al.deletion; A.ins = al.insertion; }
-    A.go = al.gap_open; A.ge = al.gap_ext;
-    // |values| stay far from the -inf stand-in (nvbio's infimum never wins either)
-    int64_t mag = std::max<int64_t>({std::abs((int64_t)A.match), std::abs((int64_t)A.mismatch),
-                                     std::abs((int64_t)A.go), std::abs((int64_t)A.ge), std::abs((int64_t)A.del),
-                                     std::abs((int64_t)A.ins), 1});
-    if ((int64_t)(max_p + max_t + 2) * mag * 2 >= (1ll << 28)) { set_error("scores out of the exact range"); return GASALX_ERANGE; }
-    return GASALX_OK;
-}
-
-// the packed kernel's arguments from the int32 kernel's
-static Nv16Args nv16_args(const NvArgs &A, uint32_t base, bool shared, uint32_t max_t, int G) {
-    Nv16Args D;
-    D.pw = A.pw; D.poff = A.poff; D.pbits = A.pbits; D.pbig = A.pbig;
-    D.tw = A.tw; D.toff = A.toff; D.tbig = A.tbig; D.tlen0 = A.tlen0;
-    D.score = A.score; D.score16 = A.score16; D.n = A.n;
-    D.match = A.match; D.mismatch = A.mismatch; D.go = A.go; D.ge = A.ge; D.del = A.del; D.ins = A.ins;
-    D.base = base;
-    D.lds_cols = nv16_cols(shared, shared ? A.tlen0 : max_t, G);
-    return D;
-}
-
-static int nv_too_long(uint32_t max_p, uint32_t max_t) {
-    set_error("pattern longer than 1024 or text too long for LDS (" + std::to_string(max_p) + ", " +
-              std::to_string(max_t) + ")");
-    return GASALX_ERANGE;
+    const NvPlan P = nv_make_plan(al, max_p, max_t, per_pair_text, text_bits);
+    if (P.family == NV_FAMILY_NONE) return "none";
+    return std::string(P.family == NV_FAMILY_PACKED ? "nvbio16_" : "nvbio_") + an[al.aligner] + "_" + tn[al.type] +
+           (per_pair_text ? "" : "_shared") + "_G" + std::to_string(kNvShapes[P.shape].G) + "R" +
+           std::to_string(kNvShapes[P.shape].R);
 }
 
 int nv_score_device(const gasalx_nv_aligner &al, uint32_t n, const gasalx_nv_strings &pat,
                     const gasalx_nv_strings &txt, int32_t *scores, int16_t *scores16, uint32_t max_p, uint32_t max_t,
                     hipStream_t st) {
     if (n == 0) return GASALX_OK;
-    NvArgs A;
-    if (int rc = nv_score_args(al, n, pat, txt, scores || scores16, max_p, max_t, A)) return rc;
-    A.score = scores; A.score16 = scores16;
-    const bool gotoh = al.aligner == NV_GOTOH;
-    // LOCAL pads (pattern rows >= M, text columns >= N) never exceed a real cell when no
-    // step can raise a score without a match; otherwise mask them
-    const bool mask = al.type == NV_LOCAL &&
-                      (A.mismatch > 0 || (gotoh ? (A.go > 0 || A.ge > 0) : (A.del > 0 || A.ins > 0)));
-    const uint32_t stride = (std::max<uint32_t>(max_t, 1) + 7u) & ~7u;
-    size_t lds = 0;
-    const NvShape *sh = nv_shape(max_p, stride, txt.offsets != nullptr, &lds);
-    uint32_t base = 0;
-    if (sh && nv16_ok(gotoh ? NV_GOTOH : NV_SW, al.type, A.match, A.mismatch, A.go, A.ge, A.del, A.ins, !txt.offsets,
-                      txt.bits, max_p, max_t, &base)) {
-        const bool shared = !txt.offsets;
-        Nv16Fn fn = nv16_lookup(gotoh ? NV_GOTOH : NV_SW, al.type, shared, sh->G, sh->R);
-        if (fn) {
-            const Nv16Args D = nv16_args(A, base, shared, max_t, sh->G);
-            const size_t lds16 = nv16_lds(shared, shared ? A.tlen0 : max_t, sh->G);
-            if (lds16 <= 160 * 1024) {
-                const uint32_t per_block = 8 * (64 / sh->G);   // two pairs per lane group
-                hipError_t e = launch_lds(fn, dim3((n + per_block - 1) / per_block), dim3(256), lds16, st, D);
-                if (e != hipSuccess) { set_error(hipGetErrorString(e)); return GASALX_EDEVICE; }
-                return GASALX_OK;
-            }
-        }
-    }
-    NvFn fn = sh ? nv_lookup(gotoh, al.type, mask, sh->G, sh->R) : nullptr;
-    if (fn) {
-        A.lds_stride = stride;
-        const uint32_t per_block = 4 * (64 / sh->G);
-        hipError_t e = launch_lds(fn, dim3((n + per_block - 1) / per_block), dim3(256), lds, st, A);
-        if (e != hipSuccess) { set_error(hipGetErrorString(e)); return GASALX_EDEVICE; }
-        return GASALX_OK;
-    }
-    return nv_too_long(max_p, max_t);
+    NvPlan P;
+    if (int rc = nv_score_plan(al, pat, txt, scores || scores16, max_p, max_t, P)) return rc;
+    const uint32_t blocks = (n + P.per_block - 1) / P.per_block;
+    if (P.family == NV_FAMILY_PACKED)
+        return launch_checked(nv16_lookup(al.aligner, al.type, !txt.offsets, P.shape), blocks, P.lds, st,
+                              nv16_args(al, n, pat, txt, P, scores, scores16));
+    return launch_checked(nv_lookup(al.aligner, al.type, P.mask, P.shape), blocks, P.lds, st,
+                          nv_args(al, n, pat, txt, P, scores, scores16));
 }
 
-// Score and BestSink position per pair (nvbio_sink.hpp).  The planner is the score-only one:
-// the packed sink kernel inside the packed kernel's window (nv16_ok, tables within LDS), the
-// int32 sink kernel otherwise, at the same lane-group shape; "_sink" marks the plan.
+// Score and BestSink position per pair (nvbio_sink.hpp).  The plan is the score-only one: the
+// packed sink kernel where the packed kernel would run, the int32 sink kernel otherwise, at the
+// same lane-group shape; "_sink" marks the name.
 std::string nv_sinks_plan_name(const gasalx_nv_aligner &al, uint32_t max_p, uint32_t max_t, bool per_pair_text,
                                uint32_t text_bits) {
     const std::string name = nv_plan_name(al, max_p, max_t, per_pair_text, text_bits);
@@ -271,136 +306,46 @@ int nv_score_sinks_device(const gasalx_nv_aligner &al, uint32_t n, const gasalx_
                           const gasalx_nv_strings &txt, int32_t *scores, uint32_t *sinks, uint32_t max_p,
                           uint32_t max_t, hipStream_t st) {
     if (n == 0) return GASALX_OK;
-    NvSinkArgs S;
-    if (int rc = nv_score_args(al, n, pat, txt, scores || sinks, max_p, max_t, S.a)) return rc;
-    S.a.score = scores; S.sinks = sinks;
-    const NvArgs &A = S.a;
-    const uint32_t stride = (std::max<uint32_t>(max_t, 1) + 7u) & ~7u;
-    size_t lds = 0;
-    const bool shared = !txt.offsets;
-    const NvShape *sh = nv_shape(max_p, stride, !shared, &lds);
-    if (!sh) return nv_too_long(max_p, max_t);
-    const int aln = al.aligner == NV_GOTOH ? NV_GOTOH : NV_SW;
-    uint32_t base = 0;
-    const size_t lds16 = nv16_lds(shared, shared ? A.tlen0 : max_t, sh->G);
-    if (lds16 <= 160 * 1024 &&
-        nv16_ok(aln, al.type, A.match, A.mismatch, A.go, A.ge, A.del, A.ins, shared, txt.bits, max_p, max_t, &base)) {
-        const Nv16SinkArgs D = {nv16_args(A, base, shared, max_t, sh->G), sinks};
-        const uint32_t per_block = 8 * (64 / sh->G);   // two pairs per lane group
-        hipError_t e = launch_lds(nv16_sink_lookup(aln, al.type, shared, sh->G, sh->R),
-                                  dim3((n + per_block - 1) / per_block), dim3(256), lds16, st, D);
-        if (e != hipSuccess) { set_error(hipGetErrorString(e)); return GASALX_EDEVICE; }
-        return GASALX_OK;
-    }
-    NvSinkFn fn = aln == NV_GOTOH ? nv_sink_lookup_t<NV_GOTOH>(al.type, sh->G, sh->R)
-                                  : nv_sink_lookup_t<NV_SW>(al.type, sh->G, sh->R);
-    S.a.lds_stride = stride;
-    const uint32_t per_block = 4 * (64 / sh->G);
-    hipError_t e = launch_lds(fn, dim3((n + per_block - 1) / per_block), dim3(256), lds, st, S);
-    if (e != hipSuccess) { set_error(hipGetErrorString(e)); return GASALX_EDEVICE; }
-    return GASALX_OK;
+    NvPlan P;
+    if (int rc = nv_score_plan(al, pat, txt, scores || sinks, max_p, max_t, P)) return rc;
+    const uint32_t blocks = (n + P.per_block - 1) / P.per_block;
+    if (P.family == NV_FAMILY_PACKED)
+        return launch_checked(nv16_sink_lookup(al.aligner, al.type, !txt.offsets, P.shape), blocks, P.lds, st,
+                              Nv16SinkArgs{nv16_args(al, n, pat, txt, P, scores, nullptr), sinks});
+    return launch_checked(nv_sink_lookup(al.aligner, al.type, P.shape), blocks, P.lds, st,
+                          NvSinkArgs{nv_args(al, n, pat, txt, P, scores, nullptr), sinks});
 }
 
 // ---- BatchedBandedAlignmentScore<band> (nvbanded.hpp): thread per pair, band in registers,
-//      instances for bands up to 8, 16 and 32 ----
-namespace {
-using NvBandFn = void (*)(NvBandArgs);
-template <int ALN, int TYPE>
-NvBandFn nv_band_pick(uint32_t band) {
-    switch (band) {
-        case 8: return &nv_banded_kernel<ALN, TYPE, 8, true>;
-        case 16: return &nv_banded_kernel<ALN, TYPE, 16, true>;
-        case 32: return &nv_banded_kernel<ALN, TYPE, 32, true>;
-        default: break;
-    }
-    if (band <= 8) return &nv_banded_kernel<ALN, TYPE, 8>;
-    if (band <= 16) return &nv_banded_kernel<ALN, TYPE, 16>;
-    if (band <= 32) return &nv_banded_kernel<ALN, TYPE, 32>;
-    return nullptr;
-}
-template <int ALN>
-NvBandFn nv_band_lookup_t(int type, uint32_t band) {
-    return type == NV_GLOBAL ? nv_band_pick<ALN, NV_GLOBAL>(band)
-         : type == NV_SEMI ? nv_band_pick<ALN, NV_SEMI>(band) : nv_band_pick<ALN, NV_LOCAL>(band);
-}
-using NvBand16Fn = void (*)(NvBand16Args);
-template <int ALN, int TYPE>
-NvBand16Fn nv_band16_pick(uint32_t band) {
-    switch (band) {   // band lengths of an instance's own size: the slot tests fold
-        case 8: return &nv_banded16_kernel<ALN, TYPE, 8, true>;
-        case 16: return &nv_banded16_kernel<ALN, TYPE, 16, true>;
-        case 32: return &nv_banded16_kernel<ALN, TYPE, 32, true>;
-        default: break;
-    }
-    if (band <= 8) return &nv_banded16_kernel<ALN, TYPE, 8>;
-    if (band <= 16) return &nv_banded16_kernel<ALN, TYPE, 16>;
-    if (band <= 32) return &nv_banded16_kernel<ALN, TYPE, 32>;
-    return nullptr;
-}
-template <int ALN>
-NvBand16Fn nv_band16_lookup_t(int type, uint32_t band) {
-    return type == NV_GLOBAL ? nv_band16_pick<ALN, NV_GLOBAL>(band)
-         : type == NV_SEMI ? nv_band16_pick<ALN, NV_SEMI>(band) : nv_band16_pick<ALN, NV_LOCAL>(band);
-}
-// the packed banded kernel: 2-bit texts, gaps <= 0, match - mismatch in a byte, every
-// value (bounded by (M + band + 2) * the largest score magnitude) inside the 16-bit f16
-// window (as nv16_ok); GASALX_NVB16=0: int32 only
-bool nvb16_ok(int32_t match, int32_t mismatch, int32_t go, int32_t ge, int32_t del, int32_t ins, uint32_t text_bits,
-              uint32_t max_p, uint32_t band, uint32_t *base) {
-    if (!env_flag("GASALX_NVB16", true)) return false;
-    if (text_bits != 2) return false;
-    if (match < mismatch || match - mismatch > 255) return false;
-    if (go > 0 || ge > 0 || del > 0 || ins > 0) return false;
-    const int64_t mag = std::max<int64_t>({std::abs((int64_t)match), std::abs((int64_t)mismatch), std::abs((int64_t)go),
-                                           std::abs((int64_t)ge), std::abs((int64_t)del), std::abs((int64_t)ins), 1});
-    if (mag > 0x200) return false;
-    const int64_t vabs = ((int64_t)max_p + band + 2) * mag * 2;
-    const int64_t b = 0x400 + 2 * (std::abs((int64_t)go) + std::abs((int64_t)ge) + std::abs((int64_t)del) +
-                                   std::abs((int64_t)ins)) + vabs + 64;
-    if (b + vabs + 512 > 0x7BFF) return false;
-    *base = (uint32_t)b;
-    return true;
-}
-}  // namespace
+//      instances for bands up to 8, 16 and 32; a band length of an instance's own size takes the
+//      EX instance, whose slot tests fold ----
+#define GX_BAND_PICK(K, a, t, ex) (band <= 8 ? &K<a, t, 8, ex> : band <= 16 ? &K<a, t, 16, ex> : &K<a, t, 32, ex>)
 
 int nv_banded_score_device(const gasalx_nv_aligner &al, uint32_t band, uint32_t n, const gasalx_nv_strings &pat,
                            const gasalx_nv_strings &txt, int32_t *scores, hipStream_t st, uint32_t max_p) {
-    if (al.aligner < 0 || al.aligner > 2 || al.type < 0 || al.type > 2) { set_error("bad aligner"); return GASALX_EINVAL; }
-    if (band < 2 || band > 32) { set_error("band length must be 2..32"); return GASALX_EINVAL; }
-    for (uint32_t b : {pat.bits, txt.bits})
-        if (b != 2 && b != 4 && b != 8) { set_error("symbol bits must be 2, 4 or 8"); return GASALX_EINVAL; }
+    if (int rc = nv_check(al, "bad aligner", "bad aligner", &band, pat, txt)) return rc;
     if (n == 0) return GASALX_OK;
-    if (!pat.words || !pat.offsets || !txt.words || !scores) { set_error("null argument"); return GASALX_EINVAL; }
-    NvBandArgs A;
-    A.pw = pat.words; A.poff = pat.offsets; A.pbits = pat.bits; A.pbig = pat.big_endian;
-    A.tw = txt.words; A.toff = txt.offsets; A.tbits = txt.bits; A.tbig = txt.big_endian;
-    A.tlen0 = txt.offsets ? 0 : txt.length;
-    A.score = scores; A.n = n; A.band = band;
-    if (al.aligner == NV_ED) { A.match = 0; A.mismatch = -1; A.del = -1; A.ins = -1; }   // ed_banded_inl.h:63-78
-    else { A.match = al.match; A.mismatch = al.mismatch; A.del = al.deletion; A.ins = al.insertion; }
-    A.go = al.gap_open; A.ge = al.gap_ext;
+    if (int rc = nv_check_ptrs(pat, txt, scores)) return rc;
+    const NvScheme s = nv_scheme(al);
+    const bool ex = band == 8 || band == 16 || band == 32;
     uint32_t base = 0;
-    if (max_p && nvb16_ok(A.match, A.mismatch, A.go, A.ge, A.del, A.ins, txt.bits, max_p, band, &base)) {
+    if (max_p && nvb16_ok(s, txt.bits, max_p, band, &base)) {
         NvBand16Args D;
-        D.pw = A.pw; D.poff = A.poff; D.pbits = A.pbits; D.pbig = A.pbig;
-        D.tw = A.tw; D.toff = A.toff; D.tbig = A.tbig; D.tlen0 = A.tlen0;
-        D.score = scores; D.n = n; D.n_lanes = (n + 1) / 2; D.band = band;
-        D.match = A.match; D.mismatch = A.mismatch; D.go = A.go; D.ge = A.ge; D.del = A.del; D.ins = A.ins;
-        D.base = base;
-        NvBand16Fn f16 = al.aligner == NV_GOTOH ? nv_band16_lookup_t<NV_GOTOH>(al.type, band)
-                                                : nv_band16_lookup_t<NV_SW>(al.type, band);
-        hipLaunchKernelGGL(f16, dim3((D.n_lanes + 255) / 256), dim3(256), 0, st, D);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { set_error(hipGetErrorString(e)); return GASALX_EDEVICE; }
-        return GASALX_OK;
+        nv_fill(D, pat, txt, s, n);
+        D.score = scores; D.n_lanes = (n + 1) / 2; D.band = band; D.base = base;
+        using Fn = void (*)(NvBand16Args);
+        const Fn fn = nv_static(al.aligner, al.type, ex, [band](auto a, auto t, auto e) -> Fn {
+            return GX_BAND_PICK(nv_banded16_kernel, a, t, e); });
+        return launch_checked(fn, (D.n_lanes + 255) / 256, st, D);
     }
-    NvBandFn fn = al.aligner == NV_GOTOH ? nv_band_lookup_t<NV_GOTOH>(al.type, band) : nv_band_lookup_t<NV_SW>(al.type, band);
-    hipLaunchKernelGGL(fn, dim3((n + 255) / 256), dim3(256), 0, st, A);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error(hipGetErrorString(e)); return GASALX_EDEVICE; }
-    return GASALX_OK;
+    NvBandArgs A;
+    nv_fill(A, pat, txt, s, n);
+    A.score = scores; A.band = band;
+    using Fn = void (*)(NvBandArgs);
+    const Fn fn = nv_static(al.aligner, al.type, ex, [band](auto a, auto t, auto e) -> Fn {
+        return GX_BAND_PICK(nv_banded_kernel, a, t, e); });
+    return launch_checked(fn, (n + 255) / 256, st, A);
 }
-
 
 // nvbio BatchedAlignmentTraceback (nvtrace.hpp): one pair per thread, flags and the previous row in
 // the caller's workspace (dir: pad8(max_p) * max_t bytes per pair, row: max_t int2 per pair)
@@ -408,35 +353,18 @@ int nv_traceback_device(const gasalx_nv_aligner &al, uint32_t n, const gasalx_nv
                         const gasalx_nv_strings &txt, uint32_t max_p, uint32_t max_t, uint8_t *dir, int32_t *row,
                         int32_t *score, uint32_t *src, uint32_t *snk, uint8_t *ops, uint32_t ops_stride,
                         uint32_t *n_ops, hipStream_t st) {
-    if (al.aligner != NV_GOTOH && al.aligner != NV_SW && al.aligner != NV_ED) {
-        set_error("traceback: unknown aligner");
-        return GASALX_EINVAL;
-    }
-    if (al.type < 0 || al.type > 2) { set_error("bad alignment type"); return GASALX_EINVAL; }
-    for (uint32_t b : {pat.bits, txt.bits})
-        if (b != 2 && b != 4 && b != 8) { set_error("symbol bits must be 2, 4 or 8"); return GASALX_EINVAL; }
+    if (int rc = nv_check(al, "traceback: unknown aligner", "bad alignment type", nullptr, pat, txt)) return rc;
     if (n == 0) return GASALX_OK;
-    if (!pat.words || !pat.offsets || !txt.words || !score || !src || !snk || !ops || !n_ops || !dir || !row) {
-        set_error("null argument");
-        return GASALX_EINVAL;
-    }
+    if (int rc = nv_check_ptrs(pat, txt, score && src && snk && ops && n_ops && dir && row)) return rc;
     NvTbArgs A;
-    A.pw = pat.words; A.poff = pat.offsets; A.pbits = pat.bits; A.pbig = pat.big_endian;
-    A.tw = txt.words; A.toff = txt.offsets; A.tlen0 = txt.offsets ? 0 : txt.length; A.tbits = txt.bits;
-    A.tbig = txt.big_endian;
-    A.match = al.match; A.mismatch = al.mismatch; A.go = al.gap_open; A.ge = al.gap_ext;
-    A.del = al.deletion; A.ins = al.insertion;
-    if (al.aligner == NV_ED) { A.match = 0; A.mismatch = -1; A.del = -1; A.ins = -1; }   // ed_inl.h:347-365
-    A.n = n; A.max_m = max_p; A.max_n = max_t;
+    nv_fill(A, pat, txt, nv_scheme(al), n);
+    A.max_m = max_p; A.max_n = max_t;
     A.dir = dir; A.row = row; A.score = score; A.src = src; A.snk = snk; A.ops = ops; A.ops_stride = ops_stride;
     A.n_ops = n_ops;
     using Fn = void (*)(NvTbArgs);
-    static const Fn tab[2][3] = {{&nv_traceback_kernel<false, 0>, &nv_traceback_kernel<false, 1>, &nv_traceback_kernel<false, 2>},
-                                 {&nv_traceback_kernel<true, 0>, &nv_traceback_kernel<true, 1>, &nv_traceback_kernel<true, 2>}};
-    hipLaunchKernelGGL(tab[al.aligner == NV_GOTOH ? 1 : 0][al.type], dim3((n + 255) / 256), dim3(256), 0, st, A);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error(hipGetErrorString(e)); return GASALX_EDEVICE; }
-    return GASALX_OK;
+    const Fn fn = nv_static(al.aligner, al.type, false, [](auto a, auto t, auto) -> Fn {
+        return &nv_traceback_kernel<a == NV_GOTOH, t>; });
+    return launch_checked(fn, (n + 255) / 256, st, A);
 }
 
 // BatchedBandedAlignmentTraceback<band> (nvtrace.hpp nv_banded_traceback_kernel); ED runs as
@@ -447,44 +375,25 @@ int nv_banded_traceback_device(const gasalx_nv_aligner &al, uint32_t band, uint3
                                const gasalx_nv_strings &txt, uint32_t max_p, uint32_t *dir, int32_t *score,
                                uint32_t *src, uint32_t *snk, uint8_t *ops, uint32_t ops_stride, uint32_t *n_ops,
                                hipStream_t st) {
-    if (al.aligner != NV_GOTOH && al.aligner != NV_SW && al.aligner != NV_ED) {
-        set_error("banded traceback: unknown aligner");
-        return GASALX_EINVAL;
-    }
-    if (al.type < 0 || al.type > 2) { set_error("bad alignment type"); return GASALX_EINVAL; }
-    if (band < 2 || band > 32) { set_error("band length must be 2..32"); return GASALX_EINVAL; }
-    for (uint32_t b : {pat.bits, txt.bits})
-        if (b != 2 && b != 4 && b != 8) { set_error("symbol bits must be 2, 4 or 8"); return GASALX_EINVAL; }
+    if (int rc = nv_check(al, "banded traceback: unknown aligner", "bad alignment type", &band, pat, txt)) return rc;
     if (n == 0) return GASALX_OK;
-    if (!pat.words || !pat.offsets || !txt.words || !score || !src || !snk || !ops || !n_ops || !dir) {
-        set_error("null argument");
-        return GASALX_EINVAL;
-    }
+    if (int rc = nv_check_ptrs(pat, txt, score && src && snk && ops && n_ops && dir)) return rc;
     NvBandTbArgs A;
-    A.pw = pat.words; A.poff = pat.offsets; A.pbits = pat.bits; A.pbig = pat.big_endian;
-    A.tw = txt.words; A.toff = txt.offsets; A.tlen0 = txt.offsets ? 0 : txt.length; A.tbits = txt.bits;
-    A.tbig = txt.big_endian;
-    A.match = al.match; A.mismatch = al.mismatch; A.go = al.gap_open; A.ge = al.gap_ext;
-    A.del = al.deletion; A.ins = al.insertion;
-    if (al.aligner == NV_ED) { A.match = 0; A.mismatch = -1; A.del = -1; A.ins = -1; }
-    A.n = n; A.band = band; A.words = (band + 3) / 4; A.max_m = max_p;
+    nv_fill(A, pat, txt, nv_scheme(al), n);
+    A.band = band; A.words = (band + 3) / 4; A.max_m = max_p;
     A.dir = dir; A.score = score; A.src = src; A.snk = snk; A.ops = ops; A.ops_stride = ops_stride; A.n_ops = n_ops;
     using Fn = void (*)(NvBandTbArgs);
-#define NVBT_ROW(G, T) {&nv_banded_traceback_kernel<G, T, 8>, &nv_banded_traceback_kernel<G, T, 16>, &nv_banded_traceback_kernel<G, T, 32>}
-    static const Fn tab[2][3][3] = {{NVBT_ROW(false, 0), NVBT_ROW(false, 1), NVBT_ROW(false, 2)},
-                                    {NVBT_ROW(true, 0), NVBT_ROW(true, 1), NVBT_ROW(true, 2)}};
-#undef NVBT_ROW
-#define NVBT_EX(G, T) {&nv_banded_traceback_kernel<G, T, 7, true>, &nv_banded_traceback_kernel<G, T, 15, true>, &nv_banded_traceback_kernel<G, T, 31, true>}
-    static const Fn tab_ex[2][3][3] = {{NVBT_EX(false, 0), NVBT_EX(false, 1), NVBT_EX(false, 2)},
-                                       {NVBT_EX(true, 0), NVBT_EX(true, 1), NVBT_EX(true, 2)}};
-#undef NVBT_EX
-    const int g = al.aligner == NV_GOTOH ? 1 : 0;
-    const int ex = band == 7 ? 0 : band == 15 ? 1 : band == 31 ? 2 : -1;
-    const Fn fn = ex >= 0 ? tab_ex[g][al.type][ex] : tab[g][al.type][band <= 8 ? 0 : band <= 16 ? 1 : 2];
-    hipLaunchKernelGGL(fn, dim3((n + 255) / 256), dim3(256), 0, st, A);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error(hipGetErrorString(e)); return GASALX_EDEVICE; }
-    return GASALX_OK;
+    const bool exact = band == 7 || band == 15 || band == 31;
+    const Fn fn = nv_static(al.aligner, al.type, exact, [band](auto a, auto t, auto ex) -> Fn {
+        constexpr bool g = a == NV_GOTOH;
+        if constexpr (ex)
+            return band == 7 ? &nv_banded_traceback_kernel<g, t, 7, true>
+                 : band == 15 ? &nv_banded_traceback_kernel<g, t, 15, true> : &nv_banded_traceback_kernel<g, t, 31, true>;
+        else
+            return GX_BAND_PICK(nv_banded_traceback_kernel, g, t, false);
+    });
+    return launch_checked(fn, (n + 255) / 256, st, A);
 }
+#undef GX_BAND_PICK
 
 }  // namespace gx

@@ -156,6 +156,70 @@ def test_plan_names_match_golden_grid(monkeypatch):
     assert not bad, (len(bad), bad[:5], [(got[k], want[k]) for k in bad[:5]])
 
 
+# ---- the nvbio launcher's planner over a fixed grid (tests/golden/nv_plan_names.json, written by
+#      tools/plan_grid.py --nv from the build of the commit it names) ----
+# every lane-group shape edge G*R of batched.hip's shape list, and the length past it
+NV_PLAN_PLENS = (64, 65, 96, 97, 128, 129, 152, 153, 192, 193, 256, 257, 320, 321, 512, 513, 1024, 1025)
+# Text lengths either side of: the packed kernel's per-pair tables leaving LDS at G = 8 (4-column
+# tables x 64 pairs: 640 columns); the int32 kernel's per-pair slots leaving LDS at G = 8 (2,560
+# codes, which moves the shape to G = 16; also the packed limit at G = 32) and at G = 64 (20,480: no
+# plan); the f16 window of the plain score set in the GLOBAL / SEMI_GLOBAL Gotoh drift frame at the
+# shortest pattern (1683 + 5 * 64 + 2 t <= 0x7BFF: 14,870); with a zero gap extension the drift
+# frame admits any text, and one shared text's tables leave LDS at 40,952 columns (G = 8); its
+# int32 slot at 81,920 (no plan).  The plain set's window outside the drift frame (1610 +
+# 8 (p + t + 2) <= 0x7BFF) closes between 2,561 and 14,870 for every pattern length.
+NV_PLAN_TLENS = (64, 640, 641, 2560, 2561, 14870, 14871, 20480, 20481, 40952, 40953, 81920, 81921)
+# (match, mismatch, gap_open, gap_ext, deletion, insertion), one either side of each admission rule
+# of the packed kernel, the sets fewest rules admit first (longer runs in the fixture): a positive
+# mismatch; match - mismatch 256; a magnitude of 0x201; an edit-distance aligner's gap_open /
+# gap_ext, which no ED kernel reads, closing the window; a magnitude of 0x200; match - mismatch
+# 255; a positive gap for Gotoh only; plain; an ED aligner's gap_open / gap_ext moving the window;
+# a zero extension; a positive gap for linear gaps only
+NV_PLAN_SCORES = ((2, 1, -2, -1, -1, -1), (200, -56, -2, -1, -1, -1), (2, -1, -0x201, -1, -1, -1),
+                  (0, 0, -300, -300, 0, 0), (2, -1, -0x200, -1, -1, -1), (200, -55, -2, -1, -1, -1),
+                  (2, -1, 1, -1, -1, -1), (2, -1, -2, -1, -1, -1), (0, 0, -3, -3, 0, 0), (2, -1, -2, 0, -1, -1),
+                  (2, -1, -2, -1, -1, 1))
+NV_PLAN_ENVS = (None, "GASALX_NV16=0")
+
+
+def nv_plan_grid_names(setenv, delenv):
+    """The name of every grid row, in the fixture's order: switch, entry point (describe_plan, then
+    describe_sinks_plan), aligner, type, shared / per-pair text, pattern length, text length, text
+    bits, score set."""
+    lib, buf = G.lib(), ctypes.create_string_buffer(128)
+    names = []
+    for env in NV_PLAN_ENVS:
+        delenv("GASALX_NV16")
+        if env:
+            setenv(*env.split("="))
+        for fn in (lib.gasalx_nv_describe_plan, lib.gasalx_nv_describe_sinks_plan):
+            for aligner in (G.NV_ED, G.NV_SW, G.NV_GOTOH):
+                for typ in (G.NV_GLOBAL, G.NV_LOCAL, G.NV_SEMI_GLOBAL):
+                    refs = [ctypes.byref(G.NvAligner(aligner, typ, *s).cstruct()) for s in NV_PLAN_SCORES]
+                    for per_pair in (0, 1):
+                        for p in NV_PLAN_PLENS:
+                            for t in NV_PLAN_TLENS:
+                                for bits in (2, 4, 8):
+                                    for ref in refs:
+                                        assert fn(ref, p, t, per_pair, bits, buf, 128) == 0
+                                        names.append(buf.value)
+    return [n.decode() for n in names]
+
+
+def test_nv_plan_names_match_golden_grid(monkeypatch):
+    """The nvbio launcher names the same kernel for every row of the grid as the build that wrote the
+    fixture (encoded as plan_names.json is)."""
+    import json
+    gold = json.load(open(os.path.join(ROOT, "tests", "golden", "nv_plan_names.json")))
+    assert gold["plens"] == list(NV_PLAN_PLENS) and gold["tlens"] == list(NV_PLAN_TLENS)
+    assert gold["scores"] == [list(s) for s in NV_PLAN_SCORES] and gold["envs"] == list(NV_PLAN_ENVS)
+    want = [gold["names"][i] for i, c in zip(gold["runs"][0::2], gold["runs"][1::2]) for _ in range(c)]
+    got = nv_plan_grid_names(monkeypatch.setenv, lambda s: monkeypatch.delenv(s, raising=False))
+    assert len(got) == len(want) == gold["rows"]
+    bad = [k for k in range(len(got)) if got[k] != want[k]]
+    assert not bad, (len(bad), bad[:5], [(got[k], want[k]) for k in bad[:5]])
+
+
 def test_synthetic_workloads_deterministic():
     a = G.Batch.synth(2, 64, 0x5EED0002)
     b = G.Batch.synth(2, 64, 0x5EED0002)

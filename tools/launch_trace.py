@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
 """The library's launch sequence, path by path, for comparing two builds of it.
 
-  launch_trace.py run            one small call per dispatcher path and per host form of the flat API on
-                                 device 0 (GASALX_LIB picks the library); meant to run under
-                                 `rocprofv3 --kernel-trace --output-format csv`
+  launch_trace.py run            one small call per dispatcher path, per host form of the flat API and
+                                 per branch of the nvbio launcher on device 0 (GASALX_LIB picks the
+                                 library); meant to run under `rocprofv3 --kernel-trace --output-format csv`
   launch_trace.py list DIR OUT   the kernel-trace CSV(s) under DIR as an ordered list, one line per
                                  launch of the library's kernels: name, grid, block, LDS bytes
 
 Two builds launch the same sequence when their lists are equal line for line
-(profiles/dispatch_refactor/README.md, profiles/capi_refactor/README.md).
+(profiles/dispatch_refactor/README.md, profiles/capi_refactor/README.md,
+profiles/nv_launcher_refactor/README.md).
 """
 import csv
 import glob
@@ -74,8 +75,10 @@ def run():
     eng.pairhmm_quals_log10_host(hmm)
     rng = np.random.default_rng(0x55)
     plen = rng.integers(20, 101, 200)
-    P = G.PackedSet.pack([rng.integers(0, 4, int(k)) for k in plen])
-    T = G.PackedSet.pack([rng.integers(0, 4, int(k) + 20) for k in plen], bits=2, big_endian=False)
+    pats = [rng.integers(0, 4, int(k)) for k in plen]
+    txts = [rng.integers(0, 4, int(k) + 20) for k in plen]
+    P = G.PackedSet.pack(pats)
+    T = G.PackedSet.pack(txts, bits=2, big_endian=False)
     al = G.NvAligner(G.NV_GOTOH, G.NV_SEMI_GLOBAL, 2, -1, -2, -1)
     eng.nv_score_host(al, P, T)
     eng.nv_banded_score_host(al, 16, P, T)
@@ -86,6 +89,23 @@ def run():
         call()
         del os.environ["GASALX_NV_TB_BUDGET"]
     eng.align_host(rand_batch(0x56, 40_000, 20, 40, 20, 40), G.make_params(algo=G.LOCAL))   # the two-stream pipeline
+
+    # every branch of the nvbio launcher (profiles/nv_launcher_refactor/README.md); the packed score
+    # and banded kernels, band 16, ran above
+    T4 = G.PackedSet.pack(txts)                                                   # 4-bit texts: the int32 kernels
+    eng.nv_score_host(al, P, G.PackedSet.pack([max(txts, key=len)], bits=2, big_endian=False, shared=True))
+    eng.nv_score_host(al, P, T4)
+    eng.nv_score_host(G.NvAligner(G.NV_GOTOH, G.NV_LOCAL, 2, 1, -2, -1), P, T)    # a positive mismatch: MASK
+    eng.nv_score_sinks_host(al, P, T)
+    eng.nv_score_sinks_host(al, P, T4)
+    for band in (16, 12):                                                         # an EX instance and a plain one
+        eng.nv_banded_score_host(al, band, P, T4)
+    eng.nv_banded_score_host(al, 12, P, T)
+    for band in (15, 16):
+        eng.nv_banded_traceback_host(al, band, P, T)
+    P199, T199 = G.PackedSet.pack(pats[:199]), G.PackedSet.pack(txts[:199], bits=2, big_endian=False)
+    eng.nv_score_host(al, P199, T199)                                             # an odd n: the packed grids round up
+    eng.nv_banded_score_host(al, 16, P199, T199)
     eng.close()
 
 

@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """Write tests/golden/plan_names.json: the plan name gasalx_describe_plan gives for every row of
 the grid of tests/test_capi.py (plan_grid_names), from the library GASALX_LIB names (default: this
-tree's build).  No GPU needed.
+tree's build).  No GPU needed.  With --nv: tests/golden/nv_plan_names.json, the names
+gasalx_nv_describe_plan and gasalx_nv_describe_sinks_plan give over nv_plan_grid_names' grid.
 
-usage: GASALX_LIB=/path/to/parent/libgasal.so plan_grid.py COMMIT [OUT.json]
+usage: GASALX_LIB=/path/to/parent/libgasal.so plan_grid.py [--nv] COMMIT [OUT.json]
 
-The fixture pins the planner across host-side refactors, so it is written from a build of the
+A fixture pins its planner across host-side refactors, so it is written from a build of the
 commit *before* the change under test (COMMIT, recorded in the file), never from the branch.
 Names are stored once; rows are run-length encoded as a flat list: name index, count, name index, count, ...
 """
@@ -20,9 +21,13 @@ import test_capi as T  # noqa: E402
 
 
 def main():
-    commit = sys.argv[1]
-    out = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "tests", "golden", "plan_names.json")
-    rows = T.plan_grid_names(os.environ.__setitem__, lambda s: os.environ.pop(s, None))
+    nv = "--nv" in sys.argv
+    args = [a for a in sys.argv[1:] if a != "--nv"]
+    commit = args[0]
+    out = args[1] if len(args) > 1 else os.path.join(ROOT, "tests", "golden",
+                                                     "nv_plan_names.json" if nv else "plan_names.json")
+    grid = T.nv_plan_grid_names if nv else T.plan_grid_names
+    rows = grid(os.environ.__setitem__, lambda s: os.environ.pop(s, None))
     names = sorted(set(rows))
     index = {n: i for i, n in enumerate(names)}
     runs = []
@@ -31,8 +36,13 @@ def main():
             runs[-1] += 1
         else:
             runs += [index[r], 1]
-    doc = {"commit": commit, "lens": list(T.PLAN_LENS), "scores": [list(s) for s in T.PLAN_SCORES],
-           "envs": list(T.PLAN_ENVS), "rows": len(rows), "names": names, "runs": runs}
+    if nv:
+        doc = {"commit": commit, "plens": list(T.NV_PLAN_PLENS), "tlens": list(T.NV_PLAN_TLENS),
+               "scores": [list(s) for s in T.NV_PLAN_SCORES], "envs": list(T.NV_PLAN_ENVS)}
+    else:
+        doc = {"commit": commit, "lens": list(T.PLAN_LENS), "scores": [list(s) for s in T.PLAN_SCORES],
+               "envs": list(T.PLAN_ENVS)}
+    doc.update(rows=len(rows), names=names, runs=runs)
     with open(out, "w") as f:
         json.dump(doc, f, separators=(",", ":"))
         f.write("\n")
