@@ -384,6 +384,37 @@ int align_host_pipelined(gasalx_engine *eng, const gasalx_params *params, const 
     return GASALX_OK;
 }
 
+// gasalx_semi_cigar_*: the argument checks, one text each, in this order.  b / out NULL (the describe
+// call): the checks on the parameters only.
+bool ranges_overlap(const void *a, uint64_t an, const void *b, uint64_t bn) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + bn && y < x + an;
+}
+int semi_cigar_checks(const gasalx_params *p, const gasalx_batch *b, const gasalx_results *out) {
+    static const char *const src[] = {"NONE", "QUERY", "TARGET", "BOTH"};
+    if (p->algo != 2) { gx::set_error("semi_cigar: algo must be SEMI_GLOBAL"); return GASALX_EINVAL; }
+    if (p->second_best) { gx::set_error("semi_cigar: second_best is not supported"); return GASALX_EUNSUPPORTED; }
+    if (p->head != 2 || p->tail != 2) {
+        gx::set_error(std::string("semi_cigar: HEAD=") + src[p->head] + " TAIL=" + src[p->tail] +
+                      " is not supported (HEAD=TARGET TAIL=TARGET only)");
+        return GASALX_EUNSUPPORTED;
+    }
+    if (!b || !out) return GASALX_OK;
+    if (!out->aln_score || !out->cigar || !out->n_cigar_ops) {
+        gx::set_error("semi_cigar: aln_score, cigar and n_cigar_ops outputs are required");
+        return GASALX_EINVAL;
+    }
+    if (out->aln_score2 || out->q_end2 || out->t_end2) {
+        gx::set_error("semi_cigar: the second-best outputs must be NULL");
+        return GASALX_EINVAL;
+    }
+    if (b->q_batch && ranges_overlap(out->cigar, b->q_bytes, b->q_batch, b->q_bytes)) {
+        gx::set_error("semi_cigar: cigar overlaps q_batch (it must be a buffer of its own)");
+        return GASALX_EINVAL;
+    }
+    return GASALX_OK;
+}
+
 // ph2pr[q] = powf(10, -q/10) on the host, as the reference builds it (tile_1.cu:216-220)
 void ph2pr_table(float *t) {
     for (int i = 0; i < 128; i++) t[i] = powf(10.f, -((float)i) / 10.f);
@@ -724,6 +755,85 @@ int gasalx_align_host(gasalx_engine *eng, const gasalx_params *params, const gas
         if (void *h = get_field(*ho, f))
             CK(hipMemcpyAsync(h, get_field(dout, f), field_bytes(f, n, hb->q_bytes), hipMemcpyDeviceToHost, st));
     return host_finish(st, GASALX_OK, {});
+}
+
+int gasalx_describe_semi_cigar_plan(const gasalx_params *params, uint32_t max_q_len, uint32_t max_t_len, char *buf,
+                                    uint32_t buf_len) {
+    if (!valid_params(params) || !buf || buf_len == 0) { gx::set_error("null argument"); return GASALX_EINVAL; }
+    buf[0] = 0;
+    int rc = semi_cigar_checks(params, nullptr, nullptr);
+    if (rc) return rc;
+    gx::BatchShape s;
+    s.max_q = max_q_len; s.max_t = max_t_len;
+    std::string why;
+    const gx::Plan pl = gx::make_semi_cigar_plan(*params, s, false, &rc, &why);
+    if (rc) gx::set_error(why);
+    std::snprintf(buf, buf_len, "%s", pl.name.c_str());
+    return rc;
+}
+
+int gasalx_semi_cigar_device(gasalx_engine *eng, const gasalx_params *params, const gasalx_batch *b,
+                             const gasalx_results *out, void *stream) {
+    if (!eng || !valid_params(params) || !b || !out) { gx::set_error("null argument"); return GASALX_EINVAL; }
+    int rc = semi_cigar_checks(params, b, out);
+    if (rc) return rc;
+    hipStream_t st;
+    if ((rc = enter(eng, stream, &st))) return rc;
+    gx::BatchShape shape;
+    shape.max_q = b->max_q_len;
+    shape.max_t = b->max_t_len;
+    if ((rc = device_max_lens(b->q_lens, b->t_lens, b->n_alns, st, &shape.max_q, &shape.max_t))) return rc;
+    return gx::semi_cigar_device(eng->ws, *params, *b, *out, st, shape, false);
+}
+
+int gasalx_semi_cigar_host(gasalx_engine *eng, const gasalx_params *params, const gasalx_batch *hb,
+                           const gasalx_results *ho) {
+    if (!eng || !valid_params(params) || !hb || !ho) { gx::set_error("null argument"); return GASALX_EINVAL; }
+    int rc = semi_cigar_checks(params, hb, ho);
+    if (rc) return rc;
+    if (!hb->q_batch || !hb->t_batch || !hb->q_offsets || !hb->t_offsets || !hb->q_lens || !hb->t_lens) {
+        gx::set_error("missing batch array");
+        return GASALX_EINVAL;
+    }
+    hipStream_t st;
+    if ((rc = enter(eng, nullptr, &st))) return rc;
+    const uint32_t n = hb->n_alns;
+    gasalx_batch db = *hb;
+    const uint32_t pk = params->is_packed ? 2 : 1;   // packed input: half the bytes the offsets count
+    Stager in{eng, st};
+    in(B_Q, db.q_batch, hb->q_bytes / pk);
+    in(B_T, db.t_batch, hb->t_bytes / pk);
+    in(B_QO, db.q_offsets, n);
+    in(B_TO, db.t_offsets, n);
+    in(B_QL, db.q_lens, n);
+    in(B_TL, db.t_lens, n);
+    in(B_QOP, db.q_ops, n);
+    in(B_TOP, db.t_ops, n);
+    if (in.rc) return in.rc;
+    db.max_q_len = hb->max_q_len ? hb->max_q_len : host_max(hb->q_lens, n);
+    db.max_t_len = hb->max_t_len ? hb->max_t_len : host_max(hb->t_lens, n);
+    // the outputs the caller asked for, each in its own device buffer; the CIGAR buffer starts as
+    // zeros, so the bytes the walk does not write come back the same on every call
+    gasalx_results dout = {};
+    for (int f : {0, 1, 2, 3, 4, kCigar, kNops}) {
+        if (!get_field(*ho, f)) continue;
+        gx::DevBuf &d = eng->buf[B_OUT + f];
+        CK(d.reserve(field_bytes(f, n, hb->q_bytes) + 16));
+        set_field(dout, f, d.p);
+    }
+    CK(hipMemsetAsync(dout.cigar, 0, hb->q_bytes, st));
+    gx::BatchShape shape;
+    shape.max_q = db.max_q_len;
+    shape.max_t = db.max_t_len;
+    shape.sort = gx::uneven_lengths(*params, hb->q_lens, hb->t_lens, n);   // the score launch: by query length
+    gasalx_params by_target = *params;
+    by_target.algo = 1;                                                    // the flags launch: by target length
+    const bool sort_t = gx::uneven_lengths(by_target, hb->q_lens, hb->t_lens, n);
+    rc = gx::semi_cigar_device(eng->ws, *params, db, dout, st, shape, sort_t);
+    return host_finish(st, rc, {{ho->aln_score, dout.aln_score, (size_t)n * 4}, {ho->q_end, dout.q_end, (size_t)n * 4},
+                                {ho->t_end, dout.t_end, (size_t)n * 4}, {ho->q_start, dout.q_start, (size_t)n * 4},
+                                {ho->t_start, dout.t_start, (size_t)n * 4}, {ho->cigar, dout.cigar, hb->q_bytes},
+                                {ho->n_cigar_ops, dout.n_cigar_ops, (size_t)n * 4}});
 }
 
 int gasalx_pairhmm_device(gasalx_engine *eng, const gasalx_hmm_batch *b, float *res, void *stream) {

@@ -423,6 +423,90 @@ Plan make_plan(const gasalx_params &p, const BatchShape &s, bool has_ops) {
     return pl;
 }
 
+// gasalx_semi_cigar_*: the value window of the packed flags kernel (wavefront16.hpp WF16_SEMI_TB) over
+// a shape's span.  GLOBAL's frame (drift e, table offset K = max(2*ceil(max(b, npen)/2), 2e)), but not
+// GLOBAL's bound: with the free target head values no longer fall along the top row.  Every cell has
+// H >= F >= -(OE + e*r) (the insertion run from H(-1, c) = 0), stored + e*(r + c) >= B - OE, and the
+// gap candidates tmp - OE >= -(2*OE + K + e*r) likewise stay within 2*OE + K + 2e of B whatever the
+// span; values rise by at most a per diagonal step and by the frame, e per row + column.
+static bool semi_tb16_ok(const gasalx_params &p, uint32_t mq, uint32_t mt, int32_t *vmin, int64_t span) {
+    if (p.match < 0 || p.mismatch < 0 || p.gap_open < 0 || p.gap_extend < 0) return false;
+    if (p.has_n_penalty && p.n_penalty < 0) return false;
+    const int64_t a = p.match, b = p.mismatch, oe = (int64_t)p.gap_open + p.gap_extend, e = p.gap_extend;
+    const int64_t npen = p.has_n_penalty ? p.n_penalty : 0;
+    const int64_t q8 = pad8(mq), t8 = pad8(mt);
+    const int64_t k = std::max(2 * ((std::max(b, npen) + 1) / 2), 2 * e);   // pk16_params, WF_GLOBAL
+    if (a + k > 255) return false;                                          // table bytes
+    if (!span) span = q8 + t8 + 2 * 64 + 8;
+    const int64_t neg = 0x400 + 2 * e + 16;
+    const int64_t v = 4 * oe + k + 2 * e + 64;   // below every reachable value, span or no span
+    const int64_t top = neg + v + a * std::min(q8, t8) + a + k + oe + 64 + e * span;
+    if (top > 0x7BFF) return false;
+    *vmin = (int32_t)v;
+    return true;
+}
+
+Plan make_semi_cigar_plan(const gasalx_params &p, const BatchShape &s, bool has_ops, int *rc, std::string *why) {
+    Plan pl;
+    pl.max_q = s.max_q; pl.max_t = s.max_t;
+    pl.name = "none";
+    *rc = GASALX_OK;
+    const uint32_t q8 = pad8(s.max_q), t8 = pad8(s.max_t);
+    // (an extension dearer than an opening, or a gap that scores: the walk's "extended" bit could then
+    // name a source the maximum did not take)
+    if (p.gap_open < 0 || p.gap_extend < 0) {
+        *rc = GASALX_EUNSUPPORTED;
+        *why = "semi_cigar: negative gap_open or gap_extend is not supported";
+        return pl;
+    }
+    if (!int16_safe(p, s.max_q, s.max_t) || t8 >= 32000) {
+        *rc = GASALX_ERANGE;
+        *why = "semi_cigar: lengths x scores leave the int16 range the semi-global kernels keep";
+        return pl;
+    }
+    const Shape *pick = nullptr;
+    for (const Shape &sh : kShapes)
+        if ((uint32_t)(sh.G * sh.R) >= q8) { pick = &sh; break; }
+    if (!pick) {
+        *rc = GASALX_ERANGE;
+        *why = "semi_cigar: padded query of " + std::to_string(q8) + " over the largest wavefront shape (" +
+               std::to_string(kShapes[sizeof(kShapes) / sizeof(kShapes[0]) - 1].G *
+                              kShapes[sizeof(kShapes) / sizeof(kShapes[0]) - 1].R) + " rows)";
+        return pl;
+    }
+    pl.G = pick->G; pl.R = pick->R;
+    pl.lds_stride = std::max<uint32_t>(t8, 8);
+    pl.lds_bytes = (size_t)kWavesPerBlock * (64 / pl.G) * pl.lds_stride;
+    if (pl.lds_bytes > 160 * 1024) {
+        *rc = GASALX_ERANGE;
+        *why = "semi_cigar: padded target of " + std::to_string(t8) + " needs more than 160 KB of LDS";
+        return pl;
+    }
+    pl.kind = PLAN_WAVEFRONT;
+    pl.wf_algo = WF_GLOBAL;   // query rows in registers, target on the step axis
+    pl.semi_tb = true;
+    pl.tb = true;
+    pl.need_pack = has_ops;
+    pl.packed16 = env_flag("GASALX_PACKED16", true) && semi_tb16_ok(p, s.max_q, s.max_t, &pl.vmin, 0);
+    if (pl.packed16) {
+        // the traceback shapes (R % 4 == 0, >= 16 rows per lane above G = 8); GASALX_GMIN as make_plan
+        const int gforce = env_int("GASALX_GMIN", 0);
+        const uint32_t gmin = gforce > 0 ? (uint32_t)gforce : 8u;
+        for (const Shape &sh : kShapes16)
+            if ((uint32_t)sh.G >= gmin && (uint32_t)(sh.G * sh.R) >= q8 && !(sh.R % 4 || (sh.G > 8 && sh.R < 16))) {
+                pl.G16 = sh.G; pl.R16 = sh.R;
+                break;
+            }
+        pl.lds16_stride = packed_lds_stride(t8, pl.G16);
+        pl.lds16_bytes = packed_lds_bytes(t8, pl.G16);
+        if (pl.G16 == 0 || pl.lds16_bytes > 160 * 1024) pl.packed16 = false;
+        if (pl.packed16) pl.packed16 = semi_tb16_ok(p, s.max_q, s.max_t, &pl.vmin, packed_span(pl.G16, pl.R16, t8));
+    }
+    pl.name = pl.packed16 ? "wavefront16_semi_tb_G" + std::to_string(pl.G16) + "R" + std::to_string(pl.R16)
+                          : "wavefront_semi_tb_G" + std::to_string(pl.G) + "R" + std::to_string(pl.R);
+    return pl;
+}
+
 #define HIPCHK(x)                                                                        \
     do {                                                                                 \
         hipError_t e__ = (x);                                                            \
@@ -636,7 +720,9 @@ static int launch_wavefront(Workspace &ws, const Plan &pl, const gasalx_params &
         v.key2 = pl.key2; v.ku16 = pl.ku16; v.kseg = pl.kseg_shift != 0;
         v.lrs = pl.wf_algo == WF_LOCAL && !pl.tb && !pl.key2 && A.lstop != nullptr && pl.kf16 != 0 && !pl.kseg_shift;
         v.stop = A.stop != nullptr;
-        WfFn f16 = pl.tb_band ? wf16_pick_r4<WF16_GLOBAL_CP>(pl.G16, pl.R16) : wf16_lookup(pl.wf_algo, pl.G16, pl.R16, v);
+        WfFn f16 = pl.semi_tb   ? wf16_semi_tb_lookup(pl.G16, pl.R16)
+                   : pl.tb_band ? wf16_pick_r4<WF16_GLOBAL_CP>(pl.G16, pl.R16)
+                                : wf16_lookup(pl.wf_algo, pl.G16, pl.R16, v);
         // WITH_START reverse passes: the register axis sized per block (rclass.hip)
         if (A.rev && !pl.tb_band && (v.stop || v.lrs)) {
             const int ra = A.stop ? WF16_SEMI_STOP : pl.ku16 ? WF16_LOCAL_U16_RS : WF16_LOCAL_RS;
@@ -670,8 +756,9 @@ static int launch_wavefront(Workspace &ws, const Plan &pl, const gasalx_params &
     }
     // (the band path's int32 launch aligns its declined blocks without direction words: the walk sends
     // those pairs to the fallback list, whose launch writes them into the capped buffer)
-    return launch_int32(pl, A.stop ? pick_instance<WfK<WF_SEMI, true, false, true>, SHAPES_R4>(pl.G, pl.R)
-                                   : wf_lookup(pl.wf_algo, pl.keys, pl.tb && !pl.tb_band, pl.G, pl.R), A, st);
+    return launch_int32(pl, pl.semi_tb ? wf_semi_tb_lookup(pl.G, pl.R)
+                            : A.stop   ? pick_instance<WfK<WF_SEMI, true, false, true>, SHAPES_R4>(pl.G, pl.R)
+                                       : wf_lookup(pl.wf_algo, pl.keys, pl.tb && !pl.tb_band, pl.G, pl.R), A, st);
 }
 
 // The counting sort's arrays in ws.sort_meta: perm[n], then (two) a second array of n words -- the
@@ -1215,7 +1302,7 @@ static TbArgs make_tb_args(const Call &c, uint64_t cigar_cap, const uint8_t *wal
     T.cigar = c.out.cigar; T.n_ops = c.out.n_cigar_ops; T.n = c.n;
     T.cigar_cap = cigar_cap ? cigar_cap : c.b.q_bytes;
     fill_scoring(T, p);
-    T.is_local = p.algo == 3;
+    T.is_local = pl.semi_tb ? kTbSemi : p.algo == 3;
     T.slot_of = c.slot_of;
     T.sc_nn = p.has_n_penalty ? -p.n_penalty : p.match;   // GLOBAL: N == N is a match unless N_PENALTY
     T.qseq = walk_qseq ? walk_qseq : c.qsrc; T.tseq = c.tsrc; T.toff = c.b.t_offsets; T.seq_packed = c.packed;
@@ -1369,6 +1456,51 @@ int align_device(Workspace &ws, const gasalx_params &p, const gasalx_batch &b, c
     // so splitting a call into halves whose walks overlap the next half's DP leaves the last walk
     // exposed and gained nothing; round 6 measured it, profiles/r06/)
     return align_body(ws, p, pl, b, out, st, sized, cigar_cap, walk_qseq);
+}
+
+// gasalx_semi_cigar_*: SEMI-GLOBAL with HEAD = TAIL = TARGET and the alignment itself.  Three steps on
+// one stream: the score launch of align_device with WITHOUT_START (score, q_end, t_end: the same
+// kernels, so the same numbers), the direction-flag launch over the same sequences (WF16_SEMI_TB, the
+// int32 kernel for declined blocks), and the walk from (ql - 1, t_end) until the query is exhausted.
+int semi_cigar_device(Workspace &ws, const gasalx_params &p, const gasalx_batch &b, const gasalx_results &out,
+                      hipStream_t st, const BatchShape &shape, bool sort_t) {
+    if (b.n_alns == 0 || b.q_bytes == 0 || b.t_bytes == 0) { set_error("empty batch"); return GASALX_EINVAL; }
+    if ((b.q_bytes & 7) || (b.t_bytes & 7)) { set_error("batch bytes not a multiple of 8"); return GASALX_EINVAL; }
+    if (shape.max_q == 0 || shape.max_t == 0) { set_error("zero-length sequence"); return GASALX_ERANGE; }
+    const bool has_ops = b.q_ops && b.t_ops;
+    const uint32_t n = b.n_alns;
+    ws.pk_flags = 0;
+    BatchShape sized = shape;
+    sized.n = n;
+    gasalx_params ps = p;
+    ps.algo = 2; ps.start_pos = 0; ps.second_best = 0; ps.head = 2; ps.tail = 2;
+    int rc = GASALX_OK;
+    std::string why;
+    BatchShape tshape = sized;
+    tshape.sort = sort_t;
+    const Plan tpl = make_semi_cigar_plan(ps, tshape, has_ops, &rc, &why);
+    if (rc) { set_error(why); return rc; }
+    const Plan spl = make_plan(ps, sized, has_ops);
+
+    // the score launch: the walk needs t_end whether the caller asked for it or not
+    gasalx_results so = {};
+    so.aln_score = out.aln_score; so.q_end = out.q_end; so.t_end = out.t_end;
+    if (!so.t_end) {
+        HIPCHK(ws.ends_t.reserve((size_t)n * 4));
+        so.t_end = ws.ends_t.as<int32_t>();
+    }
+    Call sc{ws, ps, spl, b, so, st, sized, n, false, b.q_batch, b.t_batch, ps.is_packed ? 1 : 0, so.q_end, so.t_end};
+    rc = pack_inputs(sc);
+    if (!rc) rc = size_traceback(sc, false);
+    if (!rc) rc = spl.kind == PLAN_WAVEFRONT ? run_wavefront(sc, false) : run_generic(sc);
+    if (rc) return rc;
+
+    // the flags launch over the sequences the score launch read (the packed words after ops), the walk
+    Call tc{ws, ps, tpl, b, out, st, tshape, n, true, sc.qsrc, sc.tsrc, sc.packed, so.q_end, so.t_end};
+    rc = size_traceback(tc, false);
+    if (!rc) rc = run_wavefront(tc, false);
+    if (!rc) rc = run_walk(tc, b.q_bytes, nullptr);
+    return rc;
 }
 
 // ----------------------------------------------------------------------------

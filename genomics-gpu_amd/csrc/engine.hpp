@@ -91,6 +91,8 @@ struct Plan {
     bool semi_tq = false;   // SEMI TAIL=QUERY/BOTH: packed class launches (one per padded target length), int32 fallback
     bool tb_band = false;   // packed GLOBAL+TB by band recomputation (wavefront16.hpp WF16_GLOBAL_CP / _BAND)
     uint32_t band_w = 0, band_wd = 0;
+    bool semi_tb = false;   // the direction-flag launch of gasalx_semi_cigar_* (make_semi_cigar_plan): GLOBAL's
+                            // traceback kernels under the semi-global boundary (WF16_SEMI_TB / SEMITB)
     uint32_t max_q = 0, max_t = 0;   // the batch shape the plan was made for
     std::string name;
 };
@@ -106,6 +108,11 @@ struct BatchShape {
 };
 
 Plan make_plan(const gasalx_params &p, const BatchShape &shape, bool has_ops);
+
+// The direction-flag launch of gasalx_semi_cigar_* (SEMI-GLOBAL, HEAD = TAIL = TARGET, with CIGARs):
+// PLAN_WAVEFRONT, or PLAN_NONE with *why and a GASALX_E* code in *rc when the scores or the lengths
+// have no wavefront form.  The score launch that runs before it is make_plan's, unchanged.
+Plan make_semi_cigar_plan(const gasalx_params &p, const BatchShape &shape, bool has_ops, int *rc, std::string *why);
 
 // Host-side check for BatchShape::sort: the padded lengths of the step axis
 // (targets; queries for SEMI-GLOBAL, whose kernel runs transposed) spread over
@@ -140,6 +147,12 @@ inline bool one_pad8(const uint32_t *t_lens, uint32_t n, uint32_t max_t) {
 // cigar_cap: bytes writable at out.cigar (0 = b.q_bytes)
 int align_device(Workspace &ws, const gasalx_params &p, const gasalx_batch &b, const gasalx_results &out,
                  hipStream_t stream, const BatchShape &shape, uint64_t cigar_cap = 0);
+
+// SEMI-GLOBAL with HEAD = TAIL = TARGET and the alignment itself: the score launch of align_device
+// (score, ends), the direction-flag launch, the walk (CIGAR bytes, op counts, starts).  sort_t: the
+// target lengths are uneven (the flag launch runs its slots in target-length order).
+int semi_cigar_device(Workspace &ws, const gasalx_params &p, const gasalx_batch &b, const gasalx_results &out,
+                      hipStream_t stream, const BatchShape &shape, bool sort_t);
 
 int pairhmm_device(Workspace &ws, const gasalx_hmm_batch &b, float *result, hipStream_t stream, uint32_t max_r,
                    uint32_t max_h);

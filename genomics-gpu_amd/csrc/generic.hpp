@@ -571,7 +571,7 @@ struct TbArgs {
     uint32_t *n_ops;
     uint32_t n;
     int32_t a, b, o, e;
-    int32_t is_local;
+    int32_t is_local;                   // 0 GLOBAL, 1 LOCAL, 2 SEMI-GLOBAL with HEAD = TAIL = TARGET (kTbSemi)
     // pairs aligned by the packed GLOBAL+TB kernel (wavefront16.hpp) use its
     // skewed uint16 layout: flag per block of pk_ppb pairs, R rows per lane
     const uint8_t *pk_flags;
@@ -603,6 +603,14 @@ struct TbArgs {
     uint32_t n_dev_off, tb_slot;
 };
 
+// TbArgs::is_local == kTbSemi (gasalx_semi_cigar_*): the GLOBAL state machine from the end cell itself
+// -- last query row, column tend[pair], in H state, no cell one past the sequences -- until the
+// query is exhausted, a gap run ending in the H state of the cell it was opened from (the direction
+// words are those of the semi-global matrix, whose gaps open from H: wavefront16.hpp WF16_SEMI_TB); the target bases left of that point are the free head and give no ops.
+// A path that reaches column -1 first ends in the left boundary's insertions, as GLOBAL's does.
+// t_start = the first target base consumed (t_end + 1 when none is), q_start = 0.
+constexpr int32_t kTbSemi = 2;
+
 // 8 codes of a sequence cached per thread (the walk moves one position at a time)
 __device__ __forceinline__ uint32_t tb_code(const uint8_t *seq, uint32_t off, uint32_t pos, int packed, uint2 &v,
                                             int32_t &key) {
@@ -629,7 +637,8 @@ __global__ __launch_bounds__(256) void tb_kernel(TbArgs A) {
     const uint32_t *tb = A.tb + (uint64_t)(A.tb_slot ? slot : tid) * A.tb_pair_words;
     const int32_t OE = A.o + A.e;
     int i, j, total = 0, curr = 0;
-    if (A.is_local) { i = A.tend[tid]; j = A.qend[tid]; total = A.score[tid]; }
+    if (A.is_local == kTbSemi) { i = A.tend[tid]; j = (int)ql - 1; }
+    else if (A.is_local) { i = A.tend[tid]; j = A.qend[tid]; total = A.score[tid]; }
     else { i = (int)tl; j = (int)ql; }
     const bool reg2 = slot >= A.pk_p1;   // the second shape of a mixed DP launch
     const bool pk = A.pk_flags && A.pk_flags[reg2 ? A.pk_b1 + (slot - A.pk_p1) / A.pk_ppb2 : slot / A.pk_ppb];
@@ -652,7 +661,7 @@ __global__ __launch_bounds__(256) void tb_kernel(TbArgs A) {
     // packed kernel: the start cell (ql, tl), both pads, was scored with the pad
     // row's -K instead of N==N.  Its E and F are exact, so with H' the value it
     // did compute, the true cell takes the diagonal iff score + sc(N,N) >= H'.
-    bool fix_diag = pk && !A.is_local && (ql & 7) && (tl & 7) && A.score[tid] + A.sc_nn >= A.pk_fix[tid];
+    bool fix_diag = pk && A.is_local == 0 && (ql & 7) && (tl & 7) && A.score[tid] + A.sc_nn >= A.pk_fix[tid];
     uint8_t *out = A.cigar + A.qoff[tid];
     const uint64_t room = A.cigar_cap > A.qoff[tid] ? A.cigar_cap - A.qoff[tid] : 0;
     auto put = [&](int at, uint32_t byte) { if ((uint64_t)at < room) out[at] = (uint8_t)byte; };
@@ -731,6 +740,13 @@ __global__ __launch_bounds__(256) void tb_kernel(TbArgs A) {
             }
         }
         const uint32_t op = (cell_op >> op_shift) & (uint32_t)op_select;
+        if (A.is_local == kTbSemi && op_select == 1 && op == 0) {
+            // the run was opened from this cell's H (the semi-global matrix opens gaps from H): its
+            // low two bits say where that came from; no op, no move
+            op_select = 3;
+            op_shift = 0;
+            continue;
+        }
         opf = (op == 0 || op_select == 3) ? op : (uint32_t)op_shift;
         op_select = (op == 0 || (op == 1 && op_select == 3)) ? 3 : 1;
         op_shift = (op == 0 || (op == 1 && op_select == 3)) ? 0 : ((op == 2 || op == 3) ? (int)op : op_shift);
@@ -740,7 +756,7 @@ __global__ __launch_bounds__(256) void tb_kernel(TbArgs A) {
             if (count > 0) { put(off++, prev | (uint32_t)(count << 2)); n_ops++; }
             count = 1;
         }
-        if (A.is_local) {
+        if (A.is_local == 1) {
             curr += ((opf == 2 || opf == 3) && prev != opf) ? -OE
                   : ((opf == 2 || opf == 3) ? -A.e : (opf == 1 ? -A.b : A.a));
             if (curr == total) break;
@@ -755,7 +771,11 @@ __global__ __launch_bounds__(256) void tb_kernel(TbArgs A) {
     }
     put(off++, prev | (uint32_t)(count << 2));
     n_ops++;
-    if (!A.is_local) {
+    if (A.is_local == kTbSemi) {
+        while (j >= 0) { const int rc = (j + 1) <= 63 ? (j + 1) : 63; put(off++, 3u | (uint32_t)(rc << 2)); n_ops++; j -= 63; }
+        if (A.tstart) A.tstart[tid] = i + 1;
+        if (A.qstart) A.qstart[tid] = 0;
+    } else if (!A.is_local) {
         while (i >= 0) { const int rc = (i + 1) <= 63 ? (i + 1) : 63; put(off++, 2u | (uint32_t)(rc << 2)); n_ops++; i -= 63; }
         while (j >= 0) { const int rc = (j + 1) <= 63 ? (j + 1) : 63; put(off++, 3u | (uint32_t)(rc << 2)); n_ops++; j -= 63; }
     } else {

@@ -170,7 +170,12 @@ __device__ __forceinline__ uint32_t load4_codes_dir(const WfArgs &A, const uint8
     return A.rev ? load4_codes_rev(base, off, L, w, A.packed, (uint32_t)A.nval) : load4_codes(base, off, w, A.packed);
 }
 
-template <int ALGO, bool KEYS, bool TB, int G, int R, bool EXACT, bool STOP>
+// SEMITB (ALGO = WF_GLOBAL with TB; gasalx_semi_cigar_*, semi_tb.hip): GLOBAL's direction nibbles over the
+// semi-global kernels' matrix for HEAD = TARGET -- H(-1, c) = 0 and F(0, c) = -(o + e) above row 0, E(r, 0)
+// = H(r, -1) - (o + e) (semiglobal_kernel_template.h:87-99,123-128), gaps opened from H (:17-28; bits 2
+// and 3 test H - OE against E - e and F - e), the LOCAL N rule -- and no score: the SEMI score launch
+// has written it.
+template <int ALGO, bool KEYS, bool TB, int G, int R, bool EXACT, bool STOP, bool SEMITB = false>
 __device__ __forceinline__ void wf_body(const WfArgs &A, const uint8_t *tcodes, const uint32_t lg,
                                         const uint32_t pair, const uint32_t tbi, const bool valid, const uint32_t ql,
                                         const uint32_t tl, const uint32_t qpad, const uint32_t tpad,
@@ -196,7 +201,7 @@ __device__ __forceinline__ void wf_body(const WfArgs &A, const uint8_t *tcodes, 
             Hk[k] = 0; Ek[k] = 0;                               // local_kernel_template.h:118-120
         } else if (ALGO == WF_GLOBAL) {
             Hk[k] = (r == 0) ? 0 : -(A.o + A.e * r);            // global.h:57-60 (Q2)
-            Ek[k] = -32768;
+            Ek[k] = SEMITB ? Hk[k] - OE : -32768;
         } else {
             const int32_t h = head_q ? 0 : ((r == 0) ? 0 : -(A.o + A.e * r));   // semiglobal :87-99
             Hk[k] = h - OE;
@@ -223,7 +228,10 @@ __device__ __forceinline__ void wf_body(const WfArgs &A, const uint8_t *tcodes, 
         int32_t diag, f;
         if (lg == 0) {
             if (ALGO == WF_LOCAL) { diag = 0; f = 0; }                    // p[],f[] reset per strip
-            else if (ALGO == WF_GLOBAL) {
+            else if (ALGO == WF_GLOBAL && SEMITB) {
+                diag = 0;
+                f = -OE;
+            } else if (ALGO == WF_GLOBAL) {
                 diag = (c <= 0) ? 0 : -(A.o + A.e * c);                    // global.h:70
                 f = -32768;                                                // global.h:69
             } else {
@@ -241,14 +249,14 @@ __device__ __forceinline__ void wf_body(const WfArgs &A, const uint8_t *tcodes, 
             const uint32_t tc = tcodes[c];
             const bool tN = (int32_t)tc == A.nval;
             int32_t Mt, Xt;
-            if (ALGO == WF_GLOBAL) {
+            if (ALGO == WF_GLOBAL && !SEMITB) {
                 Mt = (A.has_npen && tN) ? -A.npen : A.a;
                 Xt = (A.has_npen && tN) ? -A.npen : -A.b;
             } else {
                 Mt = tN ? NS : A.a;
                 Xt = tN ? NS : -A.b;
             }
-            const int32_t NQ = (ALGO == WF_GLOBAL) ? -A.npen : NS;
+            const int32_t NQ = (ALGO == WF_GLOBAL && !SEMITB) ? -A.npen : NS;
             if (ALGO == WF_SEMI) { Mt += OE; Xt += OE; }
             int32_t Cc = 0;
             if (KEYS) {
@@ -258,7 +266,7 @@ __device__ __forceinline__ void wf_body(const WfArgs &A, const uint8_t *tcodes, 
 #pragma unroll
             for (int k = 0; k < R; ++k) {
                 int32_t sc = (qc[k] == tc) ? Mt : Xt;
-                if (EXACT && (ALGO != WF_GLOBAL || A.has_npen)) sc = qn[k] ? (ALGO == WF_SEMI ? NQ + OE : NQ) : sc;
+                if (EXACT && (ALGO != WF_GLOBAL || SEMITB || A.has_npen)) sc = qn[k] ? (ALGO == WF_SEMI ? NQ + OE : NQ) : sc;
                 if (ALGO == WF_SEMI) {
                     // CORE_COMPUTE_SEMIGLOBAL (semiglobal_kernel_template.h:17-28)
                     const int32_t E = max(Hk[k], Ek[k] - ext);          // E(r,c)
@@ -282,7 +290,7 @@ __device__ __forceinline__ void wf_body(const WfArgs &A, const uint8_t *tcodes, 
                     const int32_t tmp = diag + sc;
                     int32_t H = max3(tmp, f, Ek[k]);
                     if (ALGO == WF_LOCAL) H = max(H, 0);
-                    const int32_t toe = tmp - OE;
+                    const int32_t toe = (SEMITB ? H : tmp) - OE;
                     const int32_t fm = f - ext;
                     const int32_t em = Ek[k] - ext;
                     if (TB) {
@@ -309,7 +317,7 @@ __device__ __forceinline__ void wf_body(const WfArgs &A, const uint8_t *tcodes, 
                     }
                 }
             }
-            if (ALGO == WF_GLOBAL && (uint32_t)c == tl - 1 && lg == kq_lane) {
+            if (ALGO == WF_GLOBAL && !SEMITB && (uint32_t)c == tl - 1 && lg == kq_lane) {
                 int32_t h = 0;
 #pragma unroll
                 for (int k = 0; k < R; ++k) h = (k == (int)kq) ? Hk[k] : h;
@@ -414,7 +422,7 @@ __device__ __forceinline__ void wf_body(const WfArgs &A, const uint8_t *tcodes, 
 }
 
 // One block's pairs (virtual block bx) of the int32 kernel.
-template <int ALGO, bool KEYS, bool TB, int G, int R, bool STOP>
+template <int ALGO, bool KEYS, bool TB, int G, int R, bool STOP, bool SEMITB = false>
 __device__ __forceinline__ void wf_block(const WfArgs &A, uint8_t *lds, const uint32_t bx) {
     constexpr int P = 64 / G;
     const uint32_t lane = threadIdx.x & 63;
@@ -479,12 +487,12 @@ __device__ __forceinline__ void wf_block(const WfArgs &A, uint8_t *lds, const ui
 
     // exact substitution only when a real query N could change a pad-free cell
     bool exact = A.force_exact != 0;
-    if (ALGO != WF_GLOBAL || A.has_npen) exact = exact || __any(has_n);
+    if (ALGO != WF_GLOBAL || SEMITB || A.has_npen) exact = exact || __any(has_n);
     if (exact)
-        wf_body<ALGO, KEYS, TB, G, R, true, STOP>(A, tcodes, lg, pair, A.tb_slot ? idx : pair, valid, ql, tl, qpad, tpad,
+        wf_body<ALGO, KEYS, TB, G, R, true, STOP, SEMITB>(A, tcodes, lg, pair, A.tb_slot ? idx : pair, valid, ql, tl, qpad, tpad,
                                                  nsteps, qc, qn);
     else
-        wf_body<ALGO, KEYS, TB, G, R, false, STOP>(A, tcodes, lg, pair, A.tb_slot ? idx : pair, valid, ql, tl, qpad, tpad,
+        wf_body<ALGO, KEYS, TB, G, R, false, STOP, SEMITB>(A, tcodes, lg, pair, A.tb_slot ? idx : pair, valid, ql, tl, qpad, tpad,
                                                  nsteps, qc, qn);
 }
 
@@ -515,5 +523,29 @@ __global__ __launch_bounds__(kBlock) void wf_kernel(WfArgs A) {
             wf_block<ALGO, KEYS, TB, G, R, STOP>(A, lds, base + (uint32_t)__builtin_ctzll(m) * gridDim.x);
     }
 }
+
+// wf_kernel's loop over the GLOBAL + traceback block under the semi-global boundary (wf_body SEMITB)
+template <int G, int R>
+__global__ __launch_bounds__(kBlock) void wf_semi_tb_kernel(WfArgs A) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    constexpr uint32_t PPB = kWavesPerBlock * (64 / G);
+    const uint32_t nblk = (A.n + PPB - 1) / PPB;
+    const uint32_t lane = threadIdx.x & 63;
+    for (uint32_t base = blockIdx.x; base < nblk; base += 64 * gridDim.x) {
+        const uint32_t bx = base + lane * gridDim.x;
+        bool run = bx < nblk;
+        if (run && A.skip) {
+            const uint32_t f0 = skip_flag(A, bx * PPB), f1 = skip_flag(A, min(bx * PPB + PPB, A.n) - 1);
+            bool all = true;
+            for (uint32_t f = f0; f <= f1; ++f) all &= A.skip[f] != 0;
+            run = !all;
+        }
+        for (uint64_t m = __ballot(run); m; m &= m - 1)
+            wf_block<WF_GLOBAL, false, true, G, R, false, true>(A, lds, base + (uint32_t)__builtin_ctzll(m) * gridDim.x);
+    }
+}
+
+// its instances (semi_tb.hip): the R % 4 == 0 shapes, NULL for any other
+void (*wf_semi_tb_lookup(int G, int R))(WfArgs);
 
 }  // namespace gx

@@ -432,17 +432,21 @@ __device__ __forceinline__ void step_local_tb_dr(const uint2 T, const uint32_t d
     f_out = f;
 }
 
-template <int R, bool SYNC = false>
+// HB (WF16_SEMI_TB): gaps open from H, as the semi-global kernels' cell does (semiglobal_kernel_template.h:
+// 17-28), not from the diagonal candidate: E' = max(H - OE, E - e), and x / y test H - OE against E - e /
+// F - e.  In the frame H - OE one anti-diagonal on is the stored H less o (GOC): one subtract more per cell.
+template <int R, bool SYNC = false, bool HB = false>
 __device__ __forceinline__ void step_global_tb(const uint2 T, const uint32_t diag_top, const uint32_t f_top,
                                                const uint32_t (&xs)[R], const uint32_t (&Hin)[R],
                                                uint32_t (&Hout)[R], uint32_t (&Ek)[R], uint32_t (&dw)[R],
                                                uint32_t &f_out, const uint32_t KX, const uint32_t OEX,
-                                               const uint32_t NN, const int j) {
+                                               const uint32_t NN, const int j, const uint32_t GOC = 0) {
     const uint32_t M1 = 0x01010101u << j, M2 = 0x10101010u << j;
     uint32_t diag = diag_top, f = f_top, tx = T.x, ty = T.y;
     // one cell from tmp = diag + v - KX and toe = diag + v - OEX (drift e: see step_global)
-    auto cell = [&](const int k, const uint32_t tmp, const uint32_t toe) __attribute__((always_inline)) {
+    auto cell = [&](const int k, const uint32_t tmp, const uint32_t toe_) __attribute__((always_inline)) {
         const uint32_t H = pk_max3(tmp, f, Ek[k]);
+        const uint32_t toe = HB ? pk_subnb(H, GOC) : toe_;   // what a gap opens from, less OE
         const uint32_t em = Ek[k], fm = f;               // E - e and F - e, in the frame
         const uint32_t En = pk_max3(toe, em, NN);
         const uint32_t Fn = pk_max3(toe, fm, NN);
@@ -638,6 +642,17 @@ constexpr int WF16_LOCAL_U16_RS = 12; // the same with u16 keys (local_rs.hip in
 constexpr int WF16_LOCAL_SEG = 13;
 constexpr int WF16_LOCAL_TBD = 14;    // LOCAL + traceback in the e-drift frame (step_local_tb_dr)
 constexpr int kW16_LTBD_WAVES = 2;
+// SEMI-GLOBAL (HEAD = TAIL = TARGET) direction flags for gasalx_semi_cigar_* (semi_tb.hip): the
+// WF16_GLOBAL_TB sweep -- query rows in registers, target on the step axis, step_global_tb's cell
+// and flags in the same skewed windows -- with the free target head above row 0: H(-1, c) = 0 for
+// every column and F(0, c) = -(o + e), the value the semi-global kernels hold there
+// (semiglobal_kernel_template.h:123-128 with HEAD = TARGET), E(r, 0) = H(r, -1) - (o + e) on the left,
+// and gaps opened from H (step_global_tb HB): the semi-global kernels' matrix, cell for cell.  In the
+// e-drift frame the top boundary is one value per step, the same in every top lane: scalar.  No score or end capture: the last query row
+// sits at a per-pair register index, and the packed SEMI score launch that runs first on the
+// stream leaves the score and t_end, which the walk reads (generic.hpp tb_kernel, SEMI mode).
+constexpr int WF16_SEMI_TB = 15;
+constexpr int kW16_STB_WAVES = 2;
 constexpr int kW16_TQ_WAVES = 3;
 constexpr int kW16_TQ_BIG_WAVES = 3;   // R > 20: 3 waves spill (R = 23: 20 VGPRs) and still beat 2 (profiles/r03_semi_tq_waves_ab.md)
 constexpr int kW16_CP_WAVES = 3;    // GLOBAL score sweep with band checkpoints, then its band pass
@@ -647,6 +662,7 @@ __host__ __device__ constexpr int wf16_waves(int algo, int R) {
     return algo == WF16_GLOBAL_TB ? kW16_TB_WAVES
            : algo == WF16_LOCAL_TB ? kW16_LTB_WAVES
            : algo == WF16_LOCAL_TBD ? kW16_LTBD_WAVES
+           : algo == WF16_SEMI_TB ? kW16_STB_WAVES
            : algo == WF16_LOCAL_K2 ? kW16_K2_WAVES
            : algo == WF16_SEMI_TQ ? (R > 20 ? kW16_TQ_BIG_WAVES : kW16_TQ_WAVES)
            : algo == WF16_GLOBAL_CP ? kW16_CP_WAVES
@@ -734,5 +750,7 @@ Wf16Fn wf16_local_lookup(int G, int R, bool u16, bool rs, bool seg = false);
 // WITH_START reverse passes with the register axis sized per block (rclass.hip): NULL when the
 // plan's instance (algo, G, R) has no class set
 Wf16Fn wf16_rclass_lookup(int algo, int G, int R);
+// SEMI-GLOBAL direction flags (semi_tb.hip, WF16_SEMI_TB): the R % 4 == 0 shapes, NULL for any other
+Wf16Fn wf16_semi_tb_lookup(int G, int R);
 
 }  // namespace gx

@@ -8,7 +8,8 @@
 // the compiler's decisions for the sweep: the SEMI G8R23 loop issued 21 VALU and 71 SALU more
 // per trip, 1.7-4.7 % slower, profiles/r05/g_rclass.md.)
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    constexpr bool GTB = ALGO_ == WF16_GLOBAL_TB;
+    constexpr bool STB = ALGO_ == WF16_SEMI_TB;   // GLOBAL_TB's sweep under the free target head, no captures
+    constexpr bool GTB = ALGO_ == WF16_GLOBAL_TB || STB;
     constexpr bool GCP = ALGO_ == WF16_GLOBAL_CP;
     constexpr bool GT = GTB || GCP;   // the traceback kernels' declines and start-cell capture
     constexpr bool LTB = ALGO_ == WF16_LOCAL_TB;
@@ -629,7 +630,11 @@
         uint32_t HA[R], HB[R], Ek[R];
         uint32_t dw[GTB ? R : 1];                      // traceback nibbles: last 4 steps per half
 #pragma unroll
-        for (int k = 0; k < R; ++k) { HA[k] = left((int32_t)(r0 + k)); HB[k] = HA[k]; Ek[k] = NN; }
+        for (int k = 0; k < R; ++k) {
+            HA[k] = left((int32_t)(r0 + k));
+            HB[k] = HA[k];
+            Ek[k] = STB ? pk_subnb(HA[k], GO) : NN;
+        }
 #pragma unroll
         for (int k = 0; k < (GTB ? R : 1); ++k) dw[k] = 0;
         uint32_t recvH = left((int32_t)r0 - 1), prevRecvH = recvH, recvF = NN, f = NN;
@@ -643,7 +648,7 @@
             // traceback starts at (row ql, column tl) (SURVEY Q9); when both are pad
             // positions this kernel scores that cell -K instead of N==N, and records
             // its H so tb_kernel can redo the cell's low two bits
-            fixable[h] = GT && valid[h] && xl[h] < xpad[h] && yl[h] < ypad[h];
+            fixable[h] = GT && !STB && valid[h] && xl[h] < xpad[h] && yl[h] < ypad[h];
             kp_lane[h] = xl[h] / R;
             kp[h] = xl[h] - kp_lane[h] * R;
         }
@@ -666,7 +671,7 @@
         uint32_t cap_lo = 0xFFFFFFFFu, cap_hi = 0;
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            if (valid[h]) {
+            if (valid[h] && !STB) {
                 const uint32_t sq = yl[h] - 1 + kq_lane[h];
                 cap_lo = min(cap_lo, sq);
                 cap_hi = max(cap_hi, sq);
@@ -682,6 +687,7 @@
             cap_lo = min(cap_lo, (uint32_t)__shfl_xor(cap_lo, m));
             cap_hi = max(cap_hi, (uint32_t)__shfl_xor(cap_hi, m));
         }
+        uint32_t s = 0;
         // FLG bit 0: a lane may reach column -1 (its reset to the left boundary) in this
         // phase; bit 1: captures
         auto half_step = [&](auto flg, const int32_t cc, const int j, uint32_t (&Hin)[R], uint32_t (&Hout)[R]) __attribute__((always_inline)) {
@@ -693,7 +699,10 @@
                 // the same value pb - e - o, row 0 pb - e (the general form, per register, cost
                 // ~60 VALU per step of the first G steps)
 #pragma unroll
-                for (int k = 0; k < R; ++k) { Hout[k] = k == 0 && r0 == 0 ? L_0 : L_in; Ek[k] = NN; }
+                for (int k = 0; k < R; ++k) {
+                    Hout[k] = k == 0 && r0 == 0 ? L_0 : L_in;
+                    Ek[k] = STB ? pk_subnb(Hout[k], GO) : NN;   // STB: E(r, 0) = H(r, -1) - OE
+                }
                 f = NN;
                 if (GTB && j == 0) {
 #pragma unroll
@@ -702,12 +711,20 @@
             } else {
                 // H(-1, c-1) at anti-diagonal c - 2
                 const uint32_t dtop = (uint32_t)(pb + D * (cc - 2) - (cc <= 0 ? 0 : go + ge * cc)) * 0x10001u;
-                if constexpr (GTB)
+                if constexpr (STB) {
+                    // free target head: H(-1, c-1) = 0 at anti-diagonal c - 2 and F(0, c) = -(o + e) at c;
+                    // a top lane's column is the step itself (c = s + j), so both are scalar
+                    const int32_t cs = (int32_t)s + j;
+                    const uint32_t dfree = (uint32_t)(pb + D * (cs - 2)) * 0x10001u;
+                    const uint32_t ffree = (uint32_t)(pb - go - ge + D * cs) * 0x10001u;
+                    step_global_tb<R, false, true>(T, top ? dfree : prevRecvH, top ? ffree : recvF, xs, Hin, Hout, Ek,
+                                                   dw, f, KX, OEX, NN, j, GO);
+                } else if constexpr (GTB)
                     step_global_tb<R>(T, top ? dtop : prevRecvH, top ? NN : recvF, xs, Hin, Hout, Ek, dw, f, KX,
                                       OEX, NN, j);
                 else
                     step_global<R, GCP>(T, top ? dtop : prevRecvH, top ? NN : recvF, xs, Hin, Hout, Ek, f, KX, OEX, NN);
-                if constexpr ((FLG & 2) != 0) {
+                if constexpr ((FLG & 2) != 0 && !STB) {
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
                         if (valid[h] && cc == (int32_t)yl[h] - 1 && lg == kq_lane[h]) {   // global.h:98-103,299
@@ -751,7 +768,6 @@
 #pragma unroll
         for (int h = 0; h < 2; ++h) W16[h] = (ypad[h] + G + 2) >> 2;
         constexpr uint32_t STEP = GTB ? 4 : 2;
-        uint32_t s = 0;
         auto run = [&](auto flg, const uint32_t end) __attribute__((always_inline)) {
             for (; s < end; s += STEP, c += STEP) {
                 if constexpr (GTB) {
@@ -788,7 +804,7 @@
         }
 #pragma unroll
         for (int h = 0; h < 2; ++h)
-            if (valid[h] && lg == kq_lane[h]) A.score[pr[h]] = score[h];
+            if (!STB && valid[h] && lg == kq_lane[h]) A.score[pr[h]] = score[h];
         if constexpr (GCP) {
             // the band pass right behind the sweep, in the same wave: no second prologue, and the
             // checkpoints and hand-offs just written (this wave's own stores) are read from L2

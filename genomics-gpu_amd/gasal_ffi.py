@@ -29,6 +29,7 @@ N_CODE = 0x4E
 EXPORTS = (
     "gasalx_abi_version", "gasalx_last_error", "gasalx_device_count", "gasalx_engine_create",
     "gasalx_engine_destroy", "gasalx_align_device", "gasalx_align_host", "gasalx_describe_plan",
+    "gasalx_semi_cigar_device", "gasalx_semi_cigar_host", "gasalx_describe_semi_cigar_plan",
     "gasalx_pairhmm_device", "gasalx_pairhmm_host", "gasalx_pairhmm_params", "gasalx_synth_sizes",
     "gasalx_synth_spec", "gasalx_synth_pairs", "gasalx_synth_range", "gasalx_host_alloc", "gasalx_host_free",
     "gasalx_pairhmm_quals_device", "gasalx_pairhmm_quals_host", "gasalx_hmm_file_read", "gasalx_hmm_file_free",
@@ -323,6 +324,38 @@ class Engine:
         out["cigar"] = cigar
         out["n_ops"] = n_ops
         return out
+
+    def semi_cigar_host(self, batch: Batch, params: Params, q_ops=None, t_ops=None, max_q_len=0, max_t_len=0):
+        """SEMI_GLOBAL, HEAD = TAIL = TARGET, with the alignment (gasalx_semi_cigar_host): the dict
+        align_host returns for WITHOUT_START (score, q_end, t_end) plus t_start, q_start, cigar (uint8,
+        q_bytes; decode_cigar reads it) and n_ops."""
+        n = batch.n
+        out = {k: np.full(n, SENTINEL, np.int32) for k in ("score", "q_end", "t_end", "q_start", "t_start")}
+        cigar = np.zeros(batch.q_bytes, np.uint8)
+        n_ops = np.zeros(n, np.uint32)
+        qo = None if q_ops is None else np.ascontiguousarray(q_ops, np.uint8)
+        to = None if t_ops is None else np.ascontiguousarray(t_ops, np.uint8)
+        cb = CBatch(_p(batch.q_data), _p(batch.q_offsets), _p(batch.q_lens), _p(batch.t_data), _p(batch.t_offsets),
+                    _p(batch.t_lens), batch.q_bytes, batch.t_bytes, n, _p(qo), _p(to), None, max_q_len, max_t_len)
+        cr = CResults(_p(out["score"]), _p(out["q_end"]), _p(out["t_end"]), _p(out["q_start"]), _p(out["t_start"]),
+                      None, None, None, _p(cigar), _p(n_ops))
+        _check(lib().gasalx_semi_cigar_host(self._h, ctypes.byref(params), ctypes.byref(cb), ctypes.byref(cr)),
+               "semi_cigar_host")
+        out["cigar"] = cigar
+        out["n_ops"] = n_ops
+        return out
+
+    def semi_cigar_device_ptrs(self, params: Params, ptrs: dict, q_bytes: int, t_bytes: int, n: int, max_q: int,
+                               max_t: int, stream: int = 0):
+        """Device-resident gasalx_semi_cigar_device: ptrs as align_device_ptrs (aln_score, cigar and
+        n_cigar_ops required; cigar a buffer of its own)."""
+        g = lambda k: ptrs.get(k) or None
+        cb = CBatch(g("q_batch"), g("q_offsets"), g("q_lens"), g("t_batch"), g("t_offsets"), g("t_lens"), q_bytes,
+                    t_bytes, n, g("q_ops"), g("t_ops"), None, max_q, max_t)
+        cr = CResults(g("aln_score"), g("q_end"), g("t_end"), g("q_start"), g("t_start"), g("aln_score2"),
+                      g("q_end2"), g("t_end2"), g("cigar"), g("n_cigar_ops"))
+        _check(lib().gasalx_semi_cigar_device(self._h, ctypes.byref(params), ctypes.byref(cb), ctypes.byref(cr),
+                                              ctypes.c_void_p(stream or None)), "semi_cigar_device")
 
     def packed_pairs(self):
         """(handled, total): pairs of the last packed launches the packed kernels aligned themselves
@@ -721,6 +754,14 @@ def synth_spec(kind: int):
 def describe_plan(params: Params, max_q: int, max_t: int) -> str:
     buf = ctypes.create_string_buffer(128)
     _check(lib().gasalx_describe_plan(ctypes.byref(params), max_q, max_t, buf, 128), "describe_plan")
+    return buf.value.decode()
+
+
+def describe_semi_cigar_plan(params: Params, max_q: int, max_t: int) -> str:
+    """The kernel family of gasalx_semi_cigar_*'s direction-flag launch; raises what the call would."""
+    buf = ctypes.create_string_buffer(128)
+    _check(lib().gasalx_describe_semi_cigar_plan(ctypes.byref(params), max_q, max_t, buf, 128),
+           "describe_semi_cigar_plan")
     return buf.value.decode()
 
 

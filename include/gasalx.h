@@ -129,6 +129,34 @@ int gasalx_host_free(void *ptr);
 int gasalx_describe_plan(const gasalx_params *params, uint32_t max_q_len, uint32_t max_t_len, char *buf,
                          uint32_t buf_len);
 
+/* SEMI_GLOBAL with HEAD = TARGET and TAIL = TARGET, with the alignment itself -- what a read mapper
+ * asks for and what the reference's semi-global kernel cannot give (it has no traceback branch;
+ * gasalx_align_* with WITH_TB keeps the reference's behaviour there).  params->algo must be
+ * SEMI_GLOBAL, second_best FALSE; any other HEAD / TAIL is GASALX_EUNSUPPORTED; start_pos is ignored.
+ *   aln_score, q_end, t_end   what gasalx_align_* returns with WITHOUT_START, bit for bit
+ *   cigar, n_cigar_ops        reversed RLE bytes count << 2 | op (0 M, 1 X, 2 D, 3 I) at each pair's
+ *                             query offset; a pair's ops consume its whole query and the target
+ *                             bases t_start .. t_end.  cigar must be a buffer of its own, q_bytes
+ *                             long (GASALX_EINVAL when it overlaps q_batch); bytes past a pair's
+ *                             ops are not written by the device form and are 0 from the host form
+ *   t_start                   the first target base the path consumes (t_end + 1 when it consumes
+ *                             none); q_start = 0
+ * Required outputs: aln_score, cigar, n_cigar_ops; the second-best fields must be NULL.  q_ops /
+ * t_ops and is_packed as in gasalx_align_*.  A gap run ends in the cell it was opened from (the
+ * semi-global matrix opens gaps from H), so an I run may stand next to a D run.  A negative
+ * gap_open or gap_extend is GASALX_EUNSUPPORTED; lengths with no wavefront shape (a padded query
+ * over 1,280, LDS over 160 KB, or lengths x scores past the int16 range the semi-global kernels
+ * keep) are GASALX_ERANGE.  The device form is asynchronous on `stream`
+ * when max_q_len / max_t_len are given.  gasalx_describe_semi_cigar_plan names the kernel family of
+ * the direction-flag launch ("wavefront16_semi_tb_G..R..", or "wavefront_semi_tb_G..R.." when
+ * every block takes the int32 kernel), or returns the error the call would. */
+int gasalx_semi_cigar_device(gasalx_engine *eng, const gasalx_params *params, const gasalx_batch *dev_batch,
+                             const gasalx_results *dev_out, void *stream);
+int gasalx_semi_cigar_host(gasalx_engine *eng, const gasalx_params *params, const gasalx_batch *host_batch,
+                           const gasalx_results *host_out);
+int gasalx_describe_semi_cigar_plan(const gasalx_params *params, uint32_t max_q_len, uint32_t max_t_len, char *buf,
+                                    uint32_t buf_len);
+
 /* Diagnostics: pairs of the engine's last packed (two-pairs-per-lane) launches that the packed
  * kernel aligned itself (*handled) out of the pairs those launches covered (*total); the rest went
  * to the int32 kernel.  The engine's own workspace and its two host-pipeline stages each count

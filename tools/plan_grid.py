@@ -4,7 +4,10 @@ the grid of tests/test_capi.py (plan_grid_names), from the library GASALX_LIB na
 tree's build).  No GPU needed.  With --nv: tests/golden/nv_plan_names.json, the names
 gasalx_nv_describe_plan and gasalx_nv_describe_sinks_plan give over nv_plan_grid_names' grid.
 
-usage: GASALX_LIB=/path/to/parent/libgasal.so plan_grid.py [--nv] COMMIT [OUT.json]
+With --semi-cigar: tests/golden/semi_cigar_plan_names.json, the names (or refusals)
+gasalx_describe_semi_cigar_plan gives over the grid of tests/test_semi_cigar_model.py, one row per key.
+
+usage: GASALX_LIB=/path/to/parent/libgasal.so plan_grid.py [--nv | --semi-cigar] COMMIT [OUT.json]
 
 A fixture pins its planner across host-side refactors, so it is written from a build of the
 commit *before* the change under test (COMMIT, recorded in the file), never from the branch.
@@ -20,10 +23,24 @@ sys.path[:0] = [os.path.join(ROOT, "genomics-gpu_amd"), os.path.join(ROOT, "orac
 import test_capi as T  # noqa: E402
 
 
+def semi_cigar(commit, out):
+    import test_semi_cigar_model as S
+    rows = S.semi_cigar_plan_rows(os.environ.__setitem__, lambda s: os.environ.pop(s, None))
+    doc = {"commit": commit, "lens": list(S.PLAN_LENS), "scores": [list(s) for s in S.PLAN_SCORES],
+           "envs": list(S.PLAN_ENVS), "rows": rows}
+    with open(out, "w") as f:
+        json.dump(doc, f, indent=0, sort_keys=True)
+        f.write("\n")
+    print(f"{len(rows)} rows -> {out}")
+
+
 def main():
     nv = "--nv" in sys.argv
-    args = [a for a in sys.argv[1:] if a != "--nv"]
+    args = [a for a in sys.argv[1:] if a not in ("--nv", "--semi-cigar")]
     commit = args[0]
+    if "--semi-cigar" in sys.argv:
+        return semi_cigar(commit, args[1] if len(args) > 1 else
+                          os.path.join(ROOT, "tests", "golden", "semi_cigar_plan_names.json"))
     out = args[1] if len(args) > 1 else os.path.join(ROOT, "tests", "golden",
                                                      "nv_plan_names.json" if nv else "plan_names.json")
     grid = T.nv_plan_grid_names if nv else T.plan_grid_names
