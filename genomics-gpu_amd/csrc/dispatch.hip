@@ -14,6 +14,7 @@
 #include "generic.hpp"
 #include "pairhmm.hpp"
 #include "ksw16.hpp"
+#include "plan.hpp"
 #include "start.hpp"
 #include "wavefront.hpp"
 #include "wavefront16.hpp"
@@ -42,14 +43,6 @@ void Workspace::release_all() {
     for (DevBuf *b : {&packed_q, &packed_t, &tb, &rows_h, &rows_e, &rev, &ends_q, &ends_t, &misc, &aux,
                       &rev_meta, &sort_meta, &band_cp, &band_stm, &band_fl, &band_fb, &kseg}) b->release();
 }
-
-// ----------------------------------------------------------------------------
-// the planner's shape lists, smallest first (wavefront16.hpp GX_SHAPES_R4 / GX_SHAPES_PK)
-struct Shape { int G, R; };
-#define GX_SHAPE(g, r) {g, r},
-static const Shape kShapes[] = {GX_SHAPES_R4(GX_SHAPE)};
-static const Shape kShapes16[] = {GX_SHAPES_PK(GX_SHAPE)};
-#undef GX_SHAPE
 
 using WfFn = void (*)(WfArgs);
 
@@ -89,422 +82,6 @@ static WfFn wf16_lookup(int algo, int G, int R, const Wf16Variant &v) {
                                                              : wf16_pick<WF_LOCAL>(G, R);
     if (algo == WF_GLOBAL) return v.tb ? wf16_pick_r4<WF16_GLOBAL_TB>(G, R) : wf16_pick<WF_GLOBAL>(G, R);
     return v.stop ? wf16_pick<WF16_SEMI_STOP>(G, R) : wf16_pick<WF_SEMI>(G, R);
-}
-
-// ----------------------------------------------------------------------------
-// The packed kernels' launch arithmetic, each formula written once: the planner, the tail shape,
-// the launch and the walk must agree on them, or a packed kernel overflows silently.
-// two pairs per group of G lanes
-static inline uint32_t pairs_per_wave(int G) { return 2 * (64 / G); }
-static inline uint32_t pairs_per_block(int G) { return kWavesPerBlock * (64 / G) * 2; }
-// largest row + column of any cell a G x R launch computes over y8 step-axis positions (packed16_ok)
-static inline int64_t packed_span(int G, int R, int64_t y8) { return (int64_t)G * R + y8 + 2 * G + 8; }
-// LDS per pair slot: uint2 per position, with the odd-step tail and the prefetch; and per block
-static inline uint32_t packed_lds_stride(uint32_t y8, int G) { return ((y8 + 2 * G + 4 + 3) & ~3u) * 8; }
-static inline size_t packed_lds_bytes(uint32_t y8, int G) {
-    return (size_t)kWavesPerBlock * (64 / std::max(G, 1)) * packed_lds_stride(y8, G);
-}
-// band traceback: the window of a lane with R rows and half width w, columns [max(lg*R - w, 0), + R + 2w)
-static inline uint32_t band_window(int R, uint32_t w) { return ((uint32_t)(R + 2 * w) + 3u) & ~3u; }
-// ceil(2^32 / R): the walk's division by R (generic.hpp TbArgs::pk_rmagic)
-static inline uint32_t rmagic(int R) { return (uint32_t)((0x100000000ull + R - 1) / R); }
-
-// packed LOCAL with the round-2 keys H*256 + (255 - column): H <= 255, 512 columns (two key
-// sets above 256), 256 with traceback
-static bool local_key16_ok(const gasalx_params &p, uint32_t mq, uint32_t mt) {
-    const int64_t a = p.match, b = p.mismatch, oe = (int64_t)p.gap_open + p.gap_extend;
-    const int64_t k = std::max<int64_t>(b, p.has_n_penalty ? p.n_penalty : 0);
-    const int64_t t8 = pad8(mt);
-    if (a * std::min(mq, mt) > 255 || t8 > (p.start_pos == 2 ? 256 : 512)) return false;
-    return 0x400 + oe + k + 16 + 255 + a + k + 64 <= 0x7BFF;
-}
-
-// LOCAL in the e-drift frame (wavefront16.hpp step_local_dr) for a shape G x R over q8 rows and y8
-// target columns: values B + H + e(r + c) over the shape's span stay in the window (`window`), the
-// top lane's first diagonal B - 2e stays above 0x0400 (`floor`), and the keys H*C + (C-1-c), which
-// rank kc = C + G steps (row k's carry e*k more, wf16_body.inc KA0, taken off after the sweep), fit
-// f16 patterns (`f16`)
-struct LocalDrift {
-    int64_t hmax, kc;
-    bool window, floor, f16;
-};
-static LocalDrift local_drift_frame(const gasalx_params &p, int64_t q8, int64_t y8, int G, int R) {
-    const int64_t a = std::max(p.match, 0), e = p.gap_extend, oe = (int64_t)p.gap_open + e;
-    const int64_t k = std::max<int64_t>(p.mismatch, p.has_n_penalty ? p.n_penalty : 0);
-    const int64_t hmax = a * std::min(q8, y8), base = 0x400 + oe + k + 16;
-    const int64_t span = packed_span(G, R, y8);
-    LocalDrift d;
-    d.hmax = hmax;
-    d.kc = y8 + G;
-    d.window = base + hmax + e * span + a + k + 64 <= 0x7BFF;
-    d.floor = base - 2 * e >= 0x400;
-    const int64_t hk = hmax + e * (R - 1);
-    d.f16 = (hk + 1) * d.kc <= 0x7800;
-    return d;
-}
-
-// The packed kernels (wavefront16.hpp) are exact when every stored value stays
-// inside [0x0400, 0x7BFF] (positive normal f16 patterns) and the score tables
-// fit bytes.  Mirrors pk16_params; returns false to keep the int32 kernel.
-static bool packed16_ok(const gasalx_params &p, int wf_algo, uint32_t mq, uint32_t mt, int32_t *vmin,
-                        int64_t span = 0) {
-    if (p.second_best || (p.start_pos == 1 && wf_algo == WF_GLOBAL)) return false;
-    if (p.start_pos == 2 && wf_algo == WF_SEMI) return false;     // no traceback for SEMI (reference)
-    // GLOBAL+TB reads the first pad query row, scored -K = -max(b, npen) there:
-    // exact for N-vs-base cells only if that equals the reference's -npen
-    if (p.start_pos == 2 && wf_algo == WF_GLOBAL && p.has_n_penalty && p.n_penalty < p.mismatch) return false;
-    if (p.match < 0 || p.mismatch < 0 || p.gap_open < 0 || p.gap_extend < 0) return false;
-    if (p.has_n_penalty && p.n_penalty < 0) return false;
-    const int64_t a = p.match, b = p.mismatch, oe = (int64_t)p.gap_open + p.gap_extend, e = p.gap_extend;
-    const int64_t npen = p.has_n_penalty ? p.n_penalty : 0;
-    const int64_t q8 = pad8(mq), t8 = pad8(mt);
-    if (wf_algo == WF_LOCAL) {
-        const int64_t k = std::max(b, npen);
-        if (a + k > 255) return false;   // table bytes
-        *vmin = 0;
-        // 16-bit keys H*256 + col: 256 columns each, a second key set up to 512 (not with traceback)
-        if (local_key16_ok(p, mq, mt)) return true;
-        // the e-drift kernels key on H*C + col (f16 patterns or u16; traceback: f16): make_plan
-        // checks their frame and key range for the chosen shape
-        return env_flag("GASALX_KF16", true);
-    }
-    int64_t k, top, drift = 0;
-    if (wf_algo == WF_SEMI) {
-        // TAIL=TARGET (last query row); TAIL=QUERY/BOTH score-only through the class launches
-        // (the last padded column, Q11): targets up to 256 (R <= 32), rows keyed in 16 bits
-        const bool tq = p.start_pos == 0 && (p.tail == 1 || p.tail == 3);
-        if (p.tail != 2 && !tq) return false;
-        if (tq && (t8 > 256 || q8 > 65535)) return false;
-        // table offset K = OE + e (wavefront16.hpp step_semi's frame): bytes s + K >= 0
-        if (oe + e < b || oe + e < npen) return false;
-        k = oe + e;
-    } else {
-        // GLOBAL: values drift by e per anti-diagonal, table offset K = max(2*ceil(max(b,
-        // npen)/2), 2e) (pk16_params, step_global).  Traceback reads the first pad query
-        // row, scored -K: keep the round-2 offset there (K == 2*ceil(max(b, npen)/2))
-        drift = e;
-        const int64_t k0 = 2 * ((std::max(b, npen) + 1) / 2);
-        k = std::max(k0, 2 * e);
-        if (p.start_pos == 2 && k != k0) return false;
-    }
-    if (a + k > 255) return false;
-    // span: largest row + column of any cell the launch computes.  Both halves of
-    // a register hold the same cell of two pairs of different lengths, so one
-    // pair's pad cells share 32-bit adds with the other's real cells: every
-    // computed cell (register rows up to G*R, steps past the longest sequence)
-    // must stay inside the window or a borrow corrupts the neighbour (SEMI keeps
-    // no floor on E/F; values fall by at most e per row or column along a gap).
-    // make_plan checks again with the chosen shape's span.
-    if (!span) span = q8 + t8 + 2 * 64 + 8;
-    const int64_t neg = 0x400 + 2 * e + 16;
-    if (wf_algo == WF_SEMI) {
-        // SEMI's frame (+ e per anti-diagonal): E and F never decay, every F is at least
-        // its column's top boundary and every E its row's left one, so no value falls
-        // below B - 3*OE whatever the span; values rise by the frame, e per row + column
-        // (the tail keys add up to e*(span) more to put the last row or column in one frame)
-        const int64_t v = 4 * oe + k + 64;
-        top = neg + v + a * std::min(q8, t8) + a + k + oe + 64 + e * (2 * span + 1);
-        if (top > 0x7BFF) return false;
-        *vmin = (int32_t)v;
-        return true;
-    }
-    const int64_t v = 4 * oe + k + e * span + 2 * drift + 64;   // below every reachable value
-    top = neg + v + a * std::min(q8, t8) + a + k + oe + 64 + drift * span;
-    if (top > 0x7BFF) return false;
-    *vmin = (int32_t)v;
-    return true;
-}
-
-// Largest |value| the DP can reach, to decide whether int32 arithmetic without
-// the reference's int16 row-buffer truncation is exact.
-static bool int16_safe(const gasalx_params &p, uint32_t mq, uint32_t mt) {
-    const int64_t L = (int64_t)pad8(mq) + pad8(mt) + 16;
-    const int64_t step = (int64_t)std::max({std::abs(p.match), std::abs(p.mismatch),
-                                            p.has_n_penalty ? std::abs(p.n_penalty) : 0}) +
-                         std::abs(p.gap_open) + std::abs(p.gap_extend);
-    return std::abs((int64_t)p.gap_open) + L * step < 30000;
-}
-
-// Packed banded kernel (banded16.hpp): stored values B + [0, Hmax] and keys
-// H*8 + 7 + 0x400 inside [0x0400, 0x7BFF]; pads score -b, which needs an N score
-// <= 0.  GASALX_BAND16=0 keeps every pair on the int32 kernel (A/B runs).
-static uint32_t band16_base(const gasalx_params &p) { return 0x400u + (uint32_t)(p.gap_open + p.gap_extend + p.mismatch); }
-static bool band16_ok(const gasalx_params &p, uint32_t q8, uint32_t t8) {
-    if (!env_flag("GASALX_BAND16", true)) return false;
-    if (p.match < 0 || p.mismatch < 0 || p.gap_open < 0 || p.gap_extend < 0) return false;
-    if (p.match + p.mismatch > 255 || p.gap_open + p.gap_extend > 4096) return false;
-    if (p.has_n_penalty && p.n_penalty < 0) return false;
-    if (q8 > 65535) return false;   // the first-maximum row is tracked in 16 bits
-    const int64_t hmax = (int64_t)p.match * std::min(q8, t8);
-    return hmax + band16_base(p) <= 0x7BFF && hmax * 8 + 7 + 0x400 <= 0x7BFF;
-}
-
-// Packed LOCAL second-best kernel (local16.hpp): table bytes s + K in [0, 255]
-// (K = max(0, b, N_PENALTY)), stored values B + [0, Hmax] and keys H*8 + 7 +
-// 0x400 inside [0x0400, 0x7BFF].  GASALX_LOCAL16=0 keeps every pair on the int32
-// kernel (A/B runs).
-static int32_t local16_sn(const gasalx_params &p) { return p.has_n_penalty ? -p.n_penalty : 0; }
-static uint32_t local16_k(const gasalx_params &p) { return (uint32_t)std::max({0, p.mismatch, -local16_sn(p)}); }
-static uint32_t local16_base(const gasalx_params &p) { return 0x400u + (uint32_t)(p.gap_open + p.gap_extend) + local16_k(p); }
-static bool local16_ok(const gasalx_params &p, uint32_t q8, uint32_t t8) {
-    if (!env_flag("GASALX_LOCAL16", true)) return false;
-    if (p.match < 0 || p.gap_open < 0 || p.gap_extend < 0 || p.gap_open + p.gap_extend > 4096) return false;
-    const int64_t k = local16_k(p), sn = local16_sn(p);
-    if (p.match + k > 255 || k - p.mismatch > 255 || sn + k > 255) return false;
-    if (q8 > 65535 || t8 / 8 > 65535) return false;   // rows and strips are tracked in 16 bits
-    // largest gain of one cell: match, a negative mismatch or a negative N penalty
-    const int64_t step = std::max<int64_t>({(int64_t)p.match, -(int64_t)p.mismatch, sn});
-    const int64_t hmax = step * std::min(q8, t8);
-    return hmax + local16_base(p) <= 0x7BFF && hmax * 8 + 7 + 0x400 <= 0x7BFF;
-}
-
-Plan make_plan(const gasalx_params &p, const BatchShape &s, bool has_ops) {
-    Plan pl;
-    pl.max_q = s.max_q; pl.max_t = s.max_t;
-    const uint32_t q8 = pad8(s.max_q), t8 = pad8(s.max_t);
-    const bool tb = p.start_pos == 2;
-    int wf_algo = -1;
-    bool keys = false;
-    // LOCAL WITH_START: start.hpp (its reversed query drops pad rows, exact unless N cells score > 0)
-    if (p.algo == 3 /*LOCAL*/ && !p.second_best && !(p.start_pos == 1 && p.has_n_penalty && p.n_penalty < 0)) {
-        wf_algo = WF_LOCAL;
-        keys = true;
-    }
-    else if (p.algo == 1 /*GLOBAL*/) { wf_algo = WF_GLOBAL; }
-    else if (p.algo == 2 /*SEMI*/ && !p.second_best && (p.start_pos != 1 || p.tail == 2)) {   // WITH_START: start.hpp
-        wf_algo = WF_SEMI;
-        keys = (p.tail == 2 || p.tail == 3);
-    }
-    // SEMI TAIL=NONE, score-only: the reference keeps maxHH = MINUS_INF and the initial ends
-    // (semiglobal_kernel_template.h:49-51,63-64,206-218; neither tail block runs)
-    if (p.algo == 2 && p.tail == 0 && p.start_pos == 0 && !p.second_best) {
-        pl.kind = PLAN_CONST;
-        pl.name = "semi_tail_none";
-        return pl;
-    }
-    bool ok = wf_algo >= 0 && int16_safe(p, s.max_q, s.max_t) && t8 < 32000 && p.gap_extend >= 0;
-    if (wf_algo == WF_SEMI && p.start_pos == 1 && t8 > 8192) ok = false;   // stop key: strips < 1024
-    if (ok) {
-        const Shape *pick = nullptr;
-        for (const Shape &sh : kShapes)
-            if ((uint32_t)(sh.G * sh.R) >= q8) { pick = &sh; break; }
-        if (!pick) ok = false;
-        else {
-            pl.G = pick->G; pl.R = pick->R;
-            pl.lds_stride = std::max<uint32_t>(t8, 8);
-            pl.lds_bytes = (size_t)kWavesPerBlock * (64 / pl.G) * pl.lds_stride;
-            if (pl.lds_bytes > 160 * 1024) ok = false;
-        }
-    }
-    if (ok) {
-        pl.kind = PLAN_WAVEFRONT;
-        pl.wf_algo = wf_algo; pl.keys = keys; pl.tb = tb && wf_algo != WF_SEMI;
-        pl.need_pack = has_ops;
-        // GASALX_PACKED16=0: every block on the int32 kernel (A/B runs, the int32 probe of
-        // bench.py --force-int32); read per call
-        pl.packed16 = env_flag("GASALX_PACKED16", true) && packed16_ok(p, wf_algo, s.max_q, s.max_t, &pl.vmin);
-        if (pl.packed16) {
-            const uint32_t x8 = (wf_algo == WF_SEMI) ? t8 : q8, y8 = (wf_algo == WF_SEMI) ? q8 : t8;
-            pl.G16 = 0;
-            // small batches: enough lanes per pair that the launch still holds about two
-            // waves per SIMD (128/G pairs per wave, 1024 SIMDs); traceback keeps G = 8 up
-            // GASALX_GMIN: fixed minimum G (A/B runs, parity sweeps); read per call so a
-            // test process can sweep it
-            const int gforce = env_int("GASALX_GMIN", 0);
-            uint32_t gmin = 8;
-            if (s.n && !pl.tb)
-                while (gmin < 64 && (uint64_t)s.n * gmin < 2048ull * 128) gmin *= 2;
-            if (gforce > 0) gmin = (uint32_t)gforce;
-            // traceback kernels store flags in groups of 4 rows and keep >= 16 rows per
-            // lane (their instances, wf16_pick_r4): the other shapes are never taken,
-            // forced or not
-            for (const Shape &sh : kShapes16)
-                if ((uint32_t)sh.G >= gmin && (uint32_t)(sh.G * sh.R) >= x8 &&
-                    !(pl.tb && (sh.R % 4 || (sh.G > 8 && sh.R < 16)))) {
-                    pl.G16 = sh.G; pl.R16 = sh.R;
-                    break;
-                }
-            // SEMI TAIL=QUERY/BOTH: G = 8 and R = padded target / 8 per class launch (the
-            // last padded column at register R - 1 of lane 7); the plan names the largest
-            pl.semi_tq = pl.packed16 && wf_algo == WF_SEMI && p.tail != 2;
-            if (pl.semi_tq) { pl.G16 = 8; pl.R16 = (int)(x8 / 8); }
-            pl.lds16_stride = packed_lds_stride(y8, pl.G16);
-            pl.lds16_bytes = packed_lds_bytes(y8, pl.G16);
-            if (pl.G16 == 0 || pl.lds16_bytes > 160 * 1024) pl.packed16 = false;
-            if (pl.packed16 && wf_algo != WF_LOCAL)   // the value window over the chosen shape's cells
-                pl.packed16 = packed16_ok(p, wf_algo, s.max_q, s.max_t, &pl.vmin, packed_span(pl.G16, pl.R16, y8));
-            pl.key2 = wf_algo == WF_LOCAL && y8 > 256;
-            // LOCAL score kernels in the e-drift frame (wavefront16.hpp step_local_dr): keys
-            // H*C + (C-1-c) with C = the padded target length, as f16 patterns 0x0400 + key
-            // while (Hmax + 1) * C <= 0x7800, as u16 integers (WF16_LOCAL_U16, one more
-            // instruction per two cells) up to 65536 -- either covers targets past 256 columns
-            // without the second key set; values B + H + e(r + c) over the shape's span stay in
-            // the window and the top lane's first diagonal B - 2e above 0x0400.  GASALX_KF16=0
-            // keeps the round-2 kernel (the tests' cross-check of both key forms)
-            // LOCAL + traceback takes the e-drift kernel with f16 keys (WF16_LOCAL_TBD) when they fit
-            if (wf_algo == WF_LOCAL && env_flag("GASALX_KF16", true)) {
-                const LocalDrift d = local_drift_frame(p, q8, y8, pl.G16, pl.R16);
-                const int64_t hmax = d.hmax;
-                const bool frame = d.window && d.floor;
-                // past both, f16 keys by step segments of M = 2^m columns (WF16_LOCAL_SEG): (Hmax +
-                // 1) * M <= 0x7800 for any target length.  GASALX_KSEG=0: never, 2: before u16 keys
-                const int kseg_mode = env_int("GASALX_KSEG", 1);
-                uint32_t mseg = 0;
-                while ((hmax + 1) * (int64_t)(2u << mseg) <= 0x7800 && mseg < 12) ++mseg;   // M = 2^mseg
-                const bool seg_ok = frame && kseg_mode > 0 && mseg >= 2 && y8 <= 0xFFFF;
-                const int64_t kc = d.kc;
-                if (frame && d.f16) {
-                    pl.kf16 = y8;
-                } else if (pl.tb) {
-                    // (the traceback kernel has f16 keys only)
-                } else if (seg_ok && kseg_mode == 2) {
-                    pl.kf16 = y8;
-                    pl.kseg_shift = mseg;
-                } else if (frame && (hmax + 1) * kc <= 0x10000 && y8 <= 0xFFFF) {
-                    pl.kf16 = y8;
-                    pl.ku16 = true;
-                } else if (seg_ok) {
-                    pl.kf16 = y8;
-                    pl.kseg_shift = mseg;
-                }
-                if (pl.kf16) pl.key2 = false;
-            }
-            // outside both frames the round-2 keys must hold (packed16_ok admitted the drift case)
-            if (wf_algo == WF_LOCAL && !pl.kf16 && !local_key16_ok(p, s.max_q, s.max_t)) pl.packed16 = false;
-            pl.semi_tq = pl.semi_tq && pl.packed16;
-            // GLOBAL + traceback: the score sweep stores band checkpoints, a second pass
-            // recomputes each lane's band window with flags, the walk leaves the band only
-            // through the full-matrix fallback (wavefront16.hpp WF16_GLOBAL_CP / _BAND).
-            // GASALX_TB_BAND=0: the full-matrix flags kernel (A/B); GASALX_TB_BAND_W: the
-            // band's half width w (window of lane lg: columns [max(lg*R - w, 0), + R + 2w))
-            if (pl.packed16 && pl.tb && wf_algo == WF_GLOBAL && pl.R16 % 4 == 0 && env_flag("GASALX_TB_BAND", true)) {
-                // w = 22: config 3's paths stray up to 20 cells from the diagonal, and any pair
-                // that leaves its band costs the chain a full-matrix sweep and a second walk,
-                // latency floors however few pairs they hold; w = 10 -> 22 took config 3 from
-                // 2,953 to 3,647 GCUPS on one engine and 4,240 to 4,450-4,560 on three, though
-                // the band pass grows by 60 % (profiles/r05/n_band_width.md)
-                const int w = std::max(0, env_int("GASALX_TB_BAND_W", 22));
-                pl.tb_band = true;
-                pl.band_w = (uint32_t)w;
-                pl.band_wd = band_window(pl.R16, (uint32_t)w);
-            }
-        }
-        const char *an = wf_algo == WF_LOCAL ? (p.start_pos == 1 ? "local_start" : "local")
-                       : wf_algo == WF_GLOBAL ? "global"
-                       : pl.semi_tq ? "semi_tq" : (p.start_pos == 1 ? "semi_start" : "semi");
-        if (pl.packed16)
-            // (_nodrift: a LOCAL score plan outside the e-drift frame's window, the round-2 kernel)
-            pl.name = std::string("wavefront16_") + an + (pl.tb ? (pl.tb_band ? "_tbband" : "_tb") : "") +
-                      (pl.key2 ? "_k2" : "") +
-                      (wf_algo == WF_LOCAL && !pl.tb && !pl.key2 && !pl.kf16 ? "_nodrift" : "") +
-                      (wf_algo == WF_LOCAL && pl.tb && pl.kf16 ? "_dr" : "") +
-                      (pl.ku16 ? "_u16" : "") + (pl.kseg_shift ? "_seg" + std::to_string(1u << pl.kseg_shift) : "") + "_G" +
-                      std::to_string(pl.G16) + "R" + std::to_string(pl.R16);
-        else
-            pl.name = std::string("wavefront_") + an + (pl.tb ? "_tb" : "") + (keys ? "_keys" : "") + "_G" +
-                      std::to_string(pl.G) + "R" + std::to_string(pl.R);
-    } else if (p.algo == 1 || p.algo == 2 || p.algo == 3 || p.algo == 5 || p.algo == 6) {
-        pl.kind = PLAN_GENERIC;
-        pl.need_pack = true;
-        static const char *names[] = {"?", "global", "semi", "local", "?", "banded", "ksw"};
-        pl.name = std::string("generic_") + names[p.algo];
-        if (p.algo == 5 && band16_ok(p, q8, t8)) {
-            pl.band16 = true;
-            pl.name = "banded16_local";
-        }
-        if (p.algo == 3 && p.second_best && p.start_pos == 0 && local16_ok(p, q8, t8)) {
-            pl.local16 = true;
-            pl.name = "local16_second";
-        }
-    } else {
-        pl.kind = PLAN_NONE;
-        pl.name = "none";
-    }
-    return pl;
-}
-
-// gasalx_semi_cigar_*: the value window of the packed flags kernel (wavefront16.hpp WF16_SEMI_TB) over
-// a shape's span.  GLOBAL's frame (drift e, table offset K = max(2*ceil(max(b, npen)/2), 2e)), but not
-// GLOBAL's bound: with the free target head values no longer fall along the top row.  Every cell has
-// H >= F >= -(OE + e*r) (the insertion run from H(-1, c) = 0), stored + e*(r + c) >= B - OE, and the
-// gap candidates tmp - OE >= -(2*OE + K + e*r) likewise stay within 2*OE + K + 2e of B whatever the
-// span; values rise by at most a per diagonal step and by the frame, e per row + column.
-static bool semi_tb16_ok(const gasalx_params &p, uint32_t mq, uint32_t mt, int32_t *vmin, int64_t span) {
-    if (p.match < 0 || p.mismatch < 0 || p.gap_open < 0 || p.gap_extend < 0) return false;
-    if (p.has_n_penalty && p.n_penalty < 0) return false;
-    const int64_t a = p.match, b = p.mismatch, oe = (int64_t)p.gap_open + p.gap_extend, e = p.gap_extend;
-    const int64_t npen = p.has_n_penalty ? p.n_penalty : 0;
-    const int64_t q8 = pad8(mq), t8 = pad8(mt);
-    const int64_t k = std::max(2 * ((std::max(b, npen) + 1) / 2), 2 * e);   // pk16_params, WF_GLOBAL
-    if (a + k > 255) return false;                                          // table bytes
-    if (!span) span = q8 + t8 + 2 * 64 + 8;
-    const int64_t neg = 0x400 + 2 * e + 16;
-    const int64_t v = 4 * oe + k + 2 * e + 64;   // below every reachable value, span or no span
-    const int64_t top = neg + v + a * std::min(q8, t8) + a + k + oe + 64 + e * span;
-    if (top > 0x7BFF) return false;
-    *vmin = (int32_t)v;
-    return true;
-}
-
-Plan make_semi_cigar_plan(const gasalx_params &p, const BatchShape &s, bool has_ops, int *rc, std::string *why) {
-    Plan pl;
-    pl.max_q = s.max_q; pl.max_t = s.max_t;
-    pl.name = "none";
-    *rc = GASALX_OK;
-    const uint32_t q8 = pad8(s.max_q), t8 = pad8(s.max_t);
-    // (an extension dearer than an opening, or a gap that scores: the walk's "extended" bit could then
-    // name a source the maximum did not take)
-    if (p.gap_open < 0 || p.gap_extend < 0) {
-        *rc = GASALX_EUNSUPPORTED;
-        *why = "semi_cigar: negative gap_open or gap_extend is not supported";
-        return pl;
-    }
-    if (!int16_safe(p, s.max_q, s.max_t) || t8 >= 32000) {
-        *rc = GASALX_ERANGE;
-        *why = "semi_cigar: lengths x scores leave the int16 range the semi-global kernels keep";
-        return pl;
-    }
-    const Shape *pick = nullptr;
-    for (const Shape &sh : kShapes)
-        if ((uint32_t)(sh.G * sh.R) >= q8) { pick = &sh; break; }
-    if (!pick) {
-        *rc = GASALX_ERANGE;
-        *why = "semi_cigar: padded query of " + std::to_string(q8) + " over the largest wavefront shape (" +
-               std::to_string(kShapes[sizeof(kShapes) / sizeof(kShapes[0]) - 1].G *
-                              kShapes[sizeof(kShapes) / sizeof(kShapes[0]) - 1].R) + " rows)";
-        return pl;
-    }
-    pl.G = pick->G; pl.R = pick->R;
-    pl.lds_stride = std::max<uint32_t>(t8, 8);
-    pl.lds_bytes = (size_t)kWavesPerBlock * (64 / pl.G) * pl.lds_stride;
-    if (pl.lds_bytes > 160 * 1024) {
-        *rc = GASALX_ERANGE;
-        *why = "semi_cigar: padded target of " + std::to_string(t8) + " needs more than 160 KB of LDS";
-        return pl;
-    }
-    pl.kind = PLAN_WAVEFRONT;
-    pl.wf_algo = WF_GLOBAL;   // query rows in registers, target on the step axis
-    pl.semi_tb = true;
-    pl.tb = true;
-    pl.need_pack = has_ops;
-    pl.packed16 = env_flag("GASALX_PACKED16", true) && semi_tb16_ok(p, s.max_q, s.max_t, &pl.vmin, 0);
-    if (pl.packed16) {
-        // the traceback shapes (R % 4 == 0, >= 16 rows per lane above G = 8); GASALX_GMIN as make_plan
-        const int gforce = env_int("GASALX_GMIN", 0);
-        const uint32_t gmin = gforce > 0 ? (uint32_t)gforce : 8u;
-        for (const Shape &sh : kShapes16)
-            if ((uint32_t)sh.G >= gmin && (uint32_t)(sh.G * sh.R) >= q8 && !(sh.R % 4 || (sh.G > 8 && sh.R < 16))) {
-                pl.G16 = sh.G; pl.R16 = sh.R;
-                break;
-            }
-        pl.lds16_stride = packed_lds_stride(t8, pl.G16);
-        pl.lds16_bytes = packed_lds_bytes(t8, pl.G16);
-        if (pl.G16 == 0 || pl.lds16_bytes > 160 * 1024) pl.packed16 = false;
-        if (pl.packed16) pl.packed16 = semi_tb16_ok(p, s.max_q, s.max_t, &pl.vmin, packed_span(pl.G16, pl.R16, t8));
-    }
-    pl.name = pl.packed16 ? "wavefront16_semi_tb_G" + std::to_string(pl.G16) + "R" + std::to_string(pl.R16)
-                          : "wavefront_semi_tb_G" + std::to_string(pl.G) + "R" + std::to_string(pl.R);
-    return pl;
 }
 
 #define HIPCHK(x)                                                                        \
@@ -601,9 +178,8 @@ static TailShape tail_shape(Workspace &ws, const Plan &pl, const gasalx_params &
         t.vmin = pl.vmin;
     } else {
         // the window offset for the larger span serves both shapes: their values then sit higher
-        // in the same window, whose top packed16_ok checked for that span
-        if (!packed16_ok(p, WF_GLOBAL, pl.max_q, pl.max_t, &t.vmin,
-                         std::max(packed_span(G2, R2, y8), packed_span(pl.G16, pl.R16, y8))))
+        // in the same window, whose top global_window checked for that span
+        if (!global_window(p, q8, y8, std::max(packed_span(G2, R2, y8), packed_span(pl.G16, pl.R16, y8)), &t.vmin))
             return t;
         t.vmin = std::max(t.vmin, pl.vmin);
     }
@@ -1120,12 +696,8 @@ static int run_ksw(Call &c, const GenArgs &A) {
     uint8_t *todo = ws.misc.as<uint8_t>();
     // two pairs per lane in 16-bit halves first (ksw16.hpp): the pairs it takes
     // get todo = 0xFF, the rest run the levels below (GASALX_KSW16=0: levels only)
-    const int32_t nsc = p.has_n_penalty ? -p.n_penalty : 0;
-    const int32_t kofs = std::max({0, p.mismatch, -nsc, -p.match});
-    const bool k16 = env_flag("GASALX_KSW16", true) && p.gap_open >= 0 && p.gap_extend >= 0 &&
-                     p.gap_open + p.gap_extend <= 0x300 && p.match + kofs <= 255 &&
-                     -p.mismatch + kofs <= 255 && nsc + kofs <= 255 && max_q <= 254;
-    if (k16) {
+    int32_t kofs;
+    if (ksw16_ok(p, max_q, &kofs)) {
         Ksw16Args K;
         std::memset(&K, 0, sizeof(K));
         K.qw = A.qw; K.tw = A.tw;

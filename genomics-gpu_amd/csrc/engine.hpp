@@ -107,6 +107,8 @@ struct BatchShape {
                           // then launches its one class without reading the class histogram back)
 };
 
+// The planner (plan.cpp, host only; what the launch code shares with it: plan.hpp).  has_ops: the
+// batch carries reverse / complement ops.
 Plan make_plan(const gasalx_params &p, const BatchShape &shape, bool has_ops);
 
 // The direction-flag launch of gasalx_semi_cigar_* (SEMI-GLOBAL, HEAD = TAIL = TARGET, with CIGARs):

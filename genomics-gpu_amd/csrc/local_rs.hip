@@ -1,7 +1,7 @@
 // local_rs.hip — instances of the packed LOCAL e-drift kernel (wavefront16.hpp) with u16 keys
 // (WF16_LOCAL_U16) and the WITH_START reverse pass's early stop (WF16_LOCAL_RS,
 // WF16_LOCAL_U16_RS) and with keys by step segments (WF16_LOCAL_SEG), over the packed shapes
-// (wavefront16.hpp GX_SHAPES_PK).  Compiled apart from dispatch.hip so the two build in parallel.
+// (shapes.hpp GX_SHAPES_PK).  Compiled apart from dispatch.hip so the two build in parallel.
 #include "wavefront16.hpp"
 
 namespace gx {

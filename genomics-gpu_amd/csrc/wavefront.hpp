@@ -21,9 +21,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-namespace gx {
+#include "shapes.hpp"   // WfAlgo, kWavesPerBlock
 
-enum WfAlgo { WF_LOCAL = 0, WF_GLOBAL = 1, WF_SEMI = 2 };
+namespace gx {
 
 struct WfArgs {
     const uint8_t *q;          // unpacked bytes, or packed words (packed != 0)
@@ -95,7 +95,6 @@ __device__ __forceinline__ uint32_t skip_flag(const WfArgs &A, uint32_t idx) {
     return idx < A.skip_p1 ? idx / A.skip_ppb : A.skip_b1 + (idx - A.skip_p1) / A.skip_ppb2;
 }
 
-constexpr int kWavesPerBlock = 4;
 constexpr int kBlock = 64 * kWavesPerBlock;
 constexpr uint8_t kInvalidCode = 0xFF;
 

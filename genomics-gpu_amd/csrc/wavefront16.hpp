@@ -104,7 +104,7 @@ __device__ __forceinline__ bool groups_all(uint64_t b) {
     return (b & low) == low;
 }
 
-// Value-range constants of one launch (dispatch.hip packed16_ok checks that the
+// Value-range constants of one launch (the planner's value windows, plan.cpp, check that the
 // stored values stay inside [0x0400, 0x7BFF] for these).
 struct Pk16 {
     int32_t k;      // table offset
@@ -710,20 +710,7 @@ __global__ __launch_bounds__(kBlock, wf16_waves(ALGO_, R1)) void wf16_mix_kernel
     }
 }
 
-// ---------------------------------------------------------------------------
-// (G lanes per pair, R rows per lane) shapes: register-axis positions covered = G*R.  Each list
-// is written once, here: the planner's arrays (dispatch.hip kShapes / kShapes16) and every table
-// of instances (pick_instance) come from them.
-//  * GX_SHAPES_R4: the int32 kernels (wavefront.hpp) and the packed kernels that store in groups
-//    of 4 rows (traceback flags, band windows), R % 4 == 0;
-//  * GX_SHAPES_PK: the packed score kernels (register axis = query for LOCAL/GLOBAL, target for
-//    SEMI): R = 19 fits 150 bp (152 padded) and R = 23 fits 182 bp (184 padded) exactly; the
-//    G = 16/32/64 shapes with few rows per lane serve small batches (make_plan).
-// ---------------------------------------------------------------------------
-#define GX_SHAPES_R4(X) X(8, 8) X(8, 12) X(8, 16) X(8, 20) X(16, 16) X(16, 20) X(32, 20) X(64, 20)
-#define GX_SHAPES_PK(X)                                                                               \
-    X(8, 8) X(8, 12) X(8, 16) X(8, 19) X(8, 20) X(8, 23) X(16, 10) X(16, 12) X(16, 16) X(16, 20)      \
-    X(32, 5) X(32, 6) X(32, 9) X(32, 20) X(64, 3) X(64, 5) X(64, 20)
+// the shape lists GX_SHAPES_R4 / GX_SHAPES_PK: shapes.hpp
 enum ShapeSet { SHAPES_R4, SHAPES_PK };
 
 // the instance K::fn<G, R>() of kernel family K for a shape of list L, nullptr for any other shape

@@ -374,8 +374,8 @@ def ksw_rule_batches(seed=0x155):
 
 
 def ksw_routing(qs, ts, seed, scores=(1, 4, 6, 1), env=None, npen=None):
-    """Which KSW kernel form the dispatcher's documented rule (dispatch.hip, KSW branch;
-    ksw16.hpp header; gen_ksw_kernel) sends every pair of a batch to, from the inputs alone.
+    """Which KSW kernel form the dispatcher's documented rule (plan.cpp ksw16_ok, dispatch.hip
+    run_ksw; ksw16.hpp header; gen_ksw_kernel) sends every pair of a batch to, from the inputs alone.
     Returns dict(taken: pairs ksw16 takes, level: the entry level 0/1/2 of the others' (and,
     for the taken ones, the level they would run), inst: the ksw16 instance 64 / 96 / 160 /
     0 = global entries / None = ksw16 off for the batch, tpb: threads per block of the LDS

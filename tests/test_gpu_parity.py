@@ -1009,7 +1009,7 @@ def test_host_pipeline_tb_slot_reuse(engine, algo):
 
 
 # ------------------------------------------------- every packed shape ----
-# (G, R) of kShapes16 (dispatch.hip).  GASALX_GMIN forces the minimum G; the
+# (G, R) of kShapes16 (plan.cpp).  GASALX_GMIN forces the minimum G; the
 # padded register-axis length G*R then selects exactly that shape.
 SHAPES16 = [(8, 8), (8, 12), (8, 16), (8, 19), (8, 20), (8, 23), (16, 10), (16, 12), (16, 16), (16, 20),
             (32, 5), (32, 6), (32, 9), (32, 20), (64, 3), (64, 5), (64, 20)]

@@ -9,7 +9,7 @@
 
 Two builds launch the same sequence when their lists are equal line for line
 (profiles/dispatch_refactor/README.md, profiles/capi_refactor/README.md,
-profiles/nv_launcher_refactor/README.md).
+profiles/nv_launcher_refactor/README.md, profiles/planner_refactor/README.md).
 """
 import csv
 import glob
@@ -106,6 +106,14 @@ def run():
     P199, T199 = G.PackedSet.pack(pats[:199]), G.PackedSet.pack(txts[:199], bits=2, big_endian=False)
     eng.nv_score_host(al, P199, T199)                                             # an odd n: the packed grids round up
     eng.nv_banded_score_host(al, 16, P199, T199)
+
+    # planner branches the calls above miss (profiles/planner_refactor/README.md)
+    device_call(G.Batch.synth(3, 60_000, 0x7A32), ("aln_score",), algo=G.GLOBAL)  # GLOBAL score: its tail shape
+    eng.semi_cigar_host(rand_batch(0x57, 2_000, 100, 150, 150, 182),
+                        G.make_params(algo=G.SEMI_GLOBAL, head=G.TARGET, tail=G.TARGET))
+    os.environ["GASALX_GMIN"] = "32"                                              # a forced minimum G
+    device_call(G.Batch.synth(2, 2_000, 0x7A16), ends, algo=G.LOCAL)
+    del os.environ["GASALX_GMIN"]
     eng.close()
 
 
