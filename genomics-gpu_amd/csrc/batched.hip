@@ -17,6 +17,7 @@
 #include "nvtrace.hpp"
 #include "nvbio16.hpp"
 #include "nvbanded.hpp"
+#include "nvmyers.hpp"
 
 namespace gx {
 
@@ -103,12 +104,16 @@ template <class Args> struct has_tbits<Args, std::void_t<decltype(Args::tbits)>>
 // the string sets, the scheme and the pair count of any kernel argument struct (the packed
 // kernels' have no tbits: their texts are 2-bit)
 template <class Args>
-void nv_fill(Args &A, const gasalx_nv_strings &pat, const gasalx_nv_strings &txt, const NvScheme &s, uint32_t n) {
+void nv_fill_strings(Args &A, const gasalx_nv_strings &pat, const gasalx_nv_strings &txt, uint32_t n) {
     A.pw = pat.words; A.poff = pat.offsets; A.pbits = pat.bits; A.pbig = pat.big_endian;
     A.tw = txt.words; A.toff = txt.offsets; A.tbig = txt.big_endian; A.tlen0 = txt.offsets ? 0 : txt.length;
     if constexpr (has_tbits<Args>::value) A.tbits = txt.bits;
-    A.match = s.match; A.mismatch = s.mismatch; A.go = s.go; A.ge = s.ge; A.del = s.del; A.ins = s.ins;
     A.n = n;
+}
+template <class Args>
+void nv_fill(Args &A, const gasalx_nv_strings &pat, const gasalx_nv_strings &txt, const NvScheme &s, uint32_t n) {
+    nv_fill_strings(A, pat, txt, n);
+    A.match = s.match; A.mismatch = s.mismatch; A.go = s.go; A.ge = s.ge; A.del = s.del; A.ins = s.ins;
 }
 
 int nv_fail(int rc, const std::string &msg) { set_error(msg); return rc; }
@@ -344,6 +349,42 @@ int nv_banded_score_device(const gasalx_nv_aligner &al, uint32_t band, uint32_t 
     using Fn = void (*)(NvBandArgs);
     const Fn fn = nv_static(al.aligner, al.type, ex, [band](auto a, auto t, auto e) -> Fn {
         return GX_BAND_PICK(nv_banded_kernel, a, t, e); });
+    return launch_checked(fn, (n + 255) / 256, st, A);
+}
+
+// ---- EditDistanceAligner<TYPE, MyersTag<ALPHABET>> under BatchedBandedAlignmentScore<band>
+//      (nvmyers.hpp): thread per pair, one instance per type and alphabet, the band length a
+//      launch argument.  The checks of nv_banded_score_device in its order, then the alphabet;
+//      LOCAL, which the reference's function does not have, is refused last. ----
+static int nv_myers_check(int32_t type, uint32_t alphabet, uint32_t band, const gasalx_nv_strings &pat,
+                   const gasalx_nv_strings &txt) {
+    const gasalx_nv_aligner al = {NV_ED, type, 0, -1, 0, 0, -1, -1};
+    if (int rc = nv_check(al, "bad aligner", "bad aligner", &band, pat, txt)) return rc;
+    if (alphabet != 2 && alphabet != 4 && alphabet != 5) return nv_fail(GASALX_EINVAL, "alphabet size must be 2, 4 or 5");
+    if (type == NV_LOCAL) return nv_fail(GASALX_EUNSUPPORTED, "banded Myers has no LOCAL form");
+    return GASALX_OK;
+}
+
+int nv_myers_plan_name(int32_t type, uint32_t alphabet, uint32_t band, std::string &name) {
+    const gasalx_nv_strings any = {nullptr, nullptr, 0, 2, 0};
+    if (int rc = nv_myers_check(type, alphabet, band, any, any)) return rc;
+    name = std::string("nvbio_myers_") + (type == NV_GLOBAL ? "global" : "semi") + "_a" + std::to_string(alphabet);
+    return GASALX_OK;
+}
+
+int nv_banded_myers_device(int32_t type, uint32_t alphabet, uint32_t band, uint32_t n, const gasalx_nv_strings &pat,
+                           const gasalx_nv_strings &txt, int32_t *scores, uint32_t *sinks, hipStream_t st) {
+    if (int rc = nv_myers_check(type, alphabet, band, pat, txt)) return rc;
+    if (n == 0) return GASALX_OK;
+    if (int rc = nv_check_ptrs(pat, txt, scores || sinks)) return rc;
+    NvMyersArgs A;
+    nv_fill_strings(A, pat, txt, n);
+    A.score = scores; A.sinks = sinks; A.band = band;
+    using Fn = void (*)(NvMyersArgs);
+    auto by_alphabet = [alphabet](auto t) -> Fn {
+        return alphabet == 2 ? &nv_myers_kernel<t, 2> : alphabet == 4 ? &nv_myers_kernel<t, 4> : &nv_myers_kernel<t, 5>;
+    };
+    const Fn fn = type == NV_GLOBAL ? by_alphabet(ic<NV_GLOBAL>{}) : by_alphabet(ic<NV_SEMI>{});
     return launch_checked(fn, (n + 255) / 256, st, A);
 }
 

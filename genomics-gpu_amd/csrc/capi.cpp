@@ -1112,6 +1112,49 @@ int gasalx_nv_banded_score_host(gasalx_engine *eng, const gasalx_nv_aligner *al,
     return host_finish(st, rc, {{scores, ds.p, (size_t)n * 4}});
 }
 
+int gasalx_nv_banded_myers_device(gasalx_engine *eng, int32_t type, uint32_t alphabet, uint32_t band, uint32_t n,
+                                  const gasalx_nv_strings *pat, const gasalx_nv_strings *txt, int32_t *scores,
+                                  uint32_t *sinks, uint32_t max_p, void *stream) {
+    (void)max_p;   // the kernel has no value window to size: the bound is not needed, nothing is read back
+    if (!eng || !pat || !txt) { gx::set_error("null argument"); return GASALX_EINVAL; }
+    hipStream_t st;
+    int rc = enter(eng, stream, &st);
+    if (rc) return rc;
+    return gx::nv_banded_myers_device(type, alphabet, band, n, *pat, *txt, scores, sinks, st);
+}
+
+int gasalx_nv_describe_myers_plan(int32_t type, uint32_t alphabet, uint32_t band, char *buf, uint32_t buf_len) {
+    if (!buf || buf_len == 0) { gx::set_error("null argument"); return GASALX_EINVAL; }
+    std::string name;
+    if (int rc = gx::nv_myers_plan_name(type, alphabet, band, name)) return rc;
+    std::snprintf(buf, buf_len, "%s", name.c_str());
+    return GASALX_OK;
+}
+
+int gasalx_nv_banded_myers_host(gasalx_engine *eng, int32_t type, uint32_t alphabet, uint32_t band, uint32_t n,
+                                const gasalx_nv_strings *pat, uint64_t pat_words, const gasalx_nv_strings *txt,
+                                uint64_t txt_words, int32_t *scores, uint32_t *sinks) {
+    if (!eng || !pat || !txt || !pat->words || !pat->offsets || !txt->words || (!scores && !sinks)) {
+        gx::set_error("null argument");
+        return GASALX_EINVAL;
+    }
+    // refused before anything is staged, with the device path's own codes and texts
+    std::string name;
+    if (int rc = gx::nv_myers_plan_name(type, alphabet, band, name)) return rc;
+    if (n == 0) return GASALX_OK;
+    hipStream_t st;
+    int rc = enter(eng, nullptr, &st);
+    if (rc) return rc;
+    gasalx_nv_strings dp, dt;
+    if ((rc = nv_stage_strings(eng, n, pat, pat_words, txt, txt_words, st, dp, dt))) return rc;
+    int32_t *ds = nullptr;
+    uint32_t *dk = nullptr;
+    if (scores) { CK(eng->buf[B_NV_S].reserve((size_t)n * 4)); ds = eng->buf[B_NV_S].as<int32_t>(); }
+    if (sinks) { CK(eng->buf[B_NV_SNK].reserve((size_t)n * 8)); dk = eng->buf[B_NV_SNK].as<uint32_t>(); }
+    rc = gx::nv_banded_myers_device(type, alphabet, band, n, dp, dt, ds, dk, st);
+    return host_finish(st, rc, {{scores, ds, (size_t)n * 4}, {sinks, dk, (size_t)n * 8}});
+}
+
 uint64_t gasalx_nv_traceback_workspace(uint32_t max_p, uint32_t max_t, uint32_t n) {
     const uint64_t per = (uint64_t)((max_p + 7) / 8) * 8 * max_t + (uint64_t)max_t * 8;
     return per * nv_tb_chunk(n, per) + 128;

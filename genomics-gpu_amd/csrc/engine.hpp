@@ -202,6 +202,12 @@ std::string nv_sinks_plan_name(const gasalx_nv_aligner &al, uint32_t max_p, uint
 // max_p: the longest pattern (0: unknown; the packed kernel needs it for its value window)
 int nv_banded_score_device(const gasalx_nv_aligner &al, uint32_t band, uint32_t n, const gasalx_nv_strings &pat,
                            const gasalx_nv_strings &txt, int32_t *scores, hipStream_t st, uint32_t max_p);
+// EditDistanceAligner<TYPE, MyersTag<alphabet>> under the same banded scorer (nvmyers.hpp): BestSink
+// score and position per pair (sinks as nv_score_sinks_device); scores or sinks may be NULL
+int nv_banded_myers_device(int32_t type, uint32_t alphabet, uint32_t band, uint32_t n, const gasalx_nv_strings &pat,
+                           const gasalx_nv_strings &txt, int32_t *scores, uint32_t *sinks, hipStream_t st);
+// its kernel's name ("nvbio_myers_semi_a5"), or the code the call would return
+int nv_myers_plan_name(int32_t type, uint32_t alphabet, uint32_t band, std::string &name);
 int nv_traceback_device(const gasalx_nv_aligner &al, uint32_t n, const gasalx_nv_strings &pat,
                         const gasalx_nv_strings &txt, uint32_t max_p, uint32_t max_t, uint8_t *dir, int32_t *row,
                         int32_t *score, uint32_t *src, uint32_t *snk, uint8_t *ops, uint32_t ops_stride,

@@ -363,6 +363,32 @@ int gasalx_nv_banded_score_host(gasalx_engine *eng, const gasalx_nv_aligner *ali
                                 uint32_t n_pairs, const gasalx_nv_strings *patterns, uint64_t pattern_words,
                                 const gasalx_nv_strings *texts, uint64_t text_words, int32_t *scores);
 
+/* The same banded scorer with nvbio's Myers bit-vector aligner, EditDistanceAligner<TYPE,
+ * MyersTag<alphabet_size>> (qmap's and fmmap's configuration; NvB/nvbio/alignment/myers/
+ * myers_banded_inl.h:226-288, banded_myers<band_len, 0, TYPE, alphabet_size>).  Not the banded
+ * DP's numbers: the function has its own report rule (SEMI_GLOBAL reports the text columns
+ * min(N - 1, M) + 1 .. N while the pattern's last row is inside the 32-bit column, never column
+ * M of a longer text; GLOBAL reports (N, M) once), so scores and sinks are those of nvbio's Myers
+ * path.  type: GASALX_NV_GLOBAL or _SEMI_GLOBAL (_LOCAL: GASALX_EUNSUPPORTED, the reference has
+ * none); alphabet_size 2, 4 or 5 (symbols are masked with 1 / 3; under 5, pattern symbols above 4
+ * match nothing and text symbols above 4 read as 4; the mask of symbol 4 starts at 0); band_len
+ * 2..32 (else GASALX_EINVAL).  scores: the BestSink score (minus the distance) per pair; sinks:
+ * two uint32 per pair in gasalx_nv_score_sinks_*'s layout (x = text column, y = pattern row,
+ * one-based, the last maximum); either may be NULL, not both.  A text shorter than its pattern
+ * reports nothing: INT32_MIN and (0xFFFFFFFF, 0xFFFFFFFF).  max_pattern_len is accepted for
+ * symmetry with gasalx_nv_banded_score_device and not needed. */
+int gasalx_nv_banded_myers_device(gasalx_engine *eng, int32_t type, uint32_t alphabet_size, uint32_t band_len,
+                                  uint32_t n_pairs, const gasalx_nv_strings *dev_patterns,
+                                  const gasalx_nv_strings *dev_texts, int32_t *dev_scores, uint32_t *dev_sinks,
+                                  uint32_t max_pattern_len, void *stream);
+int gasalx_nv_banded_myers_host(gasalx_engine *eng, int32_t type, uint32_t alphabet_size, uint32_t band_len,
+                                uint32_t n_pairs, const gasalx_nv_strings *patterns, uint64_t pattern_words,
+                                const gasalx_nv_strings *texts, uint64_t text_words, int32_t *scores,
+                                uint32_t *sinks);
+/* The kernel such a call runs (e.g. "nvbio_myers_semi_a5"), or the code the call would return. */
+int gasalx_nv_describe_myers_plan(int32_t type, uint32_t alphabet_size, uint32_t band_len, char *buf,
+                                  uint32_t buf_len);
+
 /* nvbio's BatchedAlignmentTraceback<CHECKPOINTS> (NvB/nvbio/alignment/batched.h:436,
  * batched_inl.h:612-664, alignment_inl.h:365-465): the full-DP traceback of the Gotoh,
  * Smith-Waterman and edit-distance aligners (ED runs as SW with 0 / -1 / -1 / -1, as

@@ -29,6 +29,10 @@
  * BatchedBandedAlignmentTraceback<BAND_LEN, CHECKPOINTS, stream_type> for the edit-distance,
  * Smith-Waterman and Gotoh aligners over a TracebackStream (nvtrace.hpp: one pair per thread,
  * as the reference's DeviceThreadScheduler runs it); the warp variants are not provided.
+ * EditDistanceAligner<TYPE, MyersTag<N>> (nvbio's Myers bit-vector edit distance,
+ * myers/myers_banded_inl.h) runs under BatchedBandedAlignmentScore and the free function
+ * batch_banded_alignment_score<BAND_LEN>, qmap's and fmmap's call, with scores and BestSink
+ * positions (nvmyers.hpp); the full-DP scorer and the tracebacks refuse it at compile time.
  *
  * Header-only C++ over the flat C-ABI (gasalx.h); link with -lgasal.
  */
@@ -57,6 +61,12 @@ enum AlignmentType { GLOBAL, LOCAL, SEMI_GLOBAL };   // alignment_base.h:54
 
 struct PatternBlockingTag {};
 struct TextBlockingTag {};
+// the Myers bit-vector algorithm over an alphabet of N symbols (alignment_base.h:64-65): edit
+// distance only, banded scoring only (myers/myers_banded_inl.h is the one function this tree has)
+template <uint32 N>
+struct MyersTag { static const uint32 ALPHABET_SIZE = N; };
+template <typename T> struct is_myers_tag : std::false_type {};
+template <uint32 N> struct is_myers_tag<MyersTag<N> > : std::true_type {};
 
 // batch schedulers (batched.h:44-87): tags only; all run the same device kernel
 struct HostThreadScheduler {};
@@ -176,7 +186,8 @@ struct AlignmentStream {
     // On ties BestSink keeps the last maximum in the aligner's report order, and the kernels
     // follow the TextBlockingTag order (text stripes of 8 columns).
     void set_sinks(uint32 *sinks) {
-        static_assert(std::is_same<typename aligner_type::algorithm_tag, TextBlockingTag>::value,
+        static_assert(std::is_same<typename aligner_type::algorithm_tag, TextBlockingTag>::value ||
+                          is_myers_tag<typename aligner_type::algorithm_tag>::value,
                       "sinks are provided for TextBlockingTag aligners only: PatternBlockingTag reports cells in "
                       "another order (pattern stripes), so its tied sinks differ; make the aligner with "
                       "make_*_aligner<TYPE, TextBlockingTag>(...) or score without sinks");
@@ -222,6 +233,9 @@ struct BatchedAlignmentScore {
     // enact the batch on the engine's stream (nvbio's enact is asynchronous too; the
     // benchmark synchronises the device afterwards).  Errors exit, as nvbio's do.
     void enact(stream_type stream, uint64 temp_size = 0u, uint8 *temp = NULL, void *hip_stream = NULL) {
+        static_assert(!is_myers_tag<typename aligner_type::algorithm_tag>::value,
+                      "MyersTag aligners run under BatchedBandedAlignmentScore only: nvbio has the banded Myers "
+                      "scorer (myers/myers_banded_inl.h) and no full-DP or traceback form of it");
         (void)temp_size; (void)temp;
         const gasalx_nv_aligner a = stream.aligner().c_aligner();
         gasalx_nv_strings p = {stream.m_patterns, stream.m_offsets, 0, stream.m_pattern_bits,
@@ -273,6 +287,18 @@ struct BatchedBandedAlignmentScore {
                                stream.m_pattern_big_endian};
         gasalx_nv_strings t = {stream.m_text, stream.m_text_offsets, stream.m_text_len, stream.m_text_bits,
                                stream.m_text_big_endian};
+        if constexpr (is_myers_tag<typename aligner_type::algorithm_tag>::value) {
+            // EditDistanceAligner<TYPE, MyersTag<N>>: nvbio's banded_myers, with the BestSink
+            // positions when the stream carries them (scores or sinks, not neither)
+            const int rc = gasalx_nv_banded_myers_device(engine(), a.type, aligner_type::algorithm_tag::ALPHABET_SIZE,
+                                                         BAND_LEN, stream.size(), &p, &t, stream.m_scores32,
+                                                         stream.m_sinks, stream.max_pattern_length(), hip_stream);
+            if (rc != GASALX_OK) {
+                fprintf(stderr, "BatchedBandedAlignmentScore::enact: %s\n", gasalx_last_error());
+                exit(EXIT_FAILURE);
+            }
+            return;
+        }
         if (stream.m_scores32 == NULL) {
             fprintf(stderr, "BatchedBandedAlignmentScore::enact: banded scores are int32, set m_scores32\n");
             exit(EXIT_FAILURE);
@@ -285,6 +311,49 @@ struct BatchedBandedAlignmentScore {
         }
     }
 };
+
+// A packed string set and the sinks of a batch as the free function below takes them: what qmap
+// passes as read_infix_set / genome_infix_set and sinks.begin() (examples/qmap/qmap.cu:285-293),
+// with the packing made explicit.  All pointers are device pointers; offsets: count + 1 symbol
+// offsets into words.  BestSinks is a vector of BestSink<int32> as two arrays: scores[k], and
+// sinks[2k] = x (text), sinks[2k + 1] = y (pattern); either may be NULL.
+struct PackedStringSet {
+    PackedStringSet(const uint32 count, const uint32 *words, const uint32 *offsets, const uint32 bits,
+                    const uint32 big_endian)
+        : m_count(count), m_words(words), m_offsets(offsets), m_bits(bits), m_big_endian(big_endian) {}
+    uint32 size() const { return m_count; }
+    uint32 m_count;
+    const uint32 *m_words, *m_offsets;
+    uint32 m_bits, m_big_endian;
+};
+struct BestSinks {
+    int32 *scores;
+    uint32 *sinks;
+};
+
+// batch_banded_alignment_score<BAND_LEN>(aligner, patterns, texts, sinks, scheduler, max_pattern_length,
+// max_text_length) (batched.h:216-231), the form qmap and fmmap call: patterns[k] against texts[k]
+// on the engine's stream (asynchronous, as nvbio's).  A MyersTag aligner takes scores and sinks;
+// the DP aligners' banded scorer has scores only, and a sinks array given to it is an error.
+template <uint32 BAND_LEN, typename aligner_type, typename scheduler_type>
+void batch_banded_alignment_score(const aligner_type aligner, const PackedStringSet patterns,
+                                  const PackedStringSet texts, BestSinks sinks, const scheduler_type,
+                                  const uint32 max_pattern_length, const uint32 max_text_length) {
+    (void)max_text_length;
+    AlignmentStream<aligner_type> stream(aligner, patterns.size(), patterns.m_offsets, patterns.m_words,
+                                         max_pattern_length, 0, texts.m_words, 0, NULL);
+    stream.m_text_offsets = texts.m_offsets;
+    stream.m_pattern_bits = patterns.m_bits; stream.m_pattern_big_endian = patterns.m_big_endian;
+    stream.m_text_bits = texts.m_bits; stream.m_text_big_endian = texts.m_big_endian;
+    stream.m_scores32 = sinks.scores;
+    if (sinks.sinks && !is_myers_tag<typename aligner_type::algorithm_tag>::value) {
+        fprintf(stderr, "batch_banded_alignment_score: the banded DP scorer reports scores only\n");
+        exit(EXIT_FAILURE);
+    }
+    stream.m_sinks = sinks.sinks;
+    BatchedBandedAlignmentScore<BAND_LEN, AlignmentStream<aligner_type>, scheduler_type> batch;
+    batch.enact(stream);
+}
 
 // The outputs of a traceback batch (batched_inl.h:612-664's stream.output(): the Alignment
 // and the backtracer of each job), as device arrays: per pair the BestSink score, the
@@ -340,6 +409,9 @@ struct BatchedAlignmentTraceback {
     }
 
     void enact(stream_type stream, uint64 temp_size = 0u, uint8 *temp = NULL, void *hip_stream = NULL) {
+        static_assert(!is_myers_tag<typename aligner_type::algorithm_tag>::value,
+                      "MyersTag aligners run under BatchedBandedAlignmentScore only: nvbio has the banded Myers "
+                      "scorer (myers/myers_banded_inl.h) and no full-DP or traceback form of it");
         (void)temp_size; (void)temp;
         const gasalx_nv_aligner a = stream.aligner().c_aligner();
         gasalx_nv_strings p = {stream.m_patterns, stream.m_offsets, 0, stream.m_pattern_bits,
@@ -375,6 +447,9 @@ struct BatchedBandedAlignmentTraceback {
     }
 
     void enact(stream_type stream, uint64 temp_size = 0u, uint8 *temp = NULL, void *hip_stream = NULL) {
+        static_assert(!is_myers_tag<typename aligner_type::algorithm_tag>::value,
+                      "MyersTag aligners run under BatchedBandedAlignmentScore only: nvbio has the banded Myers "
+                      "scorer (myers/myers_banded_inl.h) and no full-DP or traceback form of it");
         (void)temp_size; (void)temp;
         const gasalx_nv_aligner a = stream.aligner().c_aligner();
         gasalx_nv_strings p = {stream.m_patterns, stream.m_offsets, 0, stream.m_pattern_bits,
