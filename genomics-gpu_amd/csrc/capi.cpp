@@ -384,32 +384,34 @@ int align_host_pipelined(gasalx_engine *eng, const gasalx_params *params, const 
     return GASALX_OK;
 }
 
-// gasalx_semi_cigar_*: the argument checks, one text each, in this order.  b / out NULL (the describe
+// gasalx_semi_cigar_* and gasalx_semi_cigar_head_* (heads: any HEAD, its own message prefix): the argument
+// checks, one text each, in this order.  b / out NULL (the describe
 // call): the checks on the parameters only.
 bool ranges_overlap(const void *a, uint64_t an, const void *b, uint64_t bn) {
     const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
     return x < y + bn && y < x + an;
 }
-int semi_cigar_checks(const gasalx_params *p, const gasalx_batch *b, const gasalx_results *out) {
+int semi_cigar_checks(const gasalx_params *p, const gasalx_batch *b, const gasalx_results *out, bool heads) {
+    const std::string call = heads ? "semi_cigar_head: " : "semi_cigar: ";
     static const char *const src[] = {"NONE", "QUERY", "TARGET", "BOTH"};
-    if (p->algo != 2) { gx::set_error("semi_cigar: algo must be SEMI_GLOBAL"); return GASALX_EINVAL; }
-    if (p->second_best) { gx::set_error("semi_cigar: second_best is not supported"); return GASALX_EUNSUPPORTED; }
-    if (p->head != 2 || p->tail != 2) {
-        gx::set_error(std::string("semi_cigar: HEAD=") + src[p->head] + " TAIL=" + src[p->tail] +
-                      " is not supported (HEAD=TARGET TAIL=TARGET only)");
+    if (p->algo != 2) { gx::set_error(call + "algo must be SEMI_GLOBAL"); return GASALX_EINVAL; }
+    if (p->second_best) { gx::set_error(call + "second_best is not supported"); return GASALX_EUNSUPPORTED; }
+    if ((!heads && p->head != 2) || p->tail != 2) {
+        gx::set_error(call + "HEAD=" + src[p->head] + " TAIL=" + src[p->tail] + " is not supported (" +
+                      (heads ? "TAIL=TARGET only)" : "HEAD=TARGET TAIL=TARGET only)"));
         return GASALX_EUNSUPPORTED;
     }
     if (!b || !out) return GASALX_OK;
     if (!out->aln_score || !out->cigar || !out->n_cigar_ops) {
-        gx::set_error("semi_cigar: aln_score, cigar and n_cigar_ops outputs are required");
+        gx::set_error(call + "aln_score, cigar and n_cigar_ops outputs are required");
         return GASALX_EINVAL;
     }
     if (out->aln_score2 || out->q_end2 || out->t_end2) {
-        gx::set_error("semi_cigar: the second-best outputs must be NULL");
+        gx::set_error(call + "the second-best outputs must be NULL");
         return GASALX_EINVAL;
     }
     if (b->q_batch && ranges_overlap(out->cigar, b->q_bytes, b->q_batch, b->q_bytes)) {
-        gx::set_error("semi_cigar: cigar overlaps q_batch (it must be a buffer of its own)");
+        gx::set_error(call + "cigar overlaps q_batch (it must be a buffer of its own)");
         return GASALX_EINVAL;
     }
     return GASALX_OK;
@@ -757,25 +759,26 @@ int gasalx_align_host(gasalx_engine *eng, const gasalx_params *params, const gas
     return host_finish(st, GASALX_OK, {});
 }
 
-int gasalx_describe_semi_cigar_plan(const gasalx_params *params, uint32_t max_q_len, uint32_t max_t_len, char *buf,
-                                    uint32_t buf_len) {
+// the three semi-CIGAR calls, HEAD = TARGET (gasalx_semi_cigar_*) or any HEAD (gasalx_semi_cigar_head_*)
+static int semi_cigar_describe(const gasalx_params *params, uint32_t max_q_len, uint32_t max_t_len, char *buf,
+                               uint32_t buf_len, bool heads) {
     if (!valid_params(params) || !buf || buf_len == 0) { gx::set_error("null argument"); return GASALX_EINVAL; }
     buf[0] = 0;
-    int rc = semi_cigar_checks(params, nullptr, nullptr);
+    int rc = semi_cigar_checks(params, nullptr, nullptr, heads);
     if (rc) return rc;
     gx::BatchShape s;
     s.max_q = max_q_len; s.max_t = max_t_len;
     std::string why;
-    const gx::Plan pl = gx::make_semi_cigar_plan(*params, s, false, &rc, &why);
+    const gx::Plan pl = gx::make_semi_cigar_plan(*params, s, false, &rc, &why, heads);
     if (rc) gx::set_error(why);
     std::snprintf(buf, buf_len, "%s", pl.name.c_str());
     return rc;
 }
 
-int gasalx_semi_cigar_device(gasalx_engine *eng, const gasalx_params *params, const gasalx_batch *b,
-                             const gasalx_results *out, void *stream) {
+static int semi_cigar_dev(gasalx_engine *eng, const gasalx_params *params, const gasalx_batch *b,
+                          const gasalx_results *out, void *stream, bool heads) {
     if (!eng || !valid_params(params) || !b || !out) { gx::set_error("null argument"); return GASALX_EINVAL; }
-    int rc = semi_cigar_checks(params, b, out);
+    int rc = semi_cigar_checks(params, b, out, heads);
     if (rc) return rc;
     hipStream_t st;
     if ((rc = enter(eng, stream, &st))) return rc;
@@ -783,13 +786,13 @@ int gasalx_semi_cigar_device(gasalx_engine *eng, const gasalx_params *params, co
     shape.max_q = b->max_q_len;
     shape.max_t = b->max_t_len;
     if ((rc = device_max_lens(b->q_lens, b->t_lens, b->n_alns, st, &shape.max_q, &shape.max_t))) return rc;
-    return gx::semi_cigar_device(eng->ws, *params, *b, *out, st, shape, false);
+    return gx::semi_cigar_device(eng->ws, *params, *b, *out, st, shape, false, heads);
 }
 
-int gasalx_semi_cigar_host(gasalx_engine *eng, const gasalx_params *params, const gasalx_batch *hb,
-                           const gasalx_results *ho) {
+static int semi_cigar_hst(gasalx_engine *eng, const gasalx_params *params, const gasalx_batch *hb,
+                         const gasalx_results *ho, bool heads) {
     if (!eng || !valid_params(params) || !hb || !ho) { gx::set_error("null argument"); return GASALX_EINVAL; }
-    int rc = semi_cigar_checks(params, hb, ho);
+    int rc = semi_cigar_checks(params, hb, ho, heads);
     if (rc) return rc;
     if (!hb->q_batch || !hb->t_batch || !hb->q_offsets || !hb->t_offsets || !hb->q_lens || !hb->t_lens) {
         gx::set_error("missing batch array");
@@ -829,11 +832,36 @@ int gasalx_semi_cigar_host(gasalx_engine *eng, const gasalx_params *params, cons
     gasalx_params by_target = *params;
     by_target.algo = 1;                                                    // the flags launch: by target length
     const bool sort_t = gx::uneven_lengths(by_target, hb->q_lens, hb->t_lens, n);
-    rc = gx::semi_cigar_device(eng->ws, *params, db, dout, st, shape, sort_t);
+    rc = gx::semi_cigar_device(eng->ws, *params, db, dout, st, shape, sort_t, heads);
     return host_finish(st, rc, {{ho->aln_score, dout.aln_score, (size_t)n * 4}, {ho->q_end, dout.q_end, (size_t)n * 4},
                                 {ho->t_end, dout.t_end, (size_t)n * 4}, {ho->q_start, dout.q_start, (size_t)n * 4},
                                 {ho->t_start, dout.t_start, (size_t)n * 4}, {ho->cigar, dout.cigar, hb->q_bytes},
                                 {ho->n_cigar_ops, dout.n_cigar_ops, (size_t)n * 4}});
+}
+
+int gasalx_describe_semi_cigar_plan(const gasalx_params *params, uint32_t max_q_len, uint32_t max_t_len, char *buf,
+                                    uint32_t buf_len) {
+    return semi_cigar_describe(params, max_q_len, max_t_len, buf, buf_len, false);
+}
+int gasalx_semi_cigar_device(gasalx_engine *eng, const gasalx_params *params, const gasalx_batch *b,
+                             const gasalx_results *out, void *stream) {
+    return semi_cigar_dev(eng, params, b, out, stream, false);
+}
+int gasalx_semi_cigar_host(gasalx_engine *eng, const gasalx_params *params, const gasalx_batch *hb,
+                           const gasalx_results *ho) {
+    return semi_cigar_hst(eng, params, hb, ho, false);
+}
+int gasalx_describe_semi_cigar_head_plan(const gasalx_params *params, uint32_t max_q_len, uint32_t max_t_len, char *buf,
+                                         uint32_t buf_len) {
+    return semi_cigar_describe(params, max_q_len, max_t_len, buf, buf_len, true);
+}
+int gasalx_semi_cigar_head_device(gasalx_engine *eng, const gasalx_params *params, const gasalx_batch *b,
+                                  const gasalx_results *out, void *stream) {
+    return semi_cigar_dev(eng, params, b, out, stream, true);
+}
+int gasalx_semi_cigar_head_host(gasalx_engine *eng, const gasalx_params *params, const gasalx_batch *hb,
+                                const gasalx_results *ho) {
+    return semi_cigar_hst(eng, params, hb, ho, true);
 }
 
 int gasalx_pairhmm_device(gasalx_engine *eng, const gasalx_hmm_batch *b, float *res, void *stream) {

@@ -296,7 +296,7 @@ static int launch_wavefront(Workspace &ws, const Plan &pl, const gasalx_params &
         v.key2 = pl.key2; v.ku16 = pl.ku16; v.kseg = pl.kseg_shift != 0;
         v.lrs = pl.wf_algo == WF_LOCAL && !pl.tb && !pl.key2 && A.lstop != nullptr && pl.kf16 != 0 && !pl.kseg_shift;
         v.stop = A.stop != nullptr;
-        WfFn f16 = pl.semi_tb   ? wf16_semi_tb_lookup(pl.G16, pl.R16)
+        WfFn f16 = pl.semi_tb   ? wf16_semi_tb_lookup(pl.G16, pl.R16, pl.semi_heads)
                    : pl.tb_band ? wf16_pick_r4<WF16_GLOBAL_CP>(pl.G16, pl.R16)
                                 : wf16_lookup(pl.wf_algo, pl.G16, pl.R16, v);
         // WITH_START reverse passes: the register axis sized per block (rclass.hip)
@@ -332,7 +332,7 @@ static int launch_wavefront(Workspace &ws, const Plan &pl, const gasalx_params &
     }
     // (the band path's int32 launch aligns its declined blocks without direction words: the walk sends
     // those pairs to the fallback list, whose launch writes them into the capped buffer)
-    return launch_int32(pl, pl.semi_tb ? wf_semi_tb_lookup(pl.G, pl.R)
+    return launch_int32(pl, pl.semi_tb ? wf_semi_tb_lookup(pl.G, pl.R, pl.semi_heads)
                             : A.stop   ? pick_instance<WfK<WF_SEMI, true, false, true>, SHAPES_R4>(pl.G, pl.R)
                                        : wf_lookup(pl.wf_algo, pl.keys, pl.tb && !pl.tb_band, pl.G, pl.R), A, st);
 }
@@ -875,6 +875,7 @@ static TbArgs make_tb_args(const Call &c, uint64_t cigar_cap, const uint8_t *wal
     T.cigar_cap = cigar_cap ? cigar_cap : c.b.q_bytes;
     fill_scoring(T, p);
     T.is_local = pl.semi_tb ? kTbSemi : p.algo == 3;
+    T.semi_head = pl.semi_tb ? p.head : 2;
     T.slot_of = c.slot_of;
     T.sc_nn = p.has_n_penalty ? -p.n_penalty : p.match;   // GLOBAL: N == N is a match unless N_PENALTY
     T.qseq = walk_qseq ? walk_qseq : c.qsrc; T.tseq = c.tsrc; T.toff = c.b.t_offsets; T.seq_packed = c.packed;
@@ -1034,8 +1035,11 @@ int align_device(Workspace &ws, const gasalx_params &p, const gasalx_batch &b, c
 // one stream: the score launch of align_device with WITHOUT_START (score, q_end, t_end: the same
 // kernels, so the same numbers), the direction-flag launch over the same sequences (WF16_SEMI_TB, the
 // int32 kernel for declined blocks), and the walk from (ql - 1, t_end) until the query is exhausted.
+// gasalx_semi_cigar_head_* (heads): the same three steps under any HEAD -- the score launch is
+// align_device's for that HEAD, the flag launch takes the boundary from the kernel argument
+// (WF16_SEMI_TBH; HEAD = TARGET the instances above), the walk ends by that HEAD's rules.
 int semi_cigar_device(Workspace &ws, const gasalx_params &p, const gasalx_batch &b, const gasalx_results &out,
-                      hipStream_t st, const BatchShape &shape, bool sort_t) {
+                      hipStream_t st, const BatchShape &shape, bool sort_t, bool heads) {
     if (b.n_alns == 0 || b.q_bytes == 0 || b.t_bytes == 0) { set_error("empty batch"); return GASALX_EINVAL; }
     if ((b.q_bytes & 7) || (b.t_bytes & 7)) { set_error("batch bytes not a multiple of 8"); return GASALX_EINVAL; }
     if (shape.max_q == 0 || shape.max_t == 0) { set_error("zero-length sequence"); return GASALX_ERANGE; }
@@ -1045,12 +1049,13 @@ int semi_cigar_device(Workspace &ws, const gasalx_params &p, const gasalx_batch 
     BatchShape sized = shape;
     sized.n = n;
     gasalx_params ps = p;
-    ps.algo = 2; ps.start_pos = 0; ps.second_best = 0; ps.head = 2; ps.tail = 2;
+    ps.algo = 2; ps.start_pos = 0; ps.second_best = 0; ps.tail = 2;
+    if (!heads) ps.head = 2;   // (gasalx_semi_cigar_head_*: the caller's HEAD through all three steps)
     int rc = GASALX_OK;
     std::string why;
     BatchShape tshape = sized;
     tshape.sort = sort_t;
-    const Plan tpl = make_semi_cigar_plan(ps, tshape, has_ops, &rc, &why);
+    const Plan tpl = make_semi_cigar_plan(ps, tshape, has_ops, &rc, &why, heads);
     if (rc) { set_error(why); return rc; }
     const Plan spl = make_plan(ps, sized, has_ops);
 

@@ -93,6 +93,8 @@ struct Plan {
     uint32_t band_w = 0, band_wd = 0;
     bool semi_tb = false;   // the direction-flag launch of gasalx_semi_cigar_* (make_semi_cigar_plan): GLOBAL's
                             // traceback kernels under the semi-global boundary (WF16_SEMI_TB / SEMITB)
+    bool semi_heads = false;   // semi_tb under the boundary of params.head (gasalx_semi_cigar_head_* with HEAD
+                               // NONE, QUERY or BOTH: WF16_SEMI_TBH / SEMITB = 2); HEAD = TARGET keeps semi_tb's
     uint32_t max_q = 0, max_t = 0;   // the batch shape the plan was made for
     std::string name;
 };
@@ -114,7 +116,10 @@ Plan make_plan(const gasalx_params &p, const BatchShape &shape, bool has_ops);
 // The direction-flag launch of gasalx_semi_cigar_* (SEMI-GLOBAL, HEAD = TAIL = TARGET, with CIGARs):
 // PLAN_WAVEFRONT, or PLAN_NONE with *why and a GASALX_E* code in *rc when the scores or the lengths
 // have no wavefront form.  The score launch that runs before it is make_plan's, unchanged.
-Plan make_semi_cigar_plan(const gasalx_params &p, const BatchShape &shape, bool has_ops, int *rc, std::string *why);
+// heads: gasalx_semi_cigar_head_* -- p.head is any of the four (TAIL = TARGET), the name carries the head
+// (_hn, _hq, _ht, _hb) and refusals the prefix "semi_cigar_head:"; HEAD = TARGET is the same plan otherwise.
+Plan make_semi_cigar_plan(const gasalx_params &p, const BatchShape &shape, bool has_ops, int *rc, std::string *why,
+                          bool heads = false);
 
 // Host-side check for BatchShape::sort: the padded lengths of the step axis
 // (targets; queries for SEMI-GLOBAL, whose kernel runs transposed) spread over
@@ -153,8 +158,9 @@ int align_device(Workspace &ws, const gasalx_params &p, const gasalx_batch &b, c
 // SEMI-GLOBAL with HEAD = TAIL = TARGET and the alignment itself: the score launch of align_device
 // (score, ends), the direction-flag launch, the walk (CIGAR bytes, op counts, starts).  sort_t: the
 // target lengths are uneven (the flag launch runs its slots in target-length order).
+// heads: gasalx_semi_cigar_head_* (p.head kept: any HEAD, and q_start written); false forces HEAD = TARGET.
 int semi_cigar_device(Workspace &ws, const gasalx_params &p, const gasalx_batch &b, const gasalx_results &out,
-                      hipStream_t stream, const BatchShape &shape, bool sort_t);
+                      hipStream_t stream, const BatchShape &shape, bool sort_t, bool heads = false);
 
 int pairhmm_device(Workspace &ws, const gasalx_hmm_batch &b, float *result, hipStream_t stream, uint32_t max_r,
                    uint32_t max_h);

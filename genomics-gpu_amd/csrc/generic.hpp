@@ -601,6 +601,7 @@ struct TbArgs {
     // (tb_slot: its direction words at slot t of the capped buffer)
     const uint32_t *list, *n_dev;
     uint32_t n_dev_off, tb_slot;
+    int32_t semi_head;                  // kTbSemi: the HEAD whose boundary ends the walk (2 TARGET: gasalx_semi_cigar_*)
 };
 
 // TbArgs::is_local == kTbSemi (gasalx_semi_cigar_*): the GLOBAL state machine from the end cell itself
@@ -609,6 +610,11 @@ struct TbArgs {
 // words are those of the semi-global matrix, whose gaps open from H: wavefront16.hpp WF16_SEMI_TB); the target bases left of that point are the free head and give no ops.
 // A path that reaches column -1 first ends in the left boundary's insertions, as GLOBAL's does.
 // t_start = the first target base consumed (t_end + 1 when none is), q_start = 0.
+// gasalx_semi_cigar_head_* (TbArgs::semi_head, any HEAD): where the walk leaves the matrix, the boundary
+// it meets decides.  Above row 0 with target bases left: free under HEAD TARGET / BOTH (t_start = the
+// column after), the top boundary's deletions under NONE / QUERY (D bytes of their own, t_start = 0).
+// Left of column 0 with query rows left: the left boundary's insertions under NONE / TARGET, free under
+// QUERY / BOTH (no ops, q_start = the row after).
 constexpr int32_t kTbSemi = 2;
 
 // 8 codes of a sequence cached per thread (the walk moves one position at a time)
@@ -772,9 +778,14 @@ __global__ __launch_bounds__(256) void tb_kernel(TbArgs A) {
     put(off++, prev | (uint32_t)(count << 2));
     n_ops++;
     if (A.is_local == kTbSemi) {
+        const bool free_q = (A.semi_head & 1) != 0, free_t = (A.semi_head & 2) != 0;
+        const int ts = free_t ? i + 1 : 0, qs = free_q ? j + 1 : 0;
+        if (free_q) j = -1;
+        if (free_t) i = -1;
+        while (i >= 0) { const int rc = (i + 1) <= 63 ? (i + 1) : 63; put(off++, 2u | (uint32_t)(rc << 2)); n_ops++; i -= 63; }
         while (j >= 0) { const int rc = (j + 1) <= 63 ? (j + 1) : 63; put(off++, 3u | (uint32_t)(rc << 2)); n_ops++; j -= 63; }
-        if (A.tstart) A.tstart[tid] = i + 1;
-        if (A.qstart) A.qstart[tid] = 0;
+        if (A.tstart) A.tstart[tid] = ts;
+        if (A.qstart) A.qstart[tid] = qs;
     } else if (!A.is_local) {
         while (i >= 0) { const int rc = (i + 1) <= 63 ? (i + 1) : 63; put(off++, 2u | (uint32_t)(rc << 2)); n_ops++; i -= 63; }
         while (j >= 0) { const int rc = (j + 1) <= 63 ? (j + 1) : 63; put(off++, 3u | (uint32_t)(rc << 2)); n_ops++; j -= 63; }

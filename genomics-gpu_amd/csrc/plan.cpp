@@ -77,6 +77,18 @@ static bool semi_window(const gasalx_params &p, int64_t q8, int64_t t8, int64_t 
 // row.  Every cell has H >= F >= -(OE + e*r) (the insertion run from H(-1, c) = 0), stored + e*(r + c)
 // >= B - OE, and the gap candidates tmp - OE >= -(2*OE + K + e*r) likewise stay within 2*OE + K + 2e
 // of B whatever the span; values rise by at most a per diagonal step and by the frame, e per row + column.
+// The other heads (gasalx_semi_cigar_head_*), boundary by boundary, H for the true value and B + H + e*(r + c)
+// stored:
+//   top, HEAD NONE / QUERY: the value above (0, c) is -(o + e*c), which falls by e per column as GLOBAL's
+//     top row does -- but the frame adds e per column, so stored it is the constant B - o, the diagonal
+//     into (0, c) B - 2e - o and F(0, c) B - 2o - e.  Every cell has H >= F >= -(o + e*c) - (OE + e*r), the
+//     insertion run from above, stored >= B - (OE + o): no cell falls below B - 2*OE whatever the span, one
+//     OE lower than under the free target head.  Gap candidates H - OE and tmp - OE stay above B - 3*OE - K.
+//   left, HEAD QUERY / BOTH: H(r, -1) = 0 and E(r, c) >= -e*(c + 1), stored >= B + e*(r - 1) >= B - e;
+//     stored H(r, -1) = B + e*(r - 1) rises with the row, by less than e*span over the rows a shape
+//     computes (pad and register rows up to G*R included), which `rise` already holds.
+//   above: H <= a * min(r + 1, c + 1) under every head (no boundary value is positive).
+// So one bound serves the four heads: v = 4*OE + K + 2e + 64 lies below B - 3*OE - K - 2e.
 static bool semi_cigar_window(const gasalx_params &p, int64_t q8, int64_t t8, int64_t span, int32_t *vmin) {
     const int64_t e = p.gap_extend, oe = (int64_t)p.gap_open + e, k = global_k(p);
     return drift_window(p, q8, t8, k, 4 * oe + k + 2 * e + 64, e * span, vmin);
@@ -342,8 +354,10 @@ Plan make_plan(const gasalx_params &p, const BatchShape &s, bool has_ops) {
     return pl;
 }
 
-Plan make_semi_cigar_plan(const gasalx_params &p, const BatchShape &s, bool has_ops, int *rc, std::string *why) {
+Plan make_semi_cigar_plan(const gasalx_params &p, const BatchShape &s, bool has_ops, int *rc, std::string *why,
+                          bool heads) {
     Plan pl;
+    const std::string call = heads ? "semi_cigar_head: " : "semi_cigar: ";
     pl.max_q = s.max_q; pl.max_t = s.max_t;
     pl.name = "none";
     *rc = GASALX_OK;
@@ -352,25 +366,27 @@ Plan make_semi_cigar_plan(const gasalx_params &p, const BatchShape &s, bool has_
     // (an extension dearer than an opening, or a gap that scores: the walk's "extended" bit could then
     // name a source the maximum did not take)
     if (p.gap_open < 0 || p.gap_extend < 0)
-        return refuse(GASALX_EUNSUPPORTED, "semi_cigar: negative gap_open or gap_extend is not supported");
+        return refuse(GASALX_EUNSUPPORTED, call + "negative gap_open or gap_extend is not supported");
     if (!int16_safe(p, s.max_q, s.max_t) || t8 >= 32000)
-        return refuse(GASALX_ERANGE, "semi_cigar: lengths x scores leave the int16 range the semi-global kernels keep");
+        return refuse(GASALX_ERANGE, call + "lengths x scores leave the int16 range the semi-global kernels keep");
     const Int32Why i32 = pick_int32_shape(pl, q8, t8);
     const Shape &last = kShapes[sizeof(kShapes) / sizeof(kShapes[0]) - 1];
     if (i32 == QUERY_TOO_LONG)
-        return refuse(GASALX_ERANGE, "semi_cigar: padded query of " + std::to_string(q8) +
+        return refuse(GASALX_ERANGE, call + "padded query of " + std::to_string(q8) +
                                      " over the largest wavefront shape (" + std::to_string(last.G * last.R) + " rows)");
     if (i32 == TARGET_TOO_LONG)
-        return refuse(GASALX_ERANGE, "semi_cigar: padded target of " + std::to_string(t8) + " needs more than 160 KB of LDS");
+        return refuse(GASALX_ERANGE, call + "padded target of " + std::to_string(t8) + " needs more than 160 KB of LDS");
     pl.kind = PLAN_WAVEFRONT;
     pl.wf_algo = WF_GLOBAL;   // query rows in registers, target on the step axis
     pl.semi_tb = true; pl.tb = true; pl.need_pack = has_ops;
+    pl.semi_heads = heads && p.head != 2;   // HEAD = TARGET: gasalx_semi_cigar_*'s instances
     if (env_flag("GASALX_PACKED16", true) && semi_cigar_window(p, q8, t8, conservative_span(q8, t8), &pl.vmin))
         // the traceback shapes; n does not widen G (traceback keeps G = 8 up)
         pl.packed16 = set_packed_shape(pl, pick_packed_shape(q8, packed_gmin(0, true), true), t8) &&
                       semi_cigar_window(p, q8, t8, packed_span(pl.G16, pl.R16, t8), &pl.vmin);
     pl.name = pl.packed16 ? "wavefront16_semi_tb" + shape_name(pl.G16, pl.R16)
                           : "wavefront_semi_tb" + shape_name(pl.G, pl.R);
+    if (heads) pl.name += std::string("_h") + "nqtb"[p.head & 3];
     return pl;
 }
 

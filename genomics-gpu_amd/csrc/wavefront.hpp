@@ -173,8 +173,11 @@ __device__ __forceinline__ uint32_t load4_codes_dir(const WfArgs &A, const uint8
 // semi-global kernels' matrix for HEAD = TARGET -- H(-1, c) = 0 and F(0, c) = -(o + e) above row 0, E(r, 0)
 // = H(r, -1) - (o + e) (semiglobal_kernel_template.h:87-99,123-128), gaps opened from H (:17-28; bits 2
 // and 3 test H - OE against E - e and F - e), the LOCAL N rule -- and no score: the SEMI score launch
-// has written it.
-template <int ALGO, bool KEYS, bool TB, int G, int R, bool EXACT, bool STOP, bool SEMITB = false>
+// has written it.  SEMITB = 2 (gasalx_semi_cigar_head_*): the same under the boundary of A.head, any of the
+// four -- HEAD QUERY / BOTH: H(r, -1) = 0 and E(r, 0) = -e (E(r, -1) = 0, :87-93); HEAD NONE / QUERY: above
+// (0, c) stands -(o + e*c), so F(0, c) = -(o + e*c) - (o + e), and the diagonal into (0, c) is 0 for c = 0,
+// -(o + e*c) otherwise (:123-128, Q3).  The HEAD = TARGET instances (SEMITB = 1) read no head.
+template <int ALGO, bool KEYS, bool TB, int G, int R, bool EXACT, bool STOP, int SEMITB = 0>
 __device__ __forceinline__ void wf_body(const WfArgs &A, const uint8_t *tcodes, const uint32_t lg,
                                         const uint32_t pair, const uint32_t tbi, const bool valid, const uint32_t ql,
                                         const uint32_t tl, const uint32_t qpad, const uint32_t tpad,
@@ -199,8 +202,8 @@ __device__ __forceinline__ void wf_body(const WfArgs &A, const uint8_t *tcodes, 
         if (ALGO == WF_LOCAL) {
             Hk[k] = 0; Ek[k] = 0;                               // local_kernel_template.h:118-120
         } else if (ALGO == WF_GLOBAL) {
-            Hk[k] = (r == 0) ? 0 : -(A.o + A.e * r);            // global.h:57-60 (Q2)
-            Ek[k] = SEMITB ? Hk[k] - OE : -32768;
+            Hk[k] = (r == 0 || (SEMITB == 2 && head_q)) ? 0 : -(A.o + A.e * r);   // global.h:57-60 (Q2)
+            Ek[k] = SEMITB ? ((SEMITB == 2 && head_q) ? -ext : Hk[k] - OE) : -32768;
         } else {
             const int32_t h = head_q ? 0 : ((r == 0) ? 0 : -(A.o + A.e * r));   // semiglobal :87-99
             Hk[k] = h - OE;
@@ -212,7 +215,7 @@ __device__ __forceinline__ void wf_body(const WfArgs &A, const uint8_t *tcodes, 
         // the upper lane's bottom row at column -1 (its initial H)
         const int32_t rb = (int32_t)r0 - 1;
         int32_t hb;
-        if (ALGO == WF_GLOBAL) hb = (rb <= 0) ? 0 : -(A.o + A.e * rb);
+        if (ALGO == WF_GLOBAL) hb = (rb <= 0 || (SEMITB == 2 && head_q)) ? 0 : -(A.o + A.e * rb);
         else hb = (head_q ? 0 : ((rb <= 0) ? 0 : -(A.o + A.e * rb))) - OE;
         recvH = hb; prevRecvH = hb;
     }
@@ -228,8 +231,8 @@ __device__ __forceinline__ void wf_body(const WfArgs &A, const uint8_t *tcodes, 
         if (lg == 0) {
             if (ALGO == WF_LOCAL) { diag = 0; f = 0; }                    // p[],f[] reset per strip
             else if (ALGO == WF_GLOBAL && SEMITB) {
-                diag = 0;
-                f = -OE;
+                diag = (SEMITB == 2 && !head_t && c > 0) ? -(A.o + A.e * c) : 0;
+                f = ((SEMITB == 2 && !head_t) ? -(A.o + A.e * c) : 0) - OE;
             } else if (ALGO == WF_GLOBAL) {
                 diag = (c <= 0) ? 0 : -(A.o + A.e * c);                    // global.h:70
                 f = -32768;                                                // global.h:69
@@ -421,7 +424,7 @@ __device__ __forceinline__ void wf_body(const WfArgs &A, const uint8_t *tcodes, 
 }
 
 // One block's pairs (virtual block bx) of the int32 kernel.
-template <int ALGO, bool KEYS, bool TB, int G, int R, bool STOP, bool SEMITB = false>
+template <int ALGO, bool KEYS, bool TB, int G, int R, bool STOP, int SEMITB = 0>
 __device__ __forceinline__ void wf_block(const WfArgs &A, uint8_t *lds, const uint32_t bx) {
     constexpr int P = 64 / G;
     const uint32_t lane = threadIdx.x & 63;
@@ -523,8 +526,9 @@ __global__ __launch_bounds__(kBlock) void wf_kernel(WfArgs A) {
     }
 }
 
-// wf_kernel's loop over the GLOBAL + traceback block under the semi-global boundary (wf_body SEMITB)
-template <int G, int R>
+// wf_kernel's loop over the GLOBAL + traceback block under the semi-global boundary (wf_body SEMITB):
+// HEADS false HEAD = TARGET (SEMITB = 1), true the boundary of A.head (SEMITB = 2)
+template <int G, int R, bool HEADS = false>
 __global__ __launch_bounds__(kBlock) void wf_semi_tb_kernel(WfArgs A) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     constexpr uint32_t PPB = kWavesPerBlock * (64 / G);
@@ -540,11 +544,11 @@ __global__ __launch_bounds__(kBlock) void wf_semi_tb_kernel(WfArgs A) {
             run = !all;
         }
         for (uint64_t m = __ballot(run); m; m &= m - 1)
-            wf_block<WF_GLOBAL, false, true, G, R, false, true>(A, lds, base + (uint32_t)__builtin_ctzll(m) * gridDim.x);
+            wf_block<WF_GLOBAL, false, true, G, R, false, HEADS ? 2 : 1>(A, lds, base + (uint32_t)__builtin_ctzll(m) * gridDim.x);
     }
 }
 
 // its instances (semi_tb.hip): the R % 4 == 0 shapes, NULL for any other
-void (*wf_semi_tb_lookup(int G, int R))(WfArgs);
+void (*wf_semi_tb_lookup(int G, int R, bool heads = false))(WfArgs);
 
 }  // namespace gx

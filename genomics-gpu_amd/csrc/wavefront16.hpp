@@ -653,6 +653,12 @@ constexpr int kW16_LTBD_WAVES = 2;
 // stream leaves the score and t_end, which the walk reads (generic.hpp tb_kernel, SEMI mode).
 constexpr int WF16_SEMI_TB = 15;
 constexpr int kW16_STB_WAVES = 2;
+// The same for gasalx_semi_cigar_head_* under the boundary of A.head (NONE, QUERY or BOTH; HEAD = TARGET
+// keeps the instances above).  HEAD QUERY / BOTH: H(r, -1) = 0 and E(r, 0) = -e -- in the e-drift frame
+// H(r, -1) is then one value per row, left(r0) + e*k in register k, and E(r, 0) the same pattern; HEAD
+// NONE / QUERY: GLOBAL's diagonal along the top row (0 into column 0, -(o + e*c) otherwise) and F(0, c)
+// = -(o + e*c) - (o + e), in the frame one constant.  All of them wave-uniform selects on A.head.
+constexpr int WF16_SEMI_TBH = 16;
 constexpr int kW16_TQ_WAVES = 3;
 constexpr int kW16_TQ_BIG_WAVES = 3;   // R > 20: 3 waves spill (R = 23: 20 VGPRs) and still beat 2 (profiles/r03_semi_tq_waves_ab.md)
 constexpr int kW16_CP_WAVES = 3;    // GLOBAL score sweep with band checkpoints, then its band pass
@@ -662,7 +668,7 @@ __host__ __device__ constexpr int wf16_waves(int algo, int R) {
     return algo == WF16_GLOBAL_TB ? kW16_TB_WAVES
            : algo == WF16_LOCAL_TB ? kW16_LTB_WAVES
            : algo == WF16_LOCAL_TBD ? kW16_LTBD_WAVES
-           : algo == WF16_SEMI_TB ? kW16_STB_WAVES
+           : algo == WF16_SEMI_TB || algo == WF16_SEMI_TBH ? kW16_STB_WAVES
            : algo == WF16_LOCAL_K2 ? kW16_K2_WAVES
            : algo == WF16_SEMI_TQ ? (R > 20 ? kW16_TQ_BIG_WAVES : kW16_TQ_WAVES)
            : algo == WF16_GLOBAL_CP ? kW16_CP_WAVES
@@ -737,7 +743,8 @@ Wf16Fn wf16_local_lookup(int G, int R, bool u16, bool rs, bool seg = false);
 // WITH_START reverse passes with the register axis sized per block (rclass.hip): NULL when the
 // plan's instance (algo, G, R) has no class set
 Wf16Fn wf16_rclass_lookup(int algo, int G, int R);
-// SEMI-GLOBAL direction flags (semi_tb.hip, WF16_SEMI_TB): the R % 4 == 0 shapes, NULL for any other
-Wf16Fn wf16_semi_tb_lookup(int G, int R);
+// SEMI-GLOBAL direction flags (semi_tb.hip, WF16_SEMI_TB; heads: WF16_SEMI_TBH): the R % 4 == 0 shapes, NULL
+// for any other
+Wf16Fn wf16_semi_tb_lookup(int G, int R, bool heads = false);
 
 }  // namespace gx

@@ -8,7 +8,8 @@
 // the compiler's decisions for the sweep: the SEMI G8R23 loop issued 21 VALU and 71 SALU more
 // per trip, 1.7-4.7 % slower, profiles/r05/g_rclass.md.)
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    constexpr bool STB = ALGO_ == WF16_SEMI_TB;   // GLOBAL_TB's sweep under the free target head, no captures
+    constexpr bool STH = ALGO_ == WF16_SEMI_TBH;  // ... under the boundary of A.head
+    constexpr bool STB = ALGO_ == WF16_SEMI_TB || STH;   // GLOBAL_TB's sweep under the free target head, no captures
     constexpr bool GTB = ALGO_ == WF16_GLOBAL_TB || STB;
     constexpr bool GCP = ALGO_ == WF16_GLOBAL_CP;
     constexpr bool GT = GTB || GCP;   // the traceback kernels' declines and start-cell capture
@@ -623,17 +624,21 @@
         const int32_t pb = P.base, go = A.o, ge = A.e, D = P.drift;   // D = e (step_global)
         const uint32_t KX = pk_bcast(P.k - 2 * D), OEX = pk_bcast(P.k - 2 * D + A.o + A.e - D);
         // H(r, -1) (Q2), stored at anti-diagonal r - 1
+        // STH: the free query head (HEAD QUERY / BOTH) holds 0 in every row, the priced top boundary (HEAD
+        // NONE / QUERY) GLOBAL's diagonal and one F
+        const bool hq = STH && (A.head & 1) != 0, ht = !STH || (A.head & 2) != 0;
         auto left = [=](int32_t r) -> uint32_t {
-            return (uint32_t)(pb + D * (r - 1) - (r <= 0 ? 0 : go + ge * r)) * 0x10001u;
+            return (uint32_t)(pb + D * (r - 1) - (r <= 0 || hq ? 0 : go + ge * r)) * 0x10001u;
         };
         const uint32_t L_0 = (uint32_t)(pb - D) * 0x10001u, L_in = (uint32_t)(pb - D - go) * 0x10001u;   // left(0), left(r >= 1)
+        const uint32_t L_q = STH ? left((int32_t)r0) : 0;   // hq: H(r0 + k, -1) = L_q + e*k in the frame
         uint32_t HA[R], HB[R], Ek[R];
         uint32_t dw[GTB ? R : 1];                      // traceback nibbles: last 4 steps per half
 #pragma unroll
         for (int k = 0; k < R; ++k) {
             HA[k] = left((int32_t)(r0 + k));
             HB[k] = HA[k];
-            Ek[k] = STB ? pk_subnb(HA[k], GO) : NN;
+            Ek[k] = STB ? (hq ? HA[k] : pk_subnb(HA[k], GO)) : NN;   // hq: E(r, 0) = -e, H(r, -1)'s pattern
         }
 #pragma unroll
         for (int k = 0; k < (GTB ? R : 1); ++k) dw[k] = 0;
@@ -700,8 +705,8 @@
                 // ~60 VALU per step of the first G steps)
 #pragma unroll
                 for (int k = 0; k < R; ++k) {
-                    Hout[k] = k == 0 && r0 == 0 ? L_0 : L_in;
-                    Ek[k] = STB ? pk_subnb(Hout[k], GO) : NN;   // STB: E(r, 0) = H(r, -1) - OE
+                    Hout[k] = hq ? L_q + (uint32_t)(D * k) * 0x10001u : k == 0 && r0 == 0 ? L_0 : L_in;
+                    Ek[k] = STB ? (hq ? Hout[k] : pk_subnb(Hout[k], GO)) : NN;   // STB: E(r, 0) = H(r, -1) - OE
                 }
                 f = NN;
                 if (GTB && j == 0) {
@@ -717,7 +722,12 @@
                     const int32_t cs = (int32_t)s + j;
                     const uint32_t dfree = (uint32_t)(pb + D * (cs - 2)) * 0x10001u;
                     const uint32_t ffree = (uint32_t)(pb - go - ge + D * cs) * 0x10001u;
-                    step_global_tb<R, false, true>(T, top ? dfree : prevRecvH, top ? ffree : recvF, xs, Hin, Hout, Ek,
+                    // priced top boundary: the diagonal as GLOBAL's dtop at the step's column, F(0, c) =
+                    // -(o + e*c) - (o + e) at anti-diagonal c
+                    const uint32_t dpaid = (uint32_t)(pb + D * (cs - 2) - (cs <= 0 ? 0 : go + ge * cs)) * 0x10001u;
+                    const uint32_t fpaid = (uint32_t)(pb - 2 * go - ge) * 0x10001u;
+                    const uint32_t dt = ht ? dfree : dpaid, ft = ht ? ffree : fpaid;
+                    step_global_tb<R, false, true>(T, top ? dt : prevRecvH, top ? ft : recvF, xs, Hin, Hout, Ek,
                                                    dw, f, KX, OEX, NN, j, GO);
                 } else if constexpr (GTB)
                     step_global_tb<R>(T, top ? dtop : prevRecvH, top ? NN : recvF, xs, Hin, Hout, Ek, dw, f, KX,

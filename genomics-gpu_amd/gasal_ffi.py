@@ -30,6 +30,7 @@ EXPORTS = (
     "gasalx_abi_version", "gasalx_last_error", "gasalx_device_count", "gasalx_engine_create",
     "gasalx_engine_destroy", "gasalx_align_device", "gasalx_align_host", "gasalx_describe_plan",
     "gasalx_semi_cigar_device", "gasalx_semi_cigar_host", "gasalx_describe_semi_cigar_plan",
+    "gasalx_semi_cigar_head_device", "gasalx_semi_cigar_head_host", "gasalx_describe_semi_cigar_head_plan",
     "gasalx_pairhmm_device", "gasalx_pairhmm_host", "gasalx_pairhmm_params", "gasalx_synth_sizes",
     "gasalx_synth_spec", "gasalx_synth_pairs", "gasalx_synth_range", "gasalx_host_alloc", "gasalx_host_free",
     "gasalx_pairhmm_quals_device", "gasalx_pairhmm_quals_host", "gasalx_hmm_file_read", "gasalx_hmm_file_free",
@@ -326,7 +327,8 @@ class Engine:
         out["n_ops"] = n_ops
         return out
 
-    def semi_cigar_host(self, batch: Batch, params: Params, q_ops=None, t_ops=None, max_q_len=0, max_t_len=0):
+    def semi_cigar_host(self, batch: Batch, params: Params, q_ops=None, t_ops=None, max_q_len=0, max_t_len=0,
+                        call="gasalx_semi_cigar_host"):
         """SEMI_GLOBAL, HEAD = TAIL = TARGET, with the alignment (gasalx_semi_cigar_host): the dict
         align_host returns for WITHOUT_START (score, q_end, t_end) plus t_start, q_start, cigar (uint8,
         q_bytes; decode_cigar reads it) and n_ops."""
@@ -340,14 +342,25 @@ class Engine:
                     _p(batch.t_lens), batch.q_bytes, batch.t_bytes, n, _p(qo), _p(to), None, max_q_len, max_t_len)
         cr = CResults(_p(out["score"]), _p(out["q_end"]), _p(out["t_end"]), _p(out["q_start"]), _p(out["t_start"]),
                       None, None, None, _p(cigar), _p(n_ops))
-        _check(lib().gasalx_semi_cigar_host(self._h, ctypes.byref(params), ctypes.byref(cb), ctypes.byref(cr)),
-               "semi_cigar_host")
+        _check(getattr(lib(), call)(self._h, ctypes.byref(params), ctypes.byref(cb), ctypes.byref(cr)),
+               call[len("gasalx_"):])
         out["cigar"] = cigar
         out["n_ops"] = n_ops
         return out
 
+    def semi_cigar_head_host(self, batch: Batch, params: Params, q_ops=None, t_ops=None, max_q_len=0, max_t_len=0):
+        """semi_cigar_host for any HEAD (gasalx_semi_cigar_head_host; TAIL = TARGET): q_start is the first
+        query base the path consumes under HEAD QUERY / BOTH."""
+        return self.semi_cigar_host(batch, params, q_ops, t_ops, max_q_len, max_t_len, "gasalx_semi_cigar_head_host")
+
+    def semi_cigar_head_device_ptrs(self, params: Params, ptrs: dict, q_bytes: int, t_bytes: int, n: int, max_q: int,
+                                    max_t: int, stream: int = 0):
+        """Device-resident gasalx_semi_cigar_head_device: arguments as semi_cigar_device_ptrs."""
+        self.semi_cigar_device_ptrs(params, ptrs, q_bytes, t_bytes, n, max_q, max_t, stream,
+                                    "gasalx_semi_cigar_head_device")
+
     def semi_cigar_device_ptrs(self, params: Params, ptrs: dict, q_bytes: int, t_bytes: int, n: int, max_q: int,
-                               max_t: int, stream: int = 0):
+                               max_t: int, stream: int = 0, call="gasalx_semi_cigar_device"):
         """Device-resident gasalx_semi_cigar_device: ptrs as align_device_ptrs (aln_score, cigar and
         n_cigar_ops required; cigar a buffer of its own)."""
         g = lambda k: ptrs.get(k) or None
@@ -355,8 +368,8 @@ class Engine:
                     t_bytes, n, g("q_ops"), g("t_ops"), None, max_q, max_t)
         cr = CResults(g("aln_score"), g("q_end"), g("t_end"), g("q_start"), g("t_start"), g("aln_score2"),
                       g("q_end2"), g("t_end2"), g("cigar"), g("n_cigar_ops"))
-        _check(lib().gasalx_semi_cigar_device(self._h, ctypes.byref(params), ctypes.byref(cb), ctypes.byref(cr),
-                                              ctypes.c_void_p(stream or None)), "semi_cigar_device")
+        _check(getattr(lib(), call)(self._h, ctypes.byref(params), ctypes.byref(cb), ctypes.byref(cr),
+                                    ctypes.c_void_p(stream or None)), call[len("gasalx_"):])
 
     def packed_pairs(self):
         """(handled, total): pairs of the last packed launches the packed kernels aligned themselves
@@ -793,6 +806,14 @@ def describe_semi_cigar_plan(params: Params, max_q: int, max_t: int) -> str:
     buf = ctypes.create_string_buffer(128)
     _check(lib().gasalx_describe_semi_cigar_plan(ctypes.byref(params), max_q, max_t, buf, 128),
            "describe_semi_cigar_plan")
+    return buf.value.decode()
+
+
+def describe_semi_cigar_head_plan(params: Params, max_q: int, max_t: int) -> str:
+    """The same for gasalx_semi_cigar_head_* (any HEAD): the name ends in _hn, _hq, _ht or _hb."""
+    buf = ctypes.create_string_buffer(128)
+    _check(lib().gasalx_describe_semi_cigar_head_plan(ctypes.byref(params), max_q, max_t, buf, 128),
+           "describe_semi_cigar_head_plan")
     return buf.value.decode()
 
 

@@ -157,6 +157,33 @@ int gasalx_semi_cigar_host(gasalx_engine *eng, const gasalx_params *params, cons
 int gasalx_describe_semi_cigar_plan(const gasalx_params *params, uint32_t max_q_len, uint32_t max_t_len, char *buf,
                                     uint32_t buf_len);
 
+/* The same call for every HEAD: params->head is NONE, QUERY, TARGET or BOTH, params->tail must be TARGET
+ * (anything else is GASALX_EUNSUPPORTED).  Structs, required outputs, the overlay check, the capacity
+ * rule, q_ops / t_ops / is_packed and the order of the errors are those of gasalx_semi_cigar_*; messages
+ * start "semi_cigar_head:".  With HEAD = TARGET every output is byte-identical to gasalx_semi_cigar_*.
+ *   aln_score, q_end, t_end   what gasalx_align_* returns for that HEAD with WITHOUT_START, bit for bit
+ *   HEAD NONE    anchored at (0, 0): the ops consume the whole query and target bases 0 .. t_end; t_start
+ *                = 0, q_start = 0.  Target bases left of the path's first cell are a leading D run
+ *   HEAD QUERY   the query's prefix is free: the ops consume query bases q_start .. and target bases
+ *                0 .. t_end; t_start = 0
+ *   HEAD BOTH    either prefix is free: query bases q_start .., target bases t_start .. t_end
+ *   q_start      written when the pointer is given (0 under HEAD NONE / TARGET)
+ * Boundary prices a caller who re-scores a path must know (they are the reference kernel's, Q3 of the
+ * survey): a deletion run that starts at a free query head (HEAD QUERY / BOTH, q_start > 0, the path's
+ * first op) costs e per base, not o + e -- E(r, -1) = 0 there; under HEAD NONE / QUERY the value above
+ * cell (0, c) is -(o + e*c), so a leading D run of k bases followed by M / X costs o + e*k, followed by
+ * an insertion o + e*(k - 1): c + 1 target bases stand above column c for the price of c, one base for
+ * o.  Under HEAD NONE / TARGET a leading I run of k bases at t_start = 0 costs o + e*(k - 1), one base
+ * nothing, as in gasalx_semi_cigar_*.
+ * gasalx_describe_semi_cigar_head_plan: the names of gasalx_describe_semi_cigar_plan with the head
+ * appended (_hn, _hq, _ht, _hb). */
+int gasalx_semi_cigar_head_device(gasalx_engine *eng, const gasalx_params *params, const gasalx_batch *dev_batch,
+                                  const gasalx_results *dev_out, void *stream);
+int gasalx_semi_cigar_head_host(gasalx_engine *eng, const gasalx_params *params, const gasalx_batch *host_batch,
+                                const gasalx_results *host_out);
+int gasalx_describe_semi_cigar_head_plan(const gasalx_params *params, uint32_t max_q_len, uint32_t max_t_len,
+                                         char *buf, uint32_t buf_len);
+
 /* Diagnostics: pairs of the engine's last packed (two-pairs-per-lane) launches that the packed
  * kernel aligned itself (*handled) out of the pairs those launches covered (*total); the rest went
  * to the int32 kernel.  The engine's own workspace and its two host-pipeline stages each count

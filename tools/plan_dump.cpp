@@ -106,20 +106,22 @@ void plan_pass(const char *env, const Scores (&scores)[N], uint32_t n, bool ops)
                             }
 }
 
+// heads: make_semi_cigar_plan as gasalx_semi_cigar_head_* calls it, over the four heads
 template <size_t N>
-void semi_cigar_pass(const char *env, const Scores (&scores)[N]) {
+void semi_cigar_pass(const char *env, const Scores (&scores)[N], bool heads = false) {
     static const auto pairs = length_pairs();
     set_env(env);
     for (const Scores &sc : scores)
-        for (const auto &qt : pairs) {
-            const gasalx_params p = params(kSemi, 0, 0, kTarget, kTarget, sc);
-            gx::BatchShape s;
-            s.max_q = qt.first; s.max_t = qt.second;
-            int rc = 0;
-            std::string why;
-            const gx::Plan pl = gx::make_semi_cigar_plan(p, s, false, &rc, &why);
-            print_row("semi_cigar", env, p, s, false, pl, rc, why);
-        }
+        for (const auto &qt : pairs)
+            for (int head = heads ? 0 : kTarget; head < (heads ? 4 : kTarget + 1); head++) {
+                const gasalx_params p = params(kSemi, 0, 0, head, kTarget, sc);
+                gx::BatchShape s;
+                s.max_q = qt.first; s.max_t = qt.second;
+                int rc = 0;
+                std::string why;
+                const gx::Plan pl = gx::make_semi_cigar_plan(p, s, false, &rc, &why, heads);
+                print_row(heads ? "semi_cigar_head" : "semi_cigar", env, p, s, false, pl, rc, why);
+            }
 }
 
 }  // namespace
@@ -135,6 +137,11 @@ int main() {
     for (const char *env : {"", "GASALX_PACKED16=0"}) {
         semi_cigar_pass(env, kScores);
         semi_cigar_pass(env, kExtraScores);
+    }
+    // (after every earlier row, so that a dump of an older planner is a prefix of this one)
+    for (const char *env : {"", "GASALX_PACKED16=0"}) {
+        semi_cigar_pass(env, kScores, true);
+        semi_cigar_pass(env, kExtraScores, true);
     }
     set_env("");
     std::fprintf(stderr, "%ld rows\n", g_rows);

@@ -7,7 +7,10 @@ gasalx_nv_describe_plan and gasalx_nv_describe_sinks_plan give over nv_plan_grid
 With --semi-cigar: tests/golden/semi_cigar_plan_names.json, the names (or refusals)
 gasalx_describe_semi_cigar_plan gives over the grid of tests/test_semi_cigar_model.py, one row per key.
 
-usage: GASALX_LIB=/path/to/parent/libgasal.so plan_grid.py [--nv | --semi-cigar] COMMIT [OUT.json]
+With --semi-cigar-head: tests/golden/semi_cigar_head_plan_names.json, the same for
+gasalx_describe_semi_cigar_head_plan over the four heads (tests/test_semi_cigar_head_model.py).
+
+usage: GASALX_LIB=/path/to/parent/libgasal.so plan_grid.py [--nv | --semi-cigar | --semi-cigar-head] COMMIT [OUT.json]
 
 A fixture pins its planner across host-side refactors, so it is written from a build of the
 commit *before* the change under test (COMMIT, recorded in the file), never from the branch.
@@ -34,10 +37,24 @@ def semi_cigar(commit, out):
     print(f"{len(rows)} rows -> {out}")
 
 
+def semi_cigar_head(commit, out):
+    import test_semi_cigar_head_model as S
+    rows = S.semi_cigar_head_plan_rows(os.environ.__setitem__, lambda s: os.environ.pop(s, None))
+    doc = {"commit": commit, "lens": list(S.PLAN_LENS), "scores": [list(s) for s in S.PLAN_SCORES],
+           "envs": list(S.PLAN_ENVS), "heads": ["hn", "hq", "ht", "hb"], "rows": rows}
+    with open(out, "w") as f:
+        json.dump(doc, f, indent=0, sort_keys=True)
+        f.write("\n")
+    print(f"{len(rows)} rows -> {out}")
+
+
 def main():
     nv = "--nv" in sys.argv
-    args = [a for a in sys.argv[1:] if a not in ("--nv", "--semi-cigar")]
+    args = [a for a in sys.argv[1:] if a not in ("--nv", "--semi-cigar", "--semi-cigar-head")]
     commit = args[0]
+    if "--semi-cigar-head" in sys.argv:
+        return semi_cigar_head(commit, args[1] if len(args) > 1 else
+                               os.path.join(ROOT, "tests", "golden", "semi_cigar_head_plan_names.json"))
     if "--semi-cigar" in sys.argv:
         return semi_cigar(commit, args[1] if len(args) > 1 else
                           os.path.join(ROOT, "tests", "golden", "semi_cigar_plan_names.json"))
