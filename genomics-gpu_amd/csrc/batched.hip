@@ -17,6 +17,7 @@
 #include "nvtrace.hpp"
 #include "nvbio16.hpp"
 #include "nvbanded.hpp"
+#include "nvbanded_sink.hpp"
 #include "nvmyers.hpp"
 
 namespace gx {
@@ -349,6 +350,48 @@ int nv_banded_score_device(const gasalx_nv_aligner &al, uint32_t band, uint32_t 
     using Fn = void (*)(NvBandArgs);
     const Fn fn = nv_static(al.aligner, al.type, ex, [band](auto a, auto t, auto e) -> Fn {
         return GX_BAND_PICK(nv_banded_kernel, a, t, e); });
+    return launch_checked(fn, (n + 255) / 256, st, A);
+}
+
+// ---- The same scorer with the BestSink position (nvbanded_sink.hpp).  nv_banded_score_device's
+//      checks in its order and its choice of family: the packed kernel inside nvb16_ok's
+//      conditions, the int32 kernel otherwise, at the same BMAX; "_sink" marks the name. ----
+int nv_banded_sinks_plan_name(const gasalx_nv_aligner &al, uint32_t band, uint32_t max_p, uint32_t text_bits,
+                              std::string &name) {
+    static const char *an[] = {"ed", "sw", "gotoh"}, *tn[] = {"global", "local", "semi"};
+    const gasalx_nv_strings pat = {nullptr, nullptr, 0, 2, 0}, txt = {nullptr, nullptr, 0, text_bits, 0};
+    if (int rc = nv_check(al, "bad aligner", "bad aligner", &band, pat, txt)) return rc;
+    uint32_t base = 0;
+    const bool packed = max_p && nvb16_ok(nv_scheme(al), text_bits, max_p, band, &base);
+    name = std::string(packed ? "nvbio_banded16_" : "nvbio_banded_") + an[al.aligner] + "_" + tn[al.type] + "_b" +
+           std::to_string(band <= 8 ? 8 : band <= 16 ? 16 : 32) + "_sink";
+    return GASALX_OK;
+}
+
+int nv_banded_score_sinks_device(const gasalx_nv_aligner &al, uint32_t band, uint32_t n, const gasalx_nv_strings &pat,
+                                 const gasalx_nv_strings &txt, int32_t *scores, uint32_t *sinks, hipStream_t st,
+                                 uint32_t max_p) {
+    if (int rc = nv_check(al, "bad aligner", "bad aligner", &band, pat, txt)) return rc;
+    if (n == 0) return GASALX_OK;
+    if (int rc = nv_check_ptrs(pat, txt, scores || sinks)) return rc;
+    const NvScheme s = nv_scheme(al);
+    const bool ex = band == 8 || band == 16 || band == 32;
+    uint32_t base = 0;
+    if (max_p && nvb16_ok(s, txt.bits, max_p, band, &base)) {
+        NvBand16SinkArgs D;
+        nv_fill(D.a, pat, txt, s, n);
+        D.a.score = scores; D.a.n_lanes = (n + 1) / 2; D.a.band = band; D.a.base = base; D.sinks = sinks;
+        using Fn = void (*)(NvBand16SinkArgs);
+        const Fn fn = nv_static(al.aligner, al.type, ex, [band](auto a, auto t, auto e) -> Fn {
+            return GX_BAND_PICK(nv_banded16_sink_kernel, a, t, e); });
+        return launch_checked(fn, (D.a.n_lanes + 255) / 256, st, D);
+    }
+    NvBandSinkArgs A;
+    nv_fill(A.a, pat, txt, s, n);
+    A.a.score = scores; A.a.band = band; A.sinks = sinks;
+    using Fn = void (*)(NvBandSinkArgs);
+    const Fn fn = nv_static(al.aligner, al.type, ex, [band](auto a, auto t, auto e) -> Fn {
+        return GX_BAND_PICK(nv_banded_sink_kernel, a, t, e); });
     return launch_checked(fn, (n + 255) / 256, st, A);
 }
 

@@ -208,6 +208,14 @@ std::string nv_sinks_plan_name(const gasalx_nv_aligner &al, uint32_t max_p, uint
 // max_p: the longest pattern (0: unknown; the packed kernel needs it for its value window)
 int nv_banded_score_device(const gasalx_nv_aligner &al, uint32_t band, uint32_t n, const gasalx_nv_strings &pat,
                            const gasalx_nv_strings &txt, int32_t *scores, hipStream_t st, uint32_t max_p);
+// the same with the BestSink position (nvbanded_sink.hpp; sinks as nv_score_sinks_device); scores or
+// sinks may be NULL
+int nv_banded_score_sinks_device(const gasalx_nv_aligner &al, uint32_t band, uint32_t n, const gasalx_nv_strings &pat,
+                                 const gasalx_nv_strings &txt, int32_t *scores, uint32_t *sinks, hipStream_t st,
+                                 uint32_t max_p);
+// its kernel's name ("nvbio_banded16_gotoh_local_b16_sink"), or the code the call would return
+int nv_banded_sinks_plan_name(const gasalx_nv_aligner &al, uint32_t band, uint32_t max_p, uint32_t text_bits,
+                              std::string &name);
 // EditDistanceAligner<TYPE, MyersTag<alphabet>> under the same banded scorer (nvmyers.hpp): BestSink
 // score and position per pair (sinks as nv_score_sinks_device); scores or sinks may be NULL
 int nv_banded_myers_device(int32_t type, uint32_t alphabet, uint32_t band, uint32_t n, const gasalx_nv_strings &pat,

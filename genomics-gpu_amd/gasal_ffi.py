@@ -37,6 +37,8 @@ EXPORTS = (
     "gasalx_nv_score_device", "gasalx_nv_score_host", "gasalx_nv_describe_plan",
     "gasalx_nv_score_sinks_device", "gasalx_nv_score_sinks_host", "gasalx_nv_describe_sinks_plan",
     "gasalx_nv_banded_score_device", "gasalx_nv_banded_score_host",
+    "gasalx_nv_banded_score_sinks_device", "gasalx_nv_banded_score_sinks_host",
+    "gasalx_nv_describe_banded_sinks_plan",
     "gasalx_nv_banded_myers_device", "gasalx_nv_banded_myers_host", "gasalx_nv_describe_myers_plan",
     "gasalx_nv_traceback_device", "gasalx_nv_traceback_host",
     "gasalx_nv_banded_traceback_device", "gasalx_nv_banded_traceback_host",
@@ -507,6 +509,38 @@ class Engine:
                                                  ctypes.c_uint64(len(texts.words)), _p(sc)), "nv_banded_score_host")
         return sc
 
+    def nv_banded_score_sinks_host(self, aligner: "NvAligner", band: int, patterns: "PackedSet", texts: "PackedSet",
+                                   scores=True, sinks=True):
+        """The banded scorer with the BestSink position (gasalx_nv_banded_score_sinks_host): (scores
+        int32[n], sinks uint32[n, 2]) as nv_banded_myers_host returns them, the score and sink of
+        nv_banded_traceback_host; INT32_MIN and the empty sink where nothing is reported."""
+        n = patterns.n
+        sc = np.zeros(n, np.int32) if scores else None
+        sk = np.zeros(2 * n, np.uint32) if sinks else None
+        ca = aligner.cstruct()
+        _check(lib().gasalx_nv_banded_score_sinks_host(self._h, ctypes.byref(ca), ctypes.c_uint32(band),
+                                                       ctypes.c_uint32(n), ctypes.byref(patterns.cstruct()),
+                                                       ctypes.c_uint64(len(patterns.words)),
+                                                       ctypes.byref(texts.cstruct()), ctypes.c_uint64(len(texts.words)),
+                                                       _p(sc), _p(sk)), "nv_banded_score_sinks_host")
+        return sc, (sk.reshape(n, 2) if sinks else None)
+
+    def nv_banded_score_sinks_device_ptrs(self, aligner: "NvAligner", band: int, n: int, pat: dict, txt: dict,
+                                          scores_ptr: int = 0, sinks_ptr: int = 0, max_pattern_len: int = 0,
+                                          stream: int = 0):
+        """Device-resident form (gasalx_nv_banded_score_sinks_device); pat/txt as nv_score_device_ptrs,
+        scores_ptr n int32, sinks_ptr 2n uint32 (either may be 0)."""
+        mk = lambda d: CNvStrings(d["words"], d.get("offsets") or None, d.get("length", 0), d["bits"],
+                                  int(d.get("big_endian", False)))
+        ca = aligner.cstruct()
+        _check(lib().gasalx_nv_banded_score_sinks_device(self._h, ctypes.byref(ca), ctypes.c_uint32(band),
+                                                         ctypes.c_uint32(n), ctypes.byref(mk(pat)),
+                                                         ctypes.byref(mk(txt)), ctypes.c_void_p(scores_ptr or None),
+                                                         ctypes.c_void_p(sinks_ptr or None),
+                                                         ctypes.c_uint32(max_pattern_len),
+                                                         ctypes.c_void_p(stream or None)),
+               "nv_banded_score_sinks_device")
+
     def nv_banded_myers_host(self, type_: int, alphabet: int, band: int, patterns: "PackedSet", texts: "PackedSet",
                              scores=True, sinks=True):
         """nvbio's banded Myers aligner, EditDistanceAligner<type, MyersTag<alphabet>> under
@@ -833,6 +867,17 @@ def nv_describe_sinks_plan(aligner: "NvAligner", max_p: int, max_t: int, per_pai
     al = aligner.cstruct()
     _check(lib().gasalx_nv_describe_sinks_plan(ctypes.byref(al), max_p, max_t, int(per_pair_texts), text_bits, buf,
                                                128), "nv_describe_sinks_plan")
+    return buf.value.decode()
+
+
+def nv_describe_banded_sinks_plan(aligner: "NvAligner", band: int, max_p: int, text_bits: int = 2) -> str:
+    """The kernel Engine.nv_banded_score_sinks_* runs (gasalx_nv_describe_banded_sinks_plan); raises what
+    the call would."""
+    buf = ctypes.create_string_buffer(128)
+    al = aligner.cstruct()
+    _check(lib().gasalx_nv_describe_banded_sinks_plan(ctypes.byref(al), ctypes.c_uint32(band), ctypes.c_uint32(max_p),
+                                                      ctypes.c_uint32(text_bits), buf, 128),
+           "nv_describe_banded_sinks_plan")
     return buf.value.decode()
 
 

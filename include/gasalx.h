@@ -390,6 +390,35 @@ int gasalx_nv_banded_score_host(gasalx_engine *eng, const gasalx_nv_aligner *ali
                                 uint32_t n_pairs, const gasalx_nv_strings *patterns, uint64_t pattern_words,
                                 const gasalx_nv_strings *texts, uint64_t text_words, int32_t *scores);
 
+/* The banded scorer with the sink nvbio's call leaves beside the score
+ * (banded_alignment_score<BAND_LEN>(aligner, pattern, quals, text, min_score, sink), what nvBowtie
+ * places its banded traceback by): the BestSink score and position of every pair, the score and
+ * sink gasalx_nv_banded_traceback_* computes, without the flags and the walk.  ED, SW and Gotoh
+ * aligners.  sinks: two uint32 per pair in gasalx_nv_score_sinks_*'s layout, sinks[2k] = x (text),
+ * sinks[2k + 1] = y (pattern), one-based; on ties the last maximum in report order
+ * (sw_banded_inl.h:436,465,494-510, gotoh_banded_inl.h:642-659): LOCAL every cell (i + j + 1,
+ * i + 1), rows top to bottom and band slots left to right, slots past the text's end included
+ * (x may exceed the text length); SEMI_GLOBAL (M + j, M) for j < min(M + band - 1, N) - (M - 1);
+ * GLOBAL (M + band - 1, M).  A text shorter than its pattern, and a LOCAL pair with an empty
+ * pattern, report nothing: INT32_MIN and (0xFFFFFFFF, 0xFFFFFFFF).  scores or sinks may be NULL,
+ * not both (GASALX_EINVAL).  Scores equal gasalx_nv_banded_score_*'s; the packed and the int32
+ * kernel are chosen by the same rule and give the same outputs. */
+int gasalx_nv_banded_score_sinks_device(gasalx_engine *eng, const gasalx_nv_aligner *aligner, uint32_t band_len,
+                                        uint32_t n_pairs, const gasalx_nv_strings *dev_patterns,
+                                        const gasalx_nv_strings *dev_texts, int32_t *dev_scores,
+                                        uint32_t *dev_sinks, uint32_t max_pattern_len,
+                                        void *stream);   /* max_pattern_len: 0 = read back */
+int gasalx_nv_banded_score_sinks_host(gasalx_engine *eng, const gasalx_nv_aligner *aligner, uint32_t band_len,
+                                      uint32_t n_pairs, const gasalx_nv_strings *patterns, uint64_t pattern_words,
+                                      const gasalx_nv_strings *texts, uint64_t text_words, int32_t *scores,
+                                      uint32_t *sinks);
+/* The kernel such a call runs: "nvbio_banded16_<aligner>_<type>_b<8|16|32>_sink" (two pairs per
+ * lane) or "nvbio_banded_..._sink" (int32), e.g. "nvbio_banded16_gotoh_local_b16_sink"; or the
+ * code the call would return (band_len outside 2..32: GASALX_EINVAL).  max_pattern_len: the
+ * longest pattern of the batch (0, a batch of empty patterns, takes the int32 kernel). */
+int gasalx_nv_describe_banded_sinks_plan(const gasalx_nv_aligner *aligner, uint32_t band_len,
+                                         uint32_t max_pattern_len, uint32_t text_bits, char *buf, uint32_t buf_len);
+
 /* The same banded scorer with nvbio's Myers bit-vector aligner, EditDistanceAligner<TYPE,
  * MyersTag<alphabet_size>> (qmap's and fmmap's configuration; NvB/nvbio/alignment/myers/
  * myers_banded_inl.h:226-288, banded_myers<band_len, 0, TYPE, alphabet_size>).  Not the banded

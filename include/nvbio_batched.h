@@ -22,7 +22,10 @@
  * the flags of every cell, in chunks of at most 4 GiB); enact() does not use the caller's
  * temp buffer.  The TextBlockingTag /
  * PatternBlockingTag score semantics are provided (both give the same scores), full and
- * banded.  The full-DP scorer also reports where the best score ends: AlignmentStream::set_sinks
+ * banded.  The banded scorer (BatchedBandedAlignmentScore, batch_banded_alignment_score) reports
+ * the BestSink position beside the score for the ED, SW and Gotoh aligners when the stream carries a
+ * sinks array (nvbanded_sink.hpp: the banded score pass has one report order, so either blocking
+ * tag is taken), what nvBowtie places its banded traceback by.  The full-DP scorer also reports where the best score ends: AlignmentStream::set_sinks
  * asks for nvbio's BestSink position (x = text, y = pattern) of every pair, exact to the
  * TextBlockingTag report order on ties (nvbio_sink.hpp); PatternBlockingTag aligners, whose
  * tied sinks differ, are refused at compile time.  Traceback: BatchedAlignmentTraceback<CHECKPOINTS, stream_type> (full DP) and
@@ -299,12 +302,19 @@ struct BatchedBandedAlignmentScore {
             }
             return;
         }
-        if (stream.m_scores32 == NULL) {
-            fprintf(stderr, "BatchedBandedAlignmentScore::enact: banded scores are int32, set m_scores32\n");
-            exit(EXIT_FAILURE);
+        int rc;
+        if (stream.m_sinks) {
+            // ED, SW and Gotoh with the BestSink positions (scores optional)
+            rc = gasalx_nv_banded_score_sinks_device(engine(), &a, BAND_LEN, stream.size(), &p, &t, stream.m_scores32,
+                                                     stream.m_sinks, stream.max_pattern_length(), hip_stream);
+        } else {
+            if (stream.m_scores32 == NULL) {
+                fprintf(stderr, "BatchedBandedAlignmentScore::enact: banded scores are int32, set m_scores32\n");
+                exit(EXIT_FAILURE);
+            }
+            rc = gasalx_nv_banded_score_device(engine(), &a, BAND_LEN, stream.size(), &p, &t, stream.m_scores32,
+                                               stream.max_pattern_length(), hip_stream);
         }
-        const int rc = gasalx_nv_banded_score_device(engine(), &a, BAND_LEN, stream.size(), &p, &t,
-                                                     stream.m_scores32, stream.max_pattern_length(), hip_stream);
         if (rc != GASALX_OK) {
             fprintf(stderr, "BatchedBandedAlignmentScore::enact: %s\n", gasalx_last_error());
             exit(EXIT_FAILURE);
@@ -333,8 +343,9 @@ struct BestSinks {
 
 // batch_banded_alignment_score<BAND_LEN>(aligner, patterns, texts, sinks, scheduler, max_pattern_length,
 // max_text_length) (batched.h:216-231), the form qmap and fmmap call: patterns[k] against texts[k]
-// on the engine's stream (asynchronous, as nvbio's).  A MyersTag aligner takes scores and sinks;
-// the DP aligners' banded scorer has scores only, and a sinks array given to it is an error.
+// on the engine's stream (asynchronous, as nvbio's).  Every aligner takes scores and sinks: a
+// MyersTag aligner through gasalx_nv_banded_myers_*, the ED, SW and Gotoh aligners through
+// gasalx_nv_banded_score_sinks_* (gasalx_nv_banded_score_* when no sinks array is given).
 template <uint32 BAND_LEN, typename aligner_type, typename scheduler_type>
 void batch_banded_alignment_score(const aligner_type aligner, const PackedStringSet patterns,
                                   const PackedStringSet texts, BestSinks sinks, const scheduler_type,
@@ -346,10 +357,6 @@ void batch_banded_alignment_score(const aligner_type aligner, const PackedString
     stream.m_pattern_bits = patterns.m_bits; stream.m_pattern_big_endian = patterns.m_big_endian;
     stream.m_text_bits = texts.m_bits; stream.m_text_big_endian = texts.m_big_endian;
     stream.m_scores32 = sinks.scores;
-    if (sinks.sinks && !is_myers_tag<typename aligner_type::algorithm_tag>::value) {
-        fprintf(stderr, "batch_banded_alignment_score: the banded DP scorer reports scores only\n");
-        exit(EXIT_FAILURE);
-    }
     stream.m_sinks = sinks.sinks;
     BatchedBandedAlignmentScore<BAND_LEN, AlignmentStream<aligner_type>, scheduler_type> batch;
     batch.enact(stream);
