@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <array>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <type_traits>
 #include <utility>
@@ -19,6 +20,7 @@
 #include "nvbanded.hpp"
 #include "nvbanded_sink.hpp"
 #include "nvmyers.hpp"
+#include "nvmatrix.hpp"
 
 namespace gx {
 
@@ -320,6 +322,93 @@ int nv_score_sinks_device(const gasalx_nv_aligner &al, uint32_t n, const gasalx_
                               Nv16SinkArgs{nv16_args(al, n, pat, txt, P, scores, nullptr), sinks});
     return launch_checked(nv_sink_lookup(al.aligner, al.type, P.shape), blocks, P.lds, st,
                           NvSinkArgs{nv_args(al, n, pat, txt, P, scores, nullptr), sinks});
+}
+
+// ---- GotohAligner over a substitution matrix (nvmatrix.hpp): int32, full DP, the score-only or the
+//      sink-tracking form at the smallest lane-group shape that covers the patterns.  The LDS budget
+//      is this family's own: the table image, then one byte per column of every text slot. ----
+namespace {
+
+struct NvMatrixPlan {
+    bool ok = false;
+    int shape = 0;
+    size_t lds = 0;
+    uint32_t per_block = 0, lds_stride = 0;
+};
+NvMatrixPlan nv_matrix_make_plan(uint32_t max_p, uint32_t max_t, bool per_pair_text) {
+    NvMatrixPlan P;
+    P.lds_stride = (std::max<uint32_t>(max_t, 1) + 7u) & ~7u;
+    for (; P.shape < (int)kNvShapeCount; P.shape++) {
+        const NvShape &sh = kNvShapes[P.shape];
+        P.per_block = 4 * (64 / sh.G);
+        P.lds = kNvMatrixBytes + (size_t)P.lds_stride * (per_pair_text ? P.per_block : 1);
+        if ((uint32_t)(sh.G * sh.R) >= max_p && P.lds <= kNvLdsMax) { P.ok = true; break; }
+    }
+    return P;
+}
+
+// the checks that need no strings: the aligner, then the table's size
+int nv_matrix_check(const gasalx_nv_aligner &al, uint32_t matrix_n) {
+    if (al.aligner < 0 || al.aligner > 2 || al.type < 0 || al.type > 2) return nv_fail(GASALX_EINVAL, "bad aligner");
+    if (al.aligner != NV_GOTOH)
+        return nv_fail(GASALX_EUNSUPPORTED, "only the Gotoh aligner takes a substitution matrix");
+    if (matrix_n < 2 || matrix_n > kNvMatrixDim) return nv_fail(GASALX_EINVAL, "matrix size must be 2..32");
+    return GASALX_OK;
+}
+
+using NvMatrixFn = void (*)(NvMatrixArgs);
+NvMatrixFn nv_matrix_lookup(int type, bool sink, int shape) {
+    return nv_instance(NV_GOTOH, type, sink, shape, [](auto, auto t, auto s, auto g, auto r) -> NvMatrixFn {
+        return &nv_matrix_kernel<t, g, r, s>; });
+}
+
+}  // namespace
+
+int nv_matrix_plan_name(const gasalx_nv_aligner &al, uint32_t matrix_n, uint32_t max_p, uint32_t max_t,
+                        bool per_pair_text, bool sinks, std::string &name) {
+    static const char *tn[] = {"global", "local", "semi"};
+    if (int rc = nv_matrix_check(al, matrix_n)) return rc;
+    const NvMatrixPlan P = nv_matrix_make_plan(max_p, max_t, per_pair_text);
+    name = !P.ok ? "none"
+                 : std::string("nvbio_matrix_gotoh_") + tn[al.type] + (per_pair_text ? "" : "_shared") + "_G" +
+                       std::to_string(kNvShapes[P.shape].G) + "R" + std::to_string(kNvShapes[P.shape].R) +
+                       (sinks ? "_sink" : "");
+    return GASALX_OK;
+}
+
+int nv_matrix_score_device(const gasalx_nv_aligner &al, const gasalx_nv_matrix &mat, uint32_t n,
+                           const gasalx_nv_strings &pat, const gasalx_nv_strings &txt, int32_t *scores, uint32_t *sinks,
+                           uint32_t max_p, uint32_t max_t, hipStream_t st) {
+    if (int rc = nv_matrix_check(al, mat.n)) return rc;
+    if (!mat.scores) return nv_fail(GASALX_EINVAL, "null argument");
+    if (int rc = nv_check(al, "bad aligner", "bad aligner", nullptr, pat, txt)) return rc;
+    if (n == 0) return GASALX_OK;
+    if (int rc = nv_check_ptrs(pat, txt, scores || sinks)) return rc;
+    if (!txt.offsets) max_t = txt.length;
+    // the table's image, by value in the arguments: read now, no device copy to reuse across streams
+    NvMatrixArgs A;
+    int8_t image[kNvMatrixBytes] = {};
+    int32_t entry_mag = 0;
+    for (uint32_t p = 0; p < mat.n; p++)
+        for (uint32_t t = 0; t < mat.n; t++) {
+            const int8_t v = mat.scores[t + p * mat.n];
+            image[p * kNvMatrixDim + t] = v;
+            entry_mag = std::max(entry_mag, std::abs((int32_t)v));
+        }
+    std::memcpy(A.tab, image, sizeof(image));
+    // nv_score_plan's range check, the largest |entry| standing for match and mismatch
+    const NvScheme s = {entry_mag, entry_mag, al.gap_open, al.gap_ext, al.deletion, al.insertion};
+    if ((int64_t)(max_p + max_t + 2) * nv_score_mag(s) * 2 >= (1ll << 28))
+        return nv_fail(GASALX_ERANGE, "scores out of the exact range");
+    const NvMatrixPlan P = nv_matrix_make_plan(max_p, max_t, txt.offsets != nullptr);
+    if (!P.ok)
+        return nv_fail(GASALX_ERANGE, "pattern longer than 1024 or text too long for LDS (" + std::to_string(max_p) +
+                                          ", " + std::to_string(max_t) + ")");
+    nv_fill_strings(A, pat, txt, n);
+    A.score = scores; A.sinks = sinks; A.go = al.gap_open; A.ge = al.gap_ext;
+    A.lds_stride = P.lds_stride; A.nsym = mat.n;
+    return launch_checked(nv_matrix_lookup(al.type, sinks != nullptr, P.shape), (n + P.per_block - 1) / P.per_block,
+                          P.lds, st, A);
 }
 
 // ---- BatchedBandedAlignmentScore<band> (nvbanded.hpp): thread per pair, band in registers,

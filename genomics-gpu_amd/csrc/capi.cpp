@@ -1109,6 +1109,49 @@ int gasalx_nv_score_sinks_host(gasalx_engine *eng, const gasalx_nv_aligner *al, 
     return host_finish(st, rc, {{scores, ds, (size_t)n * 4}, {sinks, dk, (size_t)n * 8}});
 }
 
+int gasalx_nv_matrix_score_device(gasalx_engine *eng, const gasalx_nv_aligner *al, const gasalx_nv_matrix *mat,
+                                  uint32_t n, const gasalx_nv_strings *pat, const gasalx_nv_strings *txt,
+                                  int32_t *scores, uint32_t *sinks, uint32_t max_p, uint32_t max_t, void *stream) {
+    if (!eng || !al || !mat || !pat || !txt) { gx::set_error("null argument"); return GASALX_EINVAL; }
+    hipStream_t st;
+    int rc = enter(eng, stream, &st);
+    if (rc) return rc;
+    if ((rc = device_max_spans(pat, txt, n, st, &max_p, &max_t))) return rc;
+    return gx::nv_matrix_score_device(*al, *mat, n, *pat, *txt, scores, sinks, max_p, max_t, st);
+}
+
+int gasalx_nv_describe_matrix_plan(const gasalx_nv_aligner *al, uint32_t matrix_n, uint32_t max_p, uint32_t max_t,
+                                   int per_pair, int want_sinks, char *buf, uint32_t buf_len) {
+    if (!al || !buf || buf_len == 0) { gx::set_error("null argument"); return GASALX_EINVAL; }
+    std::string name;
+    if (int rc = gx::nv_matrix_plan_name(*al, matrix_n, max_p, max_t, per_pair != 0, want_sinks != 0, name)) return rc;
+    std::snprintf(buf, buf_len, "%s", name.c_str());
+    return GASALX_OK;
+}
+
+int gasalx_nv_matrix_score_host(gasalx_engine *eng, const gasalx_nv_aligner *al, const gasalx_nv_matrix *mat,
+                                uint32_t n, const gasalx_nv_strings *pat, uint64_t pat_words,
+                                const gasalx_nv_strings *txt, uint64_t txt_words, int32_t *scores, uint32_t *sinks) {
+    if (!eng || !al || !mat || !pat || !txt || !pat->words || !pat->offsets || !txt->words || (!scores && !sinks)) {
+        gx::set_error("null argument");
+        return GASALX_EINVAL;
+    }
+    if (n == 0) return GASALX_OK;
+    hipStream_t st;
+    int rc = enter(eng, nullptr, &st);
+    if (rc) return rc;
+    const uint32_t max_p = max_span(pat->offsets, n);
+    const uint32_t max_t = txt->offsets ? max_span(txt->offsets, n) : txt->length;
+    gasalx_nv_strings dp, dt;
+    if ((rc = nv_stage_strings(eng, n, pat, pat_words, txt, txt_words, st, dp, dt))) return rc;
+    int32_t *ds = nullptr;
+    uint32_t *dk = nullptr;
+    if (scores) { CK(eng->buf[B_NV_S].reserve((size_t)n * 4)); ds = eng->buf[B_NV_S].as<int32_t>(); }
+    if (sinks) { CK(eng->buf[B_NV_SNK].reserve((size_t)n * 8)); dk = eng->buf[B_NV_SNK].as<uint32_t>(); }
+    rc = gx::nv_matrix_score_device(*al, *mat, n, dp, dt, ds, dk, max_p, max_t, st);
+    return host_finish(st, rc, {{scores, ds, (size_t)n * 4}, {sinks, dk, (size_t)n * 8}});
+}
+
 int gasalx_nv_banded_score_device(gasalx_engine *eng, const gasalx_nv_aligner *al, uint32_t band, uint32_t n,
                                   const gasalx_nv_strings *pat, const gasalx_nv_strings *txt, int32_t *scores,
                                   uint32_t max_p, void *stream) {

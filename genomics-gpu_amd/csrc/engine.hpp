@@ -204,6 +204,15 @@ int nv_score_sinks_device(const gasalx_nv_aligner &al, uint32_t n, const gasalx_
                           uint32_t max_t, hipStream_t stream);
 std::string nv_sinks_plan_name(const gasalx_nv_aligner &al, uint32_t max_p, uint32_t max_t, bool per_pair_text,
                                uint32_t text_bits);
+// GotohAligner over a substitution matrix (nvmatrix.hpp): S = mat.scores[t + p * n] from a host table
+// read during the call, symbols >= n clamped to n - 1; al.match / al.mismatch are not read.  sinks as
+// nv_score_sinks_device (NULL: the score-only kernel); scores or sinks may be NULL
+int nv_matrix_score_device(const gasalx_nv_aligner &al, const gasalx_nv_matrix &mat, uint32_t n,
+                           const gasalx_nv_strings &pat, const gasalx_nv_strings &txt, int32_t *scores, uint32_t *sinks,
+                           uint32_t max_p, uint32_t max_t, hipStream_t stream);
+// its kernel's name ("nvbio_matrix_gotoh_local_G8R16_sink", or "none"), or the code the call would return
+int nv_matrix_plan_name(const gasalx_nv_aligner &al, uint32_t matrix_n, uint32_t max_p, uint32_t max_t,
+                        bool per_pair_text, bool sinks, std::string &name);
 // nvbio BatchedBandedAlignmentScore<band> (batched.hip / nvbanded.hpp): BestSink score per pair
 // max_p: the longest pattern (0: unknown; the packed kernel needs it for its value window)
 int nv_banded_score_device(const gasalx_nv_aligner &al, uint32_t band, uint32_t n, const gasalx_nv_strings &pat,

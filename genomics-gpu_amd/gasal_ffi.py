@@ -36,6 +36,7 @@ EXPORTS = (
     "gasalx_pairhmm_quals_device", "gasalx_pairhmm_quals_host", "gasalx_hmm_file_read", "gasalx_hmm_file_free",
     "gasalx_nv_score_device", "gasalx_nv_score_host", "gasalx_nv_describe_plan",
     "gasalx_nv_score_sinks_device", "gasalx_nv_score_sinks_host", "gasalx_nv_describe_sinks_plan",
+    "gasalx_nv_matrix_score_device", "gasalx_nv_matrix_score_host", "gasalx_nv_describe_matrix_plan",
     "gasalx_nv_banded_score_device", "gasalx_nv_banded_score_host",
     "gasalx_nv_banded_score_sinks_device", "gasalx_nv_banded_score_sinks_host",
     "gasalx_nv_describe_banded_sinks_plan",
@@ -109,6 +110,10 @@ class CNvAligner(ctypes.Structure):
 class CNvStrings(ctypes.Structure):
     _fields_ = [("words", ctypes.c_void_p), ("offsets", ctypes.c_void_p), ("length", ctypes.c_uint32),
                 ("bits", ctypes.c_uint32), ("big_endian", ctypes.c_uint32)]
+
+
+class CNvMatrix(ctypes.Structure):
+    _fields_ = [("scores", ctypes.c_void_p), ("n", ctypes.c_uint32)]
 
 
 _lib = None
@@ -497,6 +502,39 @@ class Engine:
                                                   ctypes.c_uint32(max_pattern_len), ctypes.c_uint32(max_text_len),
                                                   ctypes.c_void_p(stream or None)), "nv_score_sinks_device")
 
+    def nv_matrix_score_host(self, aligner: "NvAligner", matrix: "NvMatrix", patterns: "PackedSet",
+                             texts: "PackedSet", scores=True, sinks=True):
+        """Gotoh scores with a substitution matrix (gasalx_nv_matrix_score_host): S(p, t) =
+        matrix.scores[p, t], symbols >= n read as n - 1; aligner.match / mismatch are ignored.
+        Returns (scores int32[n], sinks uint32[n, 2]) as nv_score_sinks_host; scores=False /
+        sinks=False pass NULL for that output and return None in its place (sinks=False runs the
+        score-only kernel)."""
+        n = patterns.n
+        sc = np.zeros(n, np.int32) if scores else None
+        sk = np.zeros(2 * n, np.uint32) if sinks else None
+        ca, cm = aligner.cstruct(), matrix.cstruct()
+        _check(lib().gasalx_nv_matrix_score_host(self._h, ctypes.byref(ca), ctypes.byref(cm), ctypes.c_uint32(n),
+                                                 ctypes.byref(patterns.cstruct()), ctypes.c_uint64(len(patterns.words)),
+                                                 ctypes.byref(texts.cstruct()), ctypes.c_uint64(len(texts.words)),
+                                                 _p(sc), _p(sk)), "nv_matrix_score_host")
+        return sc, (sk.reshape(n, 2) if sinks else None)
+
+    def nv_matrix_score_device_ptrs(self, aligner: "NvAligner", matrix: "NvMatrix", n: int, pat: dict, txt: dict,
+                                    scores_ptr: int = 0, sinks_ptr: int = 0, max_pattern_len: int = 0,
+                                    max_text_len: int = 0, stream: int = 0):
+        """Device-resident strings and outputs (gasalx_nv_matrix_score_device); the table stays a
+        host array.  pat/txt as nv_score_device_ptrs, scores_ptr n int32, sinks_ptr 2n uint32
+        (either may be 0)."""
+        mk = lambda d: CNvStrings(d["words"], d.get("offsets") or None, d.get("length", 0), d["bits"],
+                                  int(d.get("big_endian", False)))
+        ca, cm = aligner.cstruct(), matrix.cstruct()
+        _check(lib().gasalx_nv_matrix_score_device(self._h, ctypes.byref(ca), ctypes.byref(cm), ctypes.c_uint32(n),
+                                                   ctypes.byref(mk(pat)), ctypes.byref(mk(txt)),
+                                                   ctypes.c_void_p(scores_ptr or None),
+                                                   ctypes.c_void_p(sinks_ptr or None),
+                                                   ctypes.c_uint32(max_pattern_len), ctypes.c_uint32(max_text_len),
+                                                   ctypes.c_void_p(stream or None)), "nv_matrix_score_device")
+
     def nv_banded_score_host(self, aligner: "NvAligner", band: int, patterns: "PackedSet", texts: "PackedSet"):
         """nvbio BatchedBandedAlignmentScore<band> (gasalx_nv_banded_score_host): BestSink
         score per pair, INT32_MIN where a text is shorter than its pattern."""
@@ -870,6 +908,18 @@ def nv_describe_sinks_plan(aligner: "NvAligner", max_p: int, max_t: int, per_pai
     return buf.value.decode()
 
 
+def nv_describe_matrix_plan(aligner: "NvAligner", matrix_n: int, max_p: int, max_t: int, per_pair_texts: bool = False,
+                            sinks: bool = False) -> str:
+    """The kernel Engine.nv_matrix_score_* runs for these bounds (gasalx_nv_describe_matrix_plan), "none"
+    when they do not plan; raises what the call would for the aligner and the matrix size."""
+    buf = ctypes.create_string_buffer(128)
+    al = aligner.cstruct()
+    _check(lib().gasalx_nv_describe_matrix_plan(ctypes.byref(al), ctypes.c_uint32(matrix_n), ctypes.c_uint32(max_p),
+                                                ctypes.c_uint32(max_t), int(per_pair_texts), int(sinks), buf, 128),
+           "nv_describe_matrix_plan")
+    return buf.value.decode()
+
+
 def nv_describe_banded_sinks_plan(aligner: "NvAligner", band: int, max_p: int, text_bits: int = 2) -> str:
     """The kernel Engine.nv_banded_score_sinks_* runs (gasalx_nv_describe_banded_sinks_plan); raises what
     the call would."""
@@ -974,6 +1024,22 @@ class NvAligner:
     def prm(self):
         return np.array([self.match, self.mismatch, self.gap_open, self.gap_ext, self.deletion, self.insertion],
                         np.int32)
+
+
+class NvMatrix:
+    """A substitution matrix for the Gotoh aligner (gasalx_nv_matrix): scores[p, t] is the score of
+    pattern symbol p against text symbol t, n x n signed bytes (the C layout scores[t + p * n])."""
+
+    def __init__(self, scores, n=None):
+        a = np.asarray(scores)
+        n = int(n if n is not None else a.shape[0])
+        if a.size != n * n or (a.size and (a.min() < -128 or a.max() > 127)):
+            raise ValueError("NvMatrix: n * n entries in -128..127")
+        self.scores = np.ascontiguousarray(a.reshape(n, n), np.int8)
+        self.n = n
+
+    def cstruct(self):
+        return CNvMatrix(_p(self.scores), self.n)
 
 
 @dataclass

@@ -376,6 +376,45 @@ int gasalx_nv_score_sinks_host(gasalx_engine *eng, const gasalx_nv_aligner *alig
 int gasalx_nv_describe_sinks_plan(const gasalx_nv_aligner *aligner, uint32_t max_pattern_len, uint32_t max_text_len,
                                   int per_pair_texts, uint32_t text_bits, char *buf, uint32_t buf_len);
 
+/* Gotoh scoring with a substitution matrix: what nvbio's GotohAligner computes when its scheme
+ * answers substitution(r_i, q_j, r, q, qq) from a table (gotoh/gotoh_inl.h:534, :1042; the
+ * proteinsw example's BlosumScheme, examples/proteinsw/proteinsw.cu:76-100): in the Gotoh cell
+ * update S(p, t) = scores[t + p * n].  Proteins, codons, IUPAC codes: the caller supplies the
+ * table, none is shipped. */
+typedef struct gasalx_nv_matrix {
+    const int8_t *scores;   /* HOST pointer: n*n entries, scores[t + p*n] (t = text symbol, p = pattern symbol) */
+    uint32_t n;             /* 2..32 */
+} gasalx_nv_matrix;
+
+/* aligner: GASALX_NV_GOTOH (Smith-Waterman and edit distance never read a substitution score
+ * from the scheme, sw_inl.h: GASALX_EUNSUPPORTED); match and mismatch are ignored, gap_open and
+ * gap_ext used as given.  The table is read during the call (it travels to the kernel by value):
+ * the caller may free or change it on return, and calls on different streams share nothing.
+ * A symbol >= n is read as n - 1 (the reference indexes past its table there).  dev_scores
+ * (int32) and dev_sinks (2 x n_pairs) have the layout and semantics of gasalx_nv_score_sinks_*:
+ * one-based (x, y), the last maximum in the TextBlockingTag report order, INT32_MIN and
+ * (0xFFFFFFFF, 0xFFFFFFFF) for a pair that reports no cell; either may be NULL, not both
+ * (GASALX_EINVAL); without sinks the score-only kernel runs.  int32, the full DP only.
+ * GASALX_EINVAL: n outside 2..32, a NULL table, symbol bits other than 2 / 4 / 8.  GASALX_ERANGE:
+ * gasalx_nv_score_*'s range check with the largest |entry| in place of match and mismatch; a
+ * pattern above 1024 symbols or texts that do not fit the LDS (one byte per symbol). */
+int gasalx_nv_matrix_score_device(gasalx_engine *eng, const gasalx_nv_aligner *aligner,
+                                  const gasalx_nv_matrix *matrix, uint32_t n_pairs,
+                                  const gasalx_nv_strings *dev_patterns, const gasalx_nv_strings *dev_texts,
+                                  int32_t *dev_scores, uint32_t *dev_sinks, uint32_t max_pattern_len,
+                                  uint32_t max_text_len, void *stream);
+int gasalx_nv_matrix_score_host(gasalx_engine *eng, const gasalx_nv_aligner *aligner,
+                                const gasalx_nv_matrix *matrix, uint32_t n_pairs,
+                                const gasalx_nv_strings *patterns, uint64_t pattern_words,
+                                const gasalx_nv_strings *texts, uint64_t text_words, int32_t *scores,
+                                uint32_t *sinks);
+/* The kernel such a call runs: "nvbio_matrix_gotoh_<global|local|semi>[_shared]_G<g>R<r>[_sink]"
+ * (e.g. proteinsw's 128 x 1024 per-pair batch: "nvbio_matrix_gotoh_local_G8R16"), "none" when the
+ * bounds do not plan, or the code the call would return for the aligner and matrix_n. */
+int gasalx_nv_describe_matrix_plan(const gasalx_nv_aligner *aligner, uint32_t matrix_n, uint32_t max_pattern_len,
+                                   uint32_t max_text_len, int per_pair_texts, int want_sinks, char *buf,
+                                   uint32_t buf_len);
+
 /* nvbio's BatchedBandedAlignmentScore<band_len> (NvB/nvbio/alignment/batched.h:337,
  * batched_banded_inl.h:44-75): the banded DP of sw_banded_inl.h / gotoh_banded_inl.h /
  * ed_banded_inl.h over cells (i, i + j), 0 <= j < band_len (2..32): two pairs per lane in

@@ -36,6 +36,16 @@
  * myers/myers_banded_inl.h) runs under BatchedBandedAlignmentScore and the free function
  * batch_banded_alignment_score<BAND_LEN>, qmap's and fmmap's call, with scores and BestSink
  * positions (nvmyers.hpp); the full-DP scorer and the tracebacks refuse it at compile time.
+ * Substitution matrices: a GotohAligner over SubstitutionMatrixScheme (a host table of n x n signed
+ * bytes, n <= 32, read as table[r + q*n] with r the text and q the pattern symbol: the proteinsw
+ * example's BlosumScheme, examples/proteinsw/proteinsw.cu:76-100, with the table made a member) is
+ * routed by BatchedAlignmentScore::enact to gasalx_nv_matrix_score_* (nvmatrix.hpp: int32 scores,
+ * BestSink positions for TextBlockingTag aligners; symbols >= n read as n - 1).  No table is
+ * shipped: the caller supplies BLOSUM62 or whatever it scores with.  Smith-Waterman never reads a
+ * substitution score from its scheme, and the banded scorer and the tracebacks have no matrix
+ * kernels: all three refuse the scheme at compile time.  ConcatenatedStringSet /
+ * make_concatenated_string_set (8-bit symbols) and the free function batch_alignment_score
+ * (batched.h:137-150), proteinsw's call, take any aligner the full scorer takes.
  *
  * Header-only C++ over the flat C-ABI (gasalx.h); link with -lgasal.
  */
@@ -47,6 +57,7 @@
 #include <stdlib.h>
 
 #include <type_traits>
+#include <utility>
 
 #include "gasalx.h"
 
@@ -57,6 +68,23 @@ typedef int16_t int16;
 typedef int32_t int32;
 typedef uint32_t uint32;
 typedef uint64_t uint64;
+
+// A set of 8-bit strings stored back to back (strings/string_set.h ConcatenatedStringSet over a
+// uint8 iterator, as proteinsw builds it): string k is symbols[offsets[k] .. offsets[k + 1]).  Both
+// are device pointers; symbols must be 4-byte aligned (the kernels read whole words, symbol s in
+// bits 8 * (s % 4) of word s / 4).
+struct ConcatenatedStringSet {
+    ConcatenatedStringSet(const uint32 count, const uint8 *symbols, const uint32 *offsets)
+        : m_count(count), m_symbols(symbols), m_offsets(offsets) {}
+    uint32 size() const { return m_count; }
+    uint32 m_count;
+    const uint8 *m_symbols;
+    const uint32 *m_offsets;
+};
+inline ConcatenatedStringSet make_concatenated_string_set(const uint32 count, const uint8 *symbols,
+                                                          const uint32 *offsets) {
+    return ConcatenatedStringSet(count, symbols, offsets);
+}
 
 namespace aln {
 
@@ -106,6 +134,44 @@ struct SimpleGotohScheme {   // utils.h:114-135
     int32 m_match = 0, m_mismatch = 0, m_gap_open = 0, m_gap_ext = 0;
 };
 
+// A Gotoh scheme whose substitution score comes from a table: nvbio's scheme concept as
+// GotohAligner reads it (gotoh_inl.h:534, :1042 call substitution(r_i, q_j, r, q, qq)), the
+// proteinsw example's BlosumScheme with the table's size a member.  table: a HOST array of n * n
+// signed bytes, n in 2..32, table[r + q*n] the score of text (reference) symbol r against pattern
+// (query) symbol q; it is read at every enact() and must live until that call returns.
+struct SubstitutionMatrixScheme {
+    SubstitutionMatrixScheme() {}
+    SubstitutionMatrixScheme(const int8_t *table, uint32 n, int32 gap_open, int32 gap_ext)
+        : m_table(table), m_n(n), m_gap_open(gap_open), m_gap_ext(gap_ext) {}
+    // the maximum match bonus: the table's largest entry
+    int32 match(uint8 = 0) const {
+        int32 best = m_table[0];
+        for (uint32 i = 1; i < m_n * m_n; ++i) best = m_table[i] > best ? m_table[i] : best;
+        return best;
+    }
+    int32 substitution(uint32 /*r_i*/, uint32 /*q_j*/, uint8 r, uint8 q, uint8 /*qq*/ = 0) const {
+        return m_table[r + q * m_n];
+    }
+    int32 pattern_gap_open() const { return m_gap_open; }
+    int32 pattern_gap_extension() const { return m_gap_ext; }
+    int32 text_gap_open() const { return m_gap_open; }
+    int32 text_gap_extension() const { return m_gap_ext; }
+    gasalx_nv_matrix c_matrix() const {
+        gasalx_nv_matrix m = {m_table, m_n};
+        return m;
+    }
+    const int8_t *m_table = nullptr;
+    uint32 m_n = 0;
+    int32 m_gap_open = 0, m_gap_ext = 0;
+};
+template <typename T> struct is_matrix_scheme : std::false_type {};
+template <> struct is_matrix_scheme<SubstitutionMatrixScheme> : std::true_type {};
+// an aligner whose scheme is a SubstitutionMatrixScheme (EditDistanceAligner has no scheme)
+template <typename A, typename = void> struct uses_matrix_scheme : std::false_type {};
+template <typename A>
+struct uses_matrix_scheme<A, std::void_t<decltype(std::declval<const A &>().scheme)> >
+    : is_matrix_scheme<typename std::decay<decltype(std::declval<const A &>().scheme)>::type> {};
+
 template <AlignmentType T_TYPE, typename AlgorithmType = PatternBlockingTag>
 struct EditDistanceAligner {
     static const AlignmentType TYPE = T_TYPE;
@@ -118,6 +184,9 @@ struct EditDistanceAligner {
 
 template <AlignmentType T_TYPE, typename scoring_scheme_type, typename AlgorithmType = PatternBlockingTag>
 struct SmithWatermanAligner {
+    static_assert(!is_matrix_scheme<scoring_scheme_type>::value,
+                  "SubstitutionMatrixScheme is a Gotoh scheme: nvbio's Smith-Waterman (sw/sw_inl.h) reads match() and "
+                  "mismatch() only and never calls substitution(); use make_gotoh_aligner");
     static const AlignmentType TYPE = T_TYPE;
     typedef AlgorithmType algorithm_tag;
     SmithWatermanAligner() {}
@@ -137,9 +206,16 @@ struct GotohAligner {
     GotohAligner() {}
     explicit GotohAligner(const scoring_scheme_type s) : scheme(s) {}
     gasalx_nv_aligner c_aligner() const {
-        gasalx_nv_aligner a = {GASALX_NV_GOTOH, (int32)TYPE, scheme.match(), scheme.mismatch(),
-                               scheme.pattern_gap_open(), scheme.pattern_gap_extension(), 0, 0};
-        return a;
+        if constexpr (is_matrix_scheme<scoring_scheme_type>::value) {
+            // match / mismatch are not read by the matrix entry points
+            gasalx_nv_aligner a = {GASALX_NV_GOTOH, (int32)TYPE, 0, 0, scheme.pattern_gap_open(),
+                                   scheme.pattern_gap_extension(), 0, 0};
+            return a;
+        } else {
+            gasalx_nv_aligner a = {GASALX_NV_GOTOH, (int32)TYPE, scheme.match(), scheme.mismatch(),
+                                   scheme.pattern_gap_open(), scheme.pattern_gap_extension(), 0, 0};
+            return a;
+        }
     }
     scoring_scheme_type scheme;
 };
@@ -257,6 +333,18 @@ struct BatchedAlignmentScore {
                 fprintf(stderr, "BatchedAlignmentScore::enact: with sinks the scores are int32, set m_scores32\n");
                 exit(EXIT_FAILURE);
             }
+        }
+        if constexpr (uses_matrix_scheme<aligner_type>::value) {
+            // GotohAligner over SubstitutionMatrixScheme: the matrix kernels (int32 scores, sinks optional)
+            if (stream.m_scores) {
+                fprintf(stderr, "BatchedAlignmentScore::enact: matrix scores are int32, set m_scores32\n");
+                exit(EXIT_FAILURE);
+            }
+            const gasalx_nv_matrix m = stream.aligner().scheme.c_matrix();
+            rc = gasalx_nv_matrix_score_device(engine(), &a, &m, stream.size(), &p, &t, stream.m_scores32,
+                                               stream.m_sinks, stream.max_pattern_length(),
+                                               stream.max_text_length(), hip_stream);
+        } else if (stream.m_sinks) {
             rc = gasalx_nv_score_sinks_device(engine(), &a, stream.size(), &p, &t, stream.m_scores32, stream.m_sinks,
                                               stream.max_pattern_length(), stream.max_text_length(), hip_stream);
         } else {
@@ -284,6 +372,9 @@ struct BatchedBandedAlignmentScore {
     static uint64 max_temp_storage(const uint32, const uint32, const uint32) { return 0; }
 
     void enact(stream_type stream, uint64 temp_size = 0u, uint8 *temp = NULL, void *hip_stream = NULL) {
+        static_assert(!uses_matrix_scheme<aligner_type>::value,
+                      "SubstitutionMatrixScheme runs under BatchedAlignmentScore / batch_alignment_score only: the "
+                      "banded scorer and the tracebacks have no matrix kernels");
         (void)temp_size; (void)temp;
         const gasalx_nv_aligner a = stream.aligner().c_aligner();
         gasalx_nv_strings p = {stream.m_patterns, stream.m_offsets, 0, stream.m_pattern_bits,
@@ -362,6 +453,32 @@ void batch_banded_alignment_score(const aligner_type aligner, const PackedString
     batch.enact(stream);
 }
 
+// batch_alignment_score(aligner, patterns, texts, sinks, scheduler, max_pattern_length, max_text_length)
+// (batched.h:137-150), the form proteinsw calls: patterns[k] against texts[k], full DP, on the engine's
+// stream (asynchronous, as nvbio's).  Every aligner BatchedAlignmentScore takes, the Simple schemes and
+// SubstitutionMatrixScheme, over PackedStringSet or ConcatenatedStringSet.  Scores are int32.
+// TextBlockingTag aligners fill sinks.scores and sinks.sinks (either may be NULL); PatternBlockingTag
+// aligners give scores only, and a non-NULL sinks.sinks with one is refused as enact() refuses it.
+inline PackedStringSet as_packed_string_set(const PackedStringSet &s) { return s; }
+inline PackedStringSet as_packed_string_set(const ConcatenatedStringSet &s) {
+    return PackedStringSet(s.m_count, reinterpret_cast<const uint32 *>(s.m_symbols), s.m_offsets, 8, 0);
+}
+template <typename aligner_type, typename pattern_set_type, typename text_set_type, typename scheduler_type>
+void batch_alignment_score(const aligner_type aligner, const pattern_set_type patterns, const text_set_type texts,
+                           BestSinks sinks, const scheduler_type, const uint32 max_pattern_length = 1000,
+                           const uint32 max_text_length = 1000) {
+    const PackedStringSet p = as_packed_string_set(patterns), t = as_packed_string_set(texts);
+    AlignmentStream<aligner_type> stream(aligner, p.size(), p.m_offsets, p.m_words, max_pattern_length, 0, t.m_words,
+                                         max_text_length, NULL);
+    stream.m_text_offsets = t.m_offsets;
+    stream.m_pattern_bits = p.m_bits; stream.m_pattern_big_endian = p.m_big_endian;
+    stream.m_text_bits = t.m_bits; stream.m_text_big_endian = t.m_big_endian;
+    stream.m_scores32 = sinks.scores;
+    stream.m_sinks = sinks.sinks;
+    BatchedAlignmentScore<AlignmentStream<aligner_type>, scheduler_type> batch;
+    batch.enact(stream);
+}
+
 // The outputs of a traceback batch (batched_inl.h:612-664's stream.output(): the Alignment
 // and the backtracer of each job), as device arrays: per pair the BestSink score, the
 // Alignment's source and sink as (x = text, y = pattern) pairs, and the backtracker's pushes
@@ -419,6 +536,9 @@ struct BatchedAlignmentTraceback {
         static_assert(!is_myers_tag<typename aligner_type::algorithm_tag>::value,
                       "MyersTag aligners run under BatchedBandedAlignmentScore only: nvbio has the banded Myers "
                       "scorer (myers/myers_banded_inl.h) and no full-DP or traceback form of it");
+        static_assert(!uses_matrix_scheme<aligner_type>::value,
+                      "SubstitutionMatrixScheme runs under BatchedAlignmentScore / batch_alignment_score only: the "
+                      "banded scorer and the tracebacks have no matrix kernels");
         (void)temp_size; (void)temp;
         const gasalx_nv_aligner a = stream.aligner().c_aligner();
         gasalx_nv_strings p = {stream.m_patterns, stream.m_offsets, 0, stream.m_pattern_bits,
@@ -457,6 +577,9 @@ struct BatchedBandedAlignmentTraceback {
         static_assert(!is_myers_tag<typename aligner_type::algorithm_tag>::value,
                       "MyersTag aligners run under BatchedBandedAlignmentScore only: nvbio has the banded Myers "
                       "scorer (myers/myers_banded_inl.h) and no full-DP or traceback form of it");
+        static_assert(!uses_matrix_scheme<aligner_type>::value,
+                      "SubstitutionMatrixScheme runs under BatchedAlignmentScore / batch_alignment_score only: the "
+                      "banded scorer and the tracebacks have no matrix kernels");
         (void)temp_size; (void)temp;
         const gasalx_nv_aligner a = stream.aligner().c_aligner();
         gasalx_nv_strings p = {stream.m_patterns, stream.m_offsets, 0, stream.m_pattern_bits,
