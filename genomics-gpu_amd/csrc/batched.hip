@@ -21,6 +21,7 @@
 #include "nvbanded_sink.hpp"
 #include "nvmyers.hpp"
 #include "nvmatrix.hpp"
+#include "nvmatrix_trace.hpp"
 
 namespace gx {
 
@@ -356,6 +357,21 @@ int nv_matrix_check(const gasalx_nv_aligner &al, uint32_t matrix_n) {
     return GASALX_OK;
 }
 
+// The caller's table (scores[t + p * n]) as the kernels' 32 x 32 image (tab[32 * p + t], zero outside
+// the n x n corner); returns the largest |entry|.
+int32_t nv_matrix_image(const gasalx_nv_matrix &mat, uint32_t (&tab)[kNvMatrixBytes / 4]) {
+    int8_t image[kNvMatrixBytes] = {};
+    int32_t entry_mag = 0;
+    for (uint32_t p = 0; p < mat.n; p++)
+        for (uint32_t t = 0; t < mat.n; t++) {
+            const int8_t v = mat.scores[t + p * mat.n];
+            image[p * kNvMatrixDim + t] = v;
+            entry_mag = std::max(entry_mag, std::abs((int32_t)v));
+        }
+    std::memcpy(tab, image, sizeof(image));
+    return entry_mag;
+}
+
 using NvMatrixFn = void (*)(NvMatrixArgs);
 NvMatrixFn nv_matrix_lookup(int type, bool sink, int shape) {
     return nv_instance(NV_GOTOH, type, sink, shape, [](auto, auto t, auto s, auto g, auto r) -> NvMatrixFn {
@@ -387,15 +403,7 @@ int nv_matrix_score_device(const gasalx_nv_aligner &al, const gasalx_nv_matrix &
     if (!txt.offsets) max_t = txt.length;
     // the table's image, by value in the arguments: read now, no device copy to reuse across streams
     NvMatrixArgs A;
-    int8_t image[kNvMatrixBytes] = {};
-    int32_t entry_mag = 0;
-    for (uint32_t p = 0; p < mat.n; p++)
-        for (uint32_t t = 0; t < mat.n; t++) {
-            const int8_t v = mat.scores[t + p * mat.n];
-            image[p * kNvMatrixDim + t] = v;
-            entry_mag = std::max(entry_mag, std::abs((int32_t)v));
-        }
-    std::memcpy(A.tab, image, sizeof(image));
+    const int32_t entry_mag = nv_matrix_image(mat, A.tab);
     // nv_score_plan's range check, the largest |entry| standing for match and mismatch
     const NvScheme s = {entry_mag, entry_mag, al.gap_open, al.gap_ext, al.deletion, al.insertion};
     if ((int64_t)(max_p + max_t + 2) * nv_score_mag(s) * 2 >= (1ll << 28))
@@ -538,6 +546,44 @@ int nv_traceback_device(const gasalx_nv_aligner &al, uint32_t n, const gasalx_nv
     const Fn fn = nv_static(al.aligner, al.type, false, [](auto a, auto t, auto) -> Fn {
         return &nv_traceback_kernel<a == NV_GOTOH, t>; });
     return launch_checked(fn, (n + 255) / 256, st, A);
+}
+
+// The same traceback of a GotohAligner over a substitution matrix (nvmatrix_trace.hpp): the checks
+// that need no lengths, in the entry points' order (the aligner and the table's size, the table,
+// the symbol bits), and the largest |entry|, which stands for match and mismatch in the range rule
+int nv_matrix_traceback_check(const gasalx_nv_aligner &al, const gasalx_nv_matrix &mat, const gasalx_nv_strings &pat,
+                              const gasalx_nv_strings &txt, int32_t *entry_mag) {
+    if (int rc = nv_matrix_check(al, mat.n)) return rc;
+    if (!mat.scores) return nv_fail(GASALX_EINVAL, "null argument");
+    if (int rc = nv_check(al, "bad aligner", "bad aligner", nullptr, pat, txt)) return rc;
+    if (entry_mag) {
+        uint32_t tab[kNvMatrixBytes / 4];
+        *entry_mag = nv_matrix_image(mat, tab);
+    }
+    return GASALX_OK;
+}
+
+// Workspace and outputs as nv_traceback_device; one instance per type, named
+// nvbio_matrix_traceback_gotoh_<global|local|semi> in traces.  The table is read now.
+int nv_matrix_traceback_device(const gasalx_nv_aligner &al, const gasalx_nv_matrix &mat, uint32_t n,
+                               const gasalx_nv_strings &pat, const gasalx_nv_strings &txt, uint32_t max_p,
+                               uint32_t max_t, uint8_t *dir, int32_t *row, int32_t *score, uint32_t *src,
+                               uint32_t *snk, uint8_t *ops, uint32_t ops_stride, uint32_t *n_ops, hipStream_t st) {
+    if (int rc = nv_matrix_traceback_check(al, mat, pat, txt, nullptr)) return rc;
+    if (n == 0) return GASALX_OK;
+    if (int rc = nv_check_ptrs(pat, txt, score && src && snk && ops && n_ops && dir && row)) return rc;
+    NvMatrixTbArgs B;
+    nv_matrix_image(mat, B.tab);
+    B.nsym = mat.n;
+    NvTbArgs &A = B.t;
+    nv_fill(A, pat, txt, NvScheme{0, 0, al.gap_open, al.gap_ext, 0, 0}, n);
+    A.max_m = max_p; A.max_n = max_t;
+    A.dir = dir; A.row = row; A.score = score; A.src = src; A.snk = snk; A.ops = ops; A.ops_stride = ops_stride;
+    A.n_ops = n_ops;
+    using Fn = void (*)(NvMatrixTbArgs);
+    const Fn fn = nv_static(NV_GOTOH, al.type, false, [](auto, auto t, auto) -> Fn {
+        return &nv_matrix_traceback_kernel<t>; });
+    return launch_checked(fn, (n + 255) / 256, st, B);
 }
 
 // BatchedBandedAlignmentTraceback<band> (nvtrace.hpp nv_banded_traceback_kernel); ED runs as

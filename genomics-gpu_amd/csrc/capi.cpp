@@ -589,12 +589,12 @@ struct NvTbOut {
     uint32_t *n_ops;
 };
 
-// A traceback batch in chunks of `chunk` pairs over the engine's workspace (band 0: the full DP):
-// the chunk from pair s on works on offsets + s, scores + s, sources + 2s, sinks + 2s,
-// ops + s * ops_stride and n_ops + s.
-int nv_tb_chunks(gasalx_engine *eng, const gasalx_nv_aligner *al, uint32_t band, uint32_t n, const gasalx_nv_strings *pat,
-                 const gasalx_nv_strings *txt, uint32_t max_p, uint32_t max_t, const NvTbOut &o, uint32_t chunk,
-                 hipStream_t st) {
+// A traceback batch in chunks of `chunk` pairs over the engine's workspace (band 0: the full DP;
+// mat: its substitution-matrix form, NULL otherwise): the chunk from pair s on works on
+// offsets + s, scores + s, sources + 2s, sinks + 2s, ops + s * ops_stride and n_ops + s.
+int nv_tb_chunks(gasalx_engine *eng, const gasalx_nv_aligner *al, const gasalx_nv_matrix *mat, uint32_t band, uint32_t n,
+                 const gasalx_nv_strings *pat, const gasalx_nv_strings *txt, uint32_t max_p, uint32_t max_t,
+                 const NvTbOut &o, uint32_t chunk, hipStream_t st) {
     gx::DevBuf &dir = eng->buf[B_NV_DIR];
     for (uint32_t s = 0; s < n; s += chunk) {
         const uint32_t m = std::min(chunk, n - s);
@@ -606,6 +606,9 @@ int nv_tb_chunks(gasalx_engine *eng, const gasalx_nv_aligner *al, uint32_t band,
         uint8_t *ops = o.ops + (size_t)s * o.ops_stride;
         const int rc = band ? gx::nv_banded_traceback_device(*al, band, m, p, t, max_p, dir.as<uint32_t>(), scores, sources,
                                                              sinks, ops, o.ops_stride, n_ops, st)
+                     : mat  ? gx::nv_matrix_traceback_device(*al, *mat, m, p, t, max_p, max_t, dir.as<uint8_t>(),
+                                                             eng->buf[B_NV_ROW].as<int32_t>(), scores, sources, sinks,
+                                                             ops, o.ops_stride, n_ops, st)
                             : gx::nv_traceback_device(*al, m, p, t, max_p, max_t, dir.as<uint8_t>(),
                                                       eng->buf[B_NV_ROW].as<int32_t>(), scores, sources, sinks, ops,
                                                       o.ops_stride, n_ops, st);
@@ -614,9 +617,10 @@ int nv_tb_chunks(gasalx_engine *eng, const gasalx_nv_aligner *al, uint32_t band,
     return GASALX_OK;
 }
 
-// The two traceback host forms after staging: the five device outputs reserved, the device form
-// (band 0: the full DP) run on them, the results copied to the caller's arrays `h`.
-int nv_tb_host_run(gasalx_engine *eng, const gasalx_nv_aligner *al, uint32_t band, uint32_t n,
+// The traceback host forms after staging: the five device outputs reserved, the device form
+// (band 0: the full DP; mat: its substitution-matrix form, NULL otherwise) run on them, the results
+// copied to the caller's arrays `h`.
+int nv_tb_host_run(gasalx_engine *eng, const gasalx_nv_aligner *al, const gasalx_nv_matrix *mat, uint32_t band, uint32_t n,
                    const gasalx_nv_strings *dp, const gasalx_nv_strings *dt, uint32_t max_p, uint32_t max_t,
                    const NvTbOut &h, hipStream_t st) {
     gx::DevBuf &s = eng->buf[B_NV_S], &src = eng->buf[B_NV_SRC], &snk = eng->buf[B_NV_SNK], &ops = eng->buf[B_NV_OPS],
@@ -629,8 +633,11 @@ int nv_tb_host_run(gasalx_engine *eng, const gasalx_nv_aligner *al, uint32_t ban
     const int rc =
         band ? gasalx_nv_banded_traceback_device(eng, al, band, n, dp, dt, max_p, s.as<int32_t>(), src.as<uint32_t>(),
                                                  snk.as<uint32_t>(), ops.as<uint8_t>(), h.ops_stride, nops.as<uint32_t>(), st)
-             : gasalx_nv_traceback_device(eng, al, n, dp, dt, max_p, max_t, s.as<int32_t>(), src.as<uint32_t>(),
-                                          snk.as<uint32_t>(), ops.as<uint8_t>(), h.ops_stride, nops.as<uint32_t>(), st);
+        : mat ? gasalx_nv_matrix_traceback_device(eng, al, mat, n, dp, dt, max_p, max_t, s.as<int32_t>(),
+                                                  src.as<uint32_t>(), snk.as<uint32_t>(), ops.as<uint8_t>(), h.ops_stride,
+                                                  nops.as<uint32_t>(), st)
+              : gasalx_nv_traceback_device(eng, al, n, dp, dt, max_p, max_t, s.as<int32_t>(), src.as<uint32_t>(),
+                                           snk.as<uint32_t>(), ops.as<uint8_t>(), h.ops_stride, nops.as<uint32_t>(), st);
     return host_finish(st, rc, {{h.scores, s.p, (size_t)n * 4}, {h.sources, src.p, (size_t)n * 8},
                                 {h.sinks, snk.p, (size_t)n * 8}, {h.ops, ops.p, (size_t)n * h.ops_stride},
                                 {h.n_ops, nops.p, (size_t)n * 4}});
@@ -1294,7 +1301,7 @@ int gasalx_nv_traceback_device(gasalx_engine *eng, const gasalx_nv_aligner *al, 
     const uint32_t chunk = (uint32_t)nv_tb_chunk(n, gasalx_nv_traceback_workspace(max_p, max_t, 1));
     CK(eng->buf[B_NV_DIR].reserve((size_t)((max_p + 7) / 8) * 8 * max_t * chunk + 64));
     CK(eng->buf[B_NV_ROW].reserve((size_t)max_t * chunk * 8 + 64));
-    return nv_tb_chunks(eng, al, 0, n, pat, txt, max_p, max_t, {scores, sources, sinks, ops, ops_stride, n_ops}, chunk, st);
+    return nv_tb_chunks(eng, al, nullptr, 0, n, pat, txt, max_p, max_t, {scores, sources, sinks, ops, ops_stride, n_ops}, chunk, st);
 }
 
 int gasalx_nv_traceback_host(gasalx_engine *eng, const gasalx_nv_aligner *al, uint32_t n, const gasalx_nv_strings *pat,
@@ -1314,7 +1321,70 @@ int gasalx_nv_traceback_host(gasalx_engine *eng, const gasalx_nv_aligner *al, ui
     if ((rc = nv_tb_checks(al, max_p, max_t, ops_stride))) return rc;
     gasalx_nv_strings dp, dt;
     if ((rc = nv_stage_strings(eng, n, pat, pat_words, txt, txt_words, st, dp, dt))) return rc;
-    return nv_tb_host_run(eng, al, 0, n, &dp, &dt, max_p, max_t, {scores, sources, sinks, ops, ops_stride, n_ops}, st);
+    return nv_tb_host_run(eng, al, nullptr, 0, n, &dp, &dt, max_p, max_t, {scores, sources, sinks, ops, ops_stride, n_ops}, st);
+}
+
+// The matrix form's checks after the null arguments: the aligner and the table's size, the table and
+// the symbol bits (before anything is read back or staged); `ranged` is then the aligner nv_tb_checks
+// takes, the largest |entry| standing for match and mismatch (the aligner's own match, mismatch,
+// deletion and insertion are never read)
+static int nv_mtb_checks(const gasalx_nv_aligner *al, const gasalx_nv_matrix *mat, const gasalx_nv_strings *pat,
+                         const gasalx_nv_strings *txt, gasalx_nv_aligner *ranged) {
+    int32_t mag = 0;
+    if (int rc = gx::nv_matrix_traceback_check(*al, *mat, *pat, *txt, &mag)) return rc;
+    *ranged = {al->aligner, al->type, mag, mag, al->gap_open, al->gap_ext, 0, 0};
+    return GASALX_OK;
+}
+
+int gasalx_nv_matrix_traceback_device(gasalx_engine *eng, const gasalx_nv_aligner *al, const gasalx_nv_matrix *mat,
+                                      uint32_t n, const gasalx_nv_strings *pat, const gasalx_nv_strings *txt,
+                                      uint32_t max_p, uint32_t max_t, int32_t *scores, uint32_t *sources,
+                                      uint32_t *sinks, uint8_t *ops, uint32_t ops_stride, uint32_t *n_ops,
+                                      void *stream) {
+    if (!eng || !al || !mat || !pat || !txt || !pat->words || !pat->offsets || !txt->words || !scores || !sources ||
+        !sinks || !ops || !n_ops) {
+        gx::set_error("null argument");
+        return GASALX_EINVAL;
+    }
+    gasalx_nv_aligner ranged;
+    int rc = nv_mtb_checks(al, mat, pat, txt, &ranged);
+    if (rc) return rc;
+    if (n == 0) return GASALX_OK;
+    hipStream_t st;
+    if ((rc = enter(eng, stream, &st))) return rc;
+    if ((rc = device_max_spans(pat, txt, n, st, &max_p, &max_t))) return rc;
+    if (!txt->offsets) max_t = txt->length;
+    if ((rc = nv_tb_checks(&ranged, max_p, max_t, ops_stride))) return rc;
+    // gasalx_nv_traceback_device's workspace and chunks
+    const uint32_t chunk = (uint32_t)nv_tb_chunk(n, gasalx_nv_traceback_workspace(max_p, max_t, 1));
+    CK(eng->buf[B_NV_DIR].reserve((size_t)((max_p + 7) / 8) * 8 * max_t * chunk + 64));
+    CK(eng->buf[B_NV_ROW].reserve((size_t)max_t * chunk * 8 + 64));
+    return nv_tb_chunks(eng, al, mat, 0, n, pat, txt, max_p, max_t, {scores, sources, sinks, ops, ops_stride, n_ops}, chunk,
+                        st);
+}
+
+int gasalx_nv_matrix_traceback_host(gasalx_engine *eng, const gasalx_nv_aligner *al, const gasalx_nv_matrix *mat,
+                                    uint32_t n, const gasalx_nv_strings *pat, uint64_t pat_words,
+                                    const gasalx_nv_strings *txt, uint64_t txt_words, int32_t *scores,
+                                    uint32_t *sources, uint32_t *sinks, uint8_t *ops, uint32_t ops_stride,
+                                    uint32_t *n_ops) {
+    if (!eng || !al || !mat || !pat || !txt || !pat->words || !pat->offsets || !txt->words || !scores || !sources ||
+        !sinks || !ops || !n_ops) {
+        gx::set_error("null argument");
+        return GASALX_EINVAL;
+    }
+    gasalx_nv_aligner ranged;
+    int rc = nv_mtb_checks(al, mat, pat, txt, &ranged);
+    if (rc) return rc;
+    if (n == 0) return GASALX_OK;
+    hipStream_t st;
+    if ((rc = enter(eng, nullptr, &st))) return rc;
+    const uint32_t max_p = max_span(pat->offsets, n);
+    const uint32_t max_t = txt->offsets ? max_span(txt->offsets, n) : txt->length;
+    if ((rc = nv_tb_checks(&ranged, max_p, max_t, ops_stride))) return rc;
+    gasalx_nv_strings dp, dt;
+    if ((rc = nv_stage_strings(eng, n, pat, pat_words, txt, txt_words, st, dp, dt))) return rc;
+    return nv_tb_host_run(eng, al, mat, 0, n, &dp, &dt, max_p, max_t, {scores, sources, sinks, ops, ops_stride, n_ops}, st);
 }
 
 int gasalx_nv_banded_traceback_device(gasalx_engine *eng, const gasalx_nv_aligner *al, uint32_t band, uint32_t n,
@@ -1330,7 +1400,7 @@ int gasalx_nv_banded_traceback_device(gasalx_engine *eng, const gasalx_nv_aligne
     if ((rc = nv_btb_checks(al, band, max_p, ops_stride))) return rc;
     const uint32_t chunk = (uint32_t)nv_tb_chunk(n, gasalx_nv_banded_traceback_workspace(max_p, band, 1));
     CK(eng->buf[B_NV_DIR].reserve((size_t)max_p * ((band + 3) / 4) * 4 * chunk + 64));
-    return nv_tb_chunks(eng, al, band, n, pat, txt, max_p, 0, {scores, sources, sinks, ops, ops_stride, n_ops}, chunk, st);
+    return nv_tb_chunks(eng, al, nullptr, band, n, pat, txt, max_p, 0, {scores, sources, sinks, ops, ops_stride, n_ops}, chunk, st);
 }
 
 int gasalx_nv_banded_traceback_host(gasalx_engine *eng, const gasalx_nv_aligner *al, uint32_t band, uint32_t n,
@@ -1350,7 +1420,7 @@ int gasalx_nv_banded_traceback_host(gasalx_engine *eng, const gasalx_nv_aligner 
     if ((rc = enter(eng, nullptr, &st))) return rc;
     gasalx_nv_strings dp, dt;
     if ((rc = nv_stage_strings(eng, n, pat, pat_words, txt, txt_words, st, dp, dt))) return rc;
-    return nv_tb_host_run(eng, al, band, n, &dp, &dt, max_p, 0, {scores, sources, sinks, ops, ops_stride, n_ops}, st);
+    return nv_tb_host_run(eng, al, nullptr, band, n, &dp, &dt, max_p, 0, {scores, sources, sinks, ops, ops_stride, n_ops}, st);
 }
 
 int gasalx_pairhmm_params(const uint8_t *bq, const uint8_t *iq, const uint8_t *dq, uint32_t n, float *qm,

@@ -235,6 +235,15 @@ int nv_traceback_device(const gasalx_nv_aligner &al, uint32_t n, const gasalx_nv
                         const gasalx_nv_strings &txt, uint32_t max_p, uint32_t max_t, uint8_t *dir, int32_t *row,
                         int32_t *score, uint32_t *src, uint32_t *snk, uint8_t *ops, uint32_t ops_stride,
                         uint32_t *n_ops, hipStream_t st);
+// the full-DP traceback of GotohAligner over a substitution matrix (nvmatrix_trace.hpp): workspace and
+// outputs as nv_traceback_device, the table as nv_matrix_score_device.  The check runs what needs no
+// lengths (aligner and table size, the table, symbol bits) and gives the largest |entry|.
+int nv_matrix_traceback_check(const gasalx_nv_aligner &al, const gasalx_nv_matrix &mat, const gasalx_nv_strings &pat,
+                              const gasalx_nv_strings &txt, int32_t *entry_mag);
+int nv_matrix_traceback_device(const gasalx_nv_aligner &al, const gasalx_nv_matrix &mat, uint32_t n,
+                               const gasalx_nv_strings &pat, const gasalx_nv_strings &txt, uint32_t max_p,
+                               uint32_t max_t, uint8_t *dir, int32_t *row, int32_t *score, uint32_t *src,
+                               uint32_t *snk, uint8_t *ops, uint32_t ops_stride, uint32_t *n_ops, hipStream_t st);
 int nv_banded_traceback_device(const gasalx_nv_aligner &al, uint32_t band, uint32_t n, const gasalx_nv_strings &pat,
                                const gasalx_nv_strings &txt, uint32_t max_p, uint32_t *dir, int32_t *score,
                                uint32_t *src, uint32_t *snk, uint8_t *ops, uint32_t ops_stride, uint32_t *n_ops,

@@ -42,6 +42,7 @@ EXPORTS = (
     "gasalx_nv_describe_banded_sinks_plan",
     "gasalx_nv_banded_myers_device", "gasalx_nv_banded_myers_host", "gasalx_nv_describe_myers_plan",
     "gasalx_nv_traceback_device", "gasalx_nv_traceback_host",
+    "gasalx_nv_matrix_traceback_device", "gasalx_nv_matrix_traceback_host",
     "gasalx_nv_banded_traceback_device", "gasalx_nv_banded_traceback_host",
     "gasalx_multi_create", "gasalx_multi_destroy", "gasalx_multi_info", "gasalx_multi_engine",
     "gasalx_shard_bounds", "gasalx_multi_align_host", "gasalx_multi_pairhmm_host",
@@ -649,6 +650,50 @@ class Engine:
                                                 ctypes.c_uint32(max_text_len), v("score"), v("source"), v("sink"),
                                                 v("ops"), ctypes.c_uint32(ops_stride), v("n_ops"),
                                                 ctypes.c_void_p(stream or None)), "nv_traceback_device")
+
+    def nv_matrix_traceback_host(self, aligner: "NvAligner", matrix: "NvMatrix", patterns: "PackedSet",
+                                 texts: "PackedSet", ops_stride: int = None):
+        """The full-DP Gotoh traceback with a substitution matrix (gasalx_nv_matrix_traceback_host): S(p, t)
+        = matrix.scores[p, t], symbols >= n read as n - 1, aligner.match / mismatch ignored.  The dict
+        nv_traceback_host returns; ops_stride defaults to its minimum, max pattern + max text length."""
+        n = patterns.n
+        po = np.asarray(patterns.offsets, np.int64)
+        plen = po[1:] - po[:-1]
+        if texts.offsets is not None:
+            to = np.asarray(texts.offsets, np.int64)
+            tlen = to[1:] - to[:-1]
+        else:
+            tlen = np.full(n, int(texts.length), np.int64)
+        stride = int(plen.max(initial=0) + tlen.max(initial=0)) if ops_stride is None else int(ops_stride)
+        sc = np.zeros(n, np.int32)
+        src = np.zeros(2 * n, np.uint32)
+        snk = np.zeros(2 * n, np.uint32)
+        ops = np.zeros(max(n * stride, 1), np.uint8)
+        nops = np.zeros(n, np.uint32)
+        ca, cm = aligner.cstruct(), matrix.cstruct()
+        _check(lib().gasalx_nv_matrix_traceback_host(self._h, ctypes.byref(ca), ctypes.byref(cm), ctypes.c_uint32(n),
+                                                     ctypes.byref(patterns.cstruct()), ctypes.c_uint64(len(patterns.words)),
+                                                     ctypes.byref(texts.cstruct()), ctypes.c_uint64(len(texts.words)),
+                                                     _p(sc), _p(src), _p(snk), _p(ops), ctypes.c_uint32(stride), _p(nops)),
+               "nv_matrix_traceback_host")
+        return dict(score=sc, source=src.reshape(n, 2), sink=snk.reshape(n, 2),
+                    ops=[ops[k * stride:k * stride + int(nops[k])].copy() for k in range(n)])
+
+    def nv_matrix_traceback_device_ptrs(self, aligner: "NvAligner", matrix: "NvMatrix", n: int, pat: dict, txt: dict,
+                                        outs: dict, ops_stride: int, max_pattern_len: int = 0, max_text_len: int = 0,
+                                        stream: int = 0):
+        """Device-resident form (gasalx_nv_matrix_traceback_device); the table stays a host array, the
+        other arguments as nv_traceback_device_ptrs."""
+        mk = lambda d: CNvStrings(d["words"], d.get("offsets") or None, d.get("length", 0), d["bits"],
+                                  int(d.get("big_endian", False)))
+        ca, cm = aligner.cstruct(), matrix.cstruct()
+        v = lambda k: ctypes.c_void_p(outs[k] or None)
+        _check(lib().gasalx_nv_matrix_traceback_device(self._h, ctypes.byref(ca), ctypes.byref(cm), ctypes.c_uint32(n),
+                                                       ctypes.byref(mk(pat)), ctypes.byref(mk(txt)),
+                                                       ctypes.c_uint32(max_pattern_len), ctypes.c_uint32(max_text_len),
+                                                       v("score"), v("source"), v("sink"), v("ops"),
+                                                       ctypes.c_uint32(ops_stride), v("n_ops"),
+                                                       ctypes.c_void_p(stream or None)), "nv_matrix_traceback_device")
 
     def nv_banded_traceback_host(self, aligner: "NvAligner", band: int, patterns: "PackedSet", texts: "PackedSet"):
         """nvbio BatchedBandedAlignmentTraceback<band> (gasalx_nv_banded_traceback_host): the dict

@@ -500,7 +500,8 @@ int gasalx_nv_describe_myers_plan(int32_t type, uint32_t alphabet_size, uint32_t
  * batch runs in chunks of at most 4 GB of it (gasalx_nv_traceback_workspace gives the bytes a
  * call reserves; the environment variable GASALX_NV_TB_BUDGET, in bytes, replaces the 4 GB for
  * both tracebacks: a test knob).  Calls that share an engine must be serialised (one workspace
- * per engine). */
+ * per engine).  gasalx_nv_traceback_workspace also serves gasalx_nv_matrix_traceback_* below: the
+ * same layout and size. */
 uint64_t gasalx_nv_traceback_workspace(uint32_t max_pattern_len, uint32_t max_text_len, uint32_t n_pairs);
 int gasalx_nv_traceback_device(gasalx_engine *eng, const gasalx_nv_aligner *aligner, uint32_t n_pairs,
                                const gasalx_nv_strings *dev_patterns, const gasalx_nv_strings *dev_texts,
@@ -512,6 +513,34 @@ int gasalx_nv_traceback_host(gasalx_engine *eng, const gasalx_nv_aligner *aligne
                              const gasalx_nv_strings *texts, uint64_t text_words, int32_t *scores,
                              uint32_t *sources, uint32_t *sinks, uint8_t *ops, uint32_t ops_stride,
                              uint32_t *n_ops);
+/* The same traceback for a GotohAligner over a substitution matrix (gasalx_nv_matrix above; the
+ * reference's cell update asks the scheme, gotoh/gotoh_inl.h:534, so its templates trace a
+ * BlosumScheme unchanged): S(p, t) = scores[t + p * n] in the cell update, everything else
+ * (flags, BestSink in the PatternBlockingTag report order, the walk, outputs and coordinates,
+ * the sentinel outputs of a pair with an empty string, ops_stride >= max pattern + max text
+ * length, max lengths 0 = read back, one shared text) as gasalx_nv_traceback_*.  GLOBAL, LOCAL and
+ * SEMI_GLOBAL; the full DP only (the banded traceback has no matrix form).  The workspace has
+ * gasalx_nv_traceback_*'s layout and size: gasalx_nv_traceback_workspace serves both, and both
+ * run in chunks under the same budget.  The table is read during the call and is the caller's
+ * again on return; a symbol >= n is read as n - 1; the aligner's match and mismatch are never read.
+ * Checks, in this order: a NULL argument GASALX_EINVAL; a bad aligner or type GASALX_EINVAL, an
+ * aligner other than GASALX_NV_GOTOH GASALX_EUNSUPPORTED, n outside 2..32 GASALX_EINVAL; a NULL
+ * table GASALX_EINVAL; symbol bits other than 2 / 4 / 8 GASALX_EINVAL; then gasalx_nv_traceback_*'s
+ * with the largest |entry| standing for match and mismatch: (max pattern + max text + 2) *
+ * max(|entry|, |gap_open|, |gap_ext|) > 32767 GASALX_ERANGE, ops_stride too small GASALX_EINVAL,
+ * pattern x text above 16 M cells GASALX_ERANGE. */
+int gasalx_nv_matrix_traceback_device(gasalx_engine *eng, const gasalx_nv_aligner *aligner,
+                                      const gasalx_nv_matrix *matrix, uint32_t n_pairs,
+                                      const gasalx_nv_strings *dev_patterns, const gasalx_nv_strings *dev_texts,
+                                      uint32_t max_pattern_len, uint32_t max_text_len, int32_t *dev_scores,
+                                      uint32_t *dev_sources, uint32_t *dev_sinks, uint8_t *dev_ops,
+                                      uint32_t ops_stride, uint32_t *dev_n_ops, void *stream);
+int gasalx_nv_matrix_traceback_host(gasalx_engine *eng, const gasalx_nv_aligner *aligner,
+                                    const gasalx_nv_matrix *matrix, uint32_t n_pairs,
+                                    const gasalx_nv_strings *patterns, uint64_t pattern_words,
+                                    const gasalx_nv_strings *texts, uint64_t text_words, int32_t *scores,
+                                    uint32_t *sources, uint32_t *sinks, uint8_t *ops, uint32_t ops_stride,
+                                    uint32_t *n_ops);
 /* nvbio BatchedBandedAlignmentTraceback<BAND_LEN, CHECKPOINTS, stream> (NvB/nvbio/alignment/
  * batched.h:464-478, batched_banded_inl.h:248-297; nvBowtie's callers traceback_inl.h:239-257):
  * the banded traceback of every pair, band length 2..32 as an argument.  Outputs as

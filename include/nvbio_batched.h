@@ -40,9 +40,11 @@
  * bytes, n <= 32, read as table[r + q*n] with r the text and q the pattern symbol: the proteinsw
  * example's BlosumScheme, examples/proteinsw/proteinsw.cu:76-100, with the table made a member) is
  * routed by BatchedAlignmentScore::enact to gasalx_nv_matrix_score_* (nvmatrix.hpp: int32 scores,
- * BestSink positions for TextBlockingTag aligners; symbols >= n read as n - 1).  No table is
+ * BestSink positions for TextBlockingTag aligners; symbols >= n read as n - 1), and by
+ * BatchedAlignmentTraceback::enact to gasalx_nv_matrix_traceback_* (nvmatrix_trace.hpp: the full-DP
+ * traceback with the same outputs and workspace as the Simple schemes').  No table is
  * shipped: the caller supplies BLOSUM62 or whatever it scores with.  Smith-Waterman never reads a
- * substitution score from its scheme, and the banded scorer and the tracebacks have no matrix
+ * substitution score from its scheme, and the banded scorer and the banded traceback have no matrix
  * kernels: all three refuse the scheme at compile time.  ConcatenatedStringSet /
  * make_concatenated_string_set (8-bit symbols) and the free function batch_alignment_score
  * (batched.h:137-150), proteinsw's call, take any aligner the full scorer takes.
@@ -373,8 +375,8 @@ struct BatchedBandedAlignmentScore {
 
     void enact(stream_type stream, uint64 temp_size = 0u, uint8 *temp = NULL, void *hip_stream = NULL) {
         static_assert(!uses_matrix_scheme<aligner_type>::value,
-                      "SubstitutionMatrixScheme runs under BatchedAlignmentScore / batch_alignment_score only: the "
-                      "banded scorer and the tracebacks have no matrix kernels");
+                      "SubstitutionMatrixScheme runs under BatchedAlignmentScore / batch_alignment_score and "
+                      "BatchedAlignmentTraceback only: the banded scorer and the banded traceback have no matrix kernels");
         (void)temp_size; (void)temp;
         const gasalx_nv_aligner a = stream.aligner().c_aligner();
         gasalx_nv_strings p = {stream.m_patterns, stream.m_offsets, 0, stream.m_pattern_bits,
@@ -536,19 +538,25 @@ struct BatchedAlignmentTraceback {
         static_assert(!is_myers_tag<typename aligner_type::algorithm_tag>::value,
                       "MyersTag aligners run under BatchedBandedAlignmentScore only: nvbio has the banded Myers "
                       "scorer (myers/myers_banded_inl.h) and no full-DP or traceback form of it");
-        static_assert(!uses_matrix_scheme<aligner_type>::value,
-                      "SubstitutionMatrixScheme runs under BatchedAlignmentScore / batch_alignment_score only: the "
-                      "banded scorer and the tracebacks have no matrix kernels");
         (void)temp_size; (void)temp;
         const gasalx_nv_aligner a = stream.aligner().c_aligner();
         gasalx_nv_strings p = {stream.m_patterns, stream.m_offsets, 0, stream.m_pattern_bits,
                                stream.m_pattern_big_endian};
         gasalx_nv_strings t = {stream.m_text, stream.m_text_offsets, stream.m_text_len, stream.m_text_bits,
                                stream.m_text_big_endian};
-        const int rc = gasalx_nv_traceback_device(engine(), &a, stream.size(), &p, &t, stream.max_pattern_length(),
-                                                  stream.m_text_offsets ? stream.m_max_text_len : stream.m_text_len,
-                                                  stream.m_scores32, stream.m_sources, stream.m_sinks, stream.m_ops,
-                                                  stream.m_ops_stride, stream.m_n_ops, hip_stream);
+        const uint32 max_text_len = stream.m_text_offsets ? stream.m_max_text_len : stream.m_text_len;
+        int rc;
+        if constexpr (uses_matrix_scheme<aligner_type>::value) {
+            // GotohAligner over SubstitutionMatrixScheme: the matrix traceback, the same workspace and outputs
+            const gasalx_nv_matrix m = stream.aligner().scheme.c_matrix();
+            rc = gasalx_nv_matrix_traceback_device(engine(), &a, &m, stream.size(), &p, &t, stream.max_pattern_length(),
+                                                   max_text_len, stream.m_scores32, stream.m_sources, stream.m_sinks,
+                                                   stream.m_ops, stream.m_ops_stride, stream.m_n_ops, hip_stream);
+        } else {
+            rc = gasalx_nv_traceback_device(engine(), &a, stream.size(), &p, &t, stream.max_pattern_length(),
+                                            max_text_len, stream.m_scores32, stream.m_sources, stream.m_sinks,
+                                            stream.m_ops, stream.m_ops_stride, stream.m_n_ops, hip_stream);
+        }
         if (rc != GASALX_OK) {
             fprintf(stderr, "BatchedAlignmentTraceback::enact: %s\n", gasalx_last_error());
             exit(EXIT_FAILURE);
@@ -578,8 +586,8 @@ struct BatchedBandedAlignmentTraceback {
                       "MyersTag aligners run under BatchedBandedAlignmentScore only: nvbio has the banded Myers "
                       "scorer (myers/myers_banded_inl.h) and no full-DP or traceback form of it");
         static_assert(!uses_matrix_scheme<aligner_type>::value,
-                      "SubstitutionMatrixScheme runs under BatchedAlignmentScore / batch_alignment_score only: the "
-                      "banded scorer and the tracebacks have no matrix kernels");
+                      "SubstitutionMatrixScheme runs under BatchedAlignmentScore / batch_alignment_score and "
+                      "BatchedAlignmentTraceback only: the banded scorer and the banded traceback have no matrix kernels");
         (void)temp_size; (void)temp;
         const gasalx_nv_aligner a = stream.aligner().c_aligner();
         gasalx_nv_strings p = {stream.m_patterns, stream.m_offsets, 0, stream.m_pattern_bits,

@@ -9,7 +9,14 @@ score only and with sinks.  The four calls alternate inside every repeat, each l
 with HIP events after warm-up launches; the median and the spread (min, max) of the repeats are
 reported.  Scores of the first pairs are checked against a numpy fill.  Prints one JSON line.
 
-usage: nv_matrix_probe.py [pairs] [repeats]"""
+--traceback times the full-DP traceback instead (gasalx_nv_matrix_traceback_device, csrc/nvmatrix_trace.hpp)
+against the Gotoh traceback under SimpleGotohScheme(1, -1, -5, -3) (gasalx_nv_traceback_device,
+csrc/nvtrace.hpp) on the same strings, GLOBAL, LOCAL and SEMI_GLOBAL: the two alternate inside every
+repeat with HIP events around each device call.  128 x 1024 takes 139 KB of workspace per pair, so a
+4 GB chunk holds about 30 K pairs: the default is 16,384 pairs, one chunk.  The LOCAL scores are checked
+against the matrix scorer's.  Prints one JSON line.
+
+usage: nv_matrix_probe.py [--traceback] [pairs] [repeats]"""
 import json
 import os
 import sys
@@ -60,7 +67,62 @@ def local_score(S, p, t):
     return best
 
 
+def traceback_leg(args):
+    n = int(args[0]) if len(args) > 0 else 16384
+    reps = int(args[1]) if len(args) > 1 else 10
+    rng = np.random.default_rng(0x5EED1024)
+    tri = np.triu(rng.integers(-4, 12, (N_SYM, N_SYM)))
+    mat = G.NvMatrix((tri + np.triu(tri, 1).T).astype(np.int8))
+    dev = torch.device("cuda:0")
+    pats = rng.integers(0, N_SYM, (n, M), dtype=np.uint8)
+    texts = rng.integers(0, N_SYM, (n, TL), dtype=np.uint8)
+    keep = [torch.from_numpy(pats.reshape(-1)).to(dev), torch.from_numpy(texts.reshape(-1)).to(dev),
+            torch.arange(0, (n + 1) * M, M, dtype=torch.int32, device=dev),
+            torch.arange(0, (n + 1) * TL, TL, dtype=torch.int32, device=dev)]
+    pat = dict(words=keep[0].data_ptr(), offsets=keep[2].data_ptr(), bits=8, big_endian=False)
+    txt = dict(words=keep[1].data_ptr(), offsets=keep[3].data_ptr(), bits=8, big_endian=False)
+    stride = M + TL
+    bufs = {k: dict(score=torch.zeros(n, dtype=torch.int32, device=dev),
+                    source=torch.zeros(2 * n, dtype=torch.int32, device=dev),
+                    sink=torch.zeros(2 * n, dtype=torch.int32, device=dev),
+                    ops=torch.zeros(n * stride, dtype=torch.uint8, device=dev),
+                    n_ops=torch.zeros(n, dtype=torch.int32, device=dev)) for k in ("matrix", "simple")}
+    ptrs = {k: {f: t.data_ptr() for f, t in v.items()} for k, v in bufs.items()}
+    eng = G.Engine(0)
+    ts = torch.cuda.Stream()
+    s = ts.cuda_stream
+    workspace = G.nv_traceback_workspace(M, TL, n)
+    line = {"probe": "nv_matrix_traceback", "pairs": n, "pattern": M, "text": TL, "symbols": N_SYM, "repeats": reps,
+            "workspace_bytes": workspace, "one_chunk": workspace >= (G.nv_traceback_workspace(M, TL, 1) - 128) * n}
+    ok = True
+    cells = n * M * TL
+    for name, type_ in (("global", G.NV_GLOBAL), ("local", G.NV_LOCAL), ("semi", G.NV_SEMI_GLOBAL)):
+        al = G.NvAligner(G.NV_GOTOH, type_, 1, -1, GO, GE)
+        calls = {
+            "simple": lambda: eng.nv_traceback_device_ptrs(al, n, pat, txt, ptrs["simple"], stride, M, TL, s),
+            "matrix": lambda: eng.nv_matrix_traceback_device_ptrs(al, mat, n, pat, txt, ptrs["matrix"], stride, M, TL, s),
+        }
+        r = timed(calls, ts, 2, reps)
+        for k, (med, lo, hi) in r.items():
+            line[f"{name}_{k}_ms"] = round(med, 3)
+            line[f"{name}_{k}_ms_min_max"] = [round(lo, 3), round(hi, 3)]
+            line[f"{name}_{k}_gcups"] = round(cells / med / 1e6, 1)
+        line[f"{name}_matrix_over_simple"] = round(r["matrix"][0] / r["simple"][0], 3)
+        line[f"{name}_mean_ops"] = {k: round(float(bufs[k]["n_ops"].float().mean()), 1) for k in bufs}
+        if type_ == G.NV_LOCAL:
+            want = torch.zeros(n, dtype=torch.int32, device=dev)
+            eng.nv_matrix_score_device_ptrs(al, mat, n, pat, txt, want.data_ptr(), 0, M, TL, s)
+            ts.synchronize()
+            ok = ok and bool(torch.equal(want, bufs["matrix"]["score"]))
+    line["scores_ok"] = ok
+    print(json.dumps(line), flush=True)
+    eng.close()
+    return 0 if ok else 1
+
+
 def main():
+    if "--traceback" in sys.argv[1:]:
+        return traceback_leg([a for a in sys.argv[1:] if a != "--traceback"])
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 50000
     reps = int(sys.argv[2]) if len(sys.argv) > 2 else 20
     rng = np.random.default_rng(0x5EED1024)

@@ -3,10 +3,13 @@
 // SubstitutionMatrixScheme must reach gasalx_nv_matrix_score_device with the scheme's table and gap
 // scores, through BatchedAlignmentScore::enact and through batch_alignment_score over 8-bit
 // ConcatenatedStringSets; a Simple scheme through the same free function must make the calls it always
-// made.  The compile-time refusals, one macro each (the file must then fail to compile):
+// made.  BatchedAlignmentTraceback::enact over a TracebackStream of the matrix aligner must reach
+// gasalx_nv_matrix_traceback_device with the table, n, the gap scores and every output pointer, and a
+// Simple-scheme stream must still reach gasalx_nv_traceback_device.  The compile-time refusals, one
+// macro each (the file must then fail to compile):
 //   -DCHECK_SW_OVER_MATRIX_REFUSED       SmithWatermanAligner over SubstitutionMatrixScheme
 //   -DCHECK_BANDED_OVER_MATRIX_REFUSED   BatchedBandedAlignmentScore with the matrix aligner
-//   -DCHECK_TRACEBACK_OVER_MATRIX_REFUSED  BatchedAlignmentTraceback with it
+//   -DCHECK_BANDED_TRACEBACK_OVER_MATRIX_REFUSED  BatchedBandedAlignmentTraceback with it
 #include <stdio.h>
 #include <string.h>
 
@@ -14,12 +17,14 @@
 
 namespace {
 struct Call {
-    int which = 0;   // 1 score, 2 score + sinks, 3 matrix
+    int which = 0;   // 1 score, 2 score + sinks, 3 matrix, 4 traceback, 5 matrix traceback
     gasalx_nv_aligner al;
     gasalx_nv_matrix mat;
     uint32_t n, max_p, max_t;
     gasalx_nv_strings p, t;
     const void *scores, *sinks;
+    const void *sources = nullptr, *ops = nullptr, *n_ops = nullptr, *stream = nullptr;   // the tracebacks
+    uint32_t ops_stride = 0;
 };
 Call last;
 int n_calls = 0, failures = 0;
@@ -50,9 +55,33 @@ int gasalx_nv_matrix_score_device(gasalx_engine *eng, const gasalx_nv_aligner *a
     n_calls++;
     return GASALX_OK;
 }
-#if defined(CHECK_BANDED_OVER_MATRIX_REFUSED) || defined(CHECK_TRACEBACK_OVER_MATRIX_REFUSED)
+uint64_t gasalx_nv_traceback_workspace(uint32_t, uint32_t, uint32_t) { return 0; }
+int gasalx_nv_traceback_device(gasalx_engine *, const gasalx_nv_aligner *al, uint32_t n, const gasalx_nv_strings *p,
+                               const gasalx_nv_strings *t, uint32_t max_p, uint32_t max_t, int32_t *scores,
+                               uint32_t *sources, uint32_t *sinks, uint8_t *ops, uint32_t ops_stride, uint32_t *n_ops,
+                               void *stream) {
+    last = Call{4, *al, {nullptr, 0}, n, max_p, max_t, *p, *t, scores, sinks, sources, ops, n_ops, stream, ops_stride};
+    n_calls++;
+    return GASALX_OK;
+}
+int gasalx_nv_matrix_traceback_device(gasalx_engine *eng, const gasalx_nv_aligner *al, const gasalx_nv_matrix *mat,
+                                      uint32_t n, const gasalx_nv_strings *p, const gasalx_nv_strings *t, uint32_t max_p,
+                                      uint32_t max_t, int32_t *scores, uint32_t *sources, uint32_t *sinks, uint8_t *ops,
+                                      uint32_t ops_stride, uint32_t *n_ops, void *stream) {
+    if (eng != kEngine) return GASALX_EINVAL;
+    last = Call{5, *al, *mat, n, max_p, max_t, *p, *t, scores, sinks, sources, ops, n_ops, stream, ops_stride};
+    n_calls++;
+    return GASALX_OK;
+}
+#if defined(CHECK_BANDED_OVER_MATRIX_REFUSED)
 int gasalx_nv_banded_score_device(gasalx_engine *, const gasalx_nv_aligner *, uint32_t, uint32_t, const gasalx_nv_strings *,
                                   const gasalx_nv_strings *, int32_t *, uint32_t, void *) { return GASALX_OK; }
+#endif
+#if defined(CHECK_BANDED_TRACEBACK_OVER_MATRIX_REFUSED)
+uint64_t gasalx_nv_banded_traceback_workspace(uint32_t, uint32_t, uint32_t) { return 0; }
+int gasalx_nv_banded_traceback_device(gasalx_engine *, const gasalx_nv_aligner *, uint32_t, uint32_t,
+                                      const gasalx_nv_strings *, const gasalx_nv_strings *, uint32_t, int32_t *, uint32_t *,
+                                      uint32_t *, uint8_t *, uint32_t, uint32_t *, void *) { return GASALX_OK; }
 #endif
 }
 
@@ -139,12 +168,49 @@ int main() {
                                          PackedStringSet(2, nullptr, txt_offsets, 8, 0), out, DeviceThreadScheduler(), 5, 13);
     }
 #endif
-#ifdef CHECK_TRACEBACK_OVER_MATRIX_REFUSED
-    {   // static_assert: no matrix tracebacks
+    {   // the full-DP traceback: the matrix aligner reaches the matrix entry point, a Simple scheme its own
+        static uint32 sources[4], n_ops[2];
+        static uint8 ops[2 * 18];
+        void *const hip_stream = reinterpret_cast<void *>(0x20);
+        auto fill = [&](auto &s) {
+            s.m_text_offsets = txt_offsets; s.m_max_text_len = 13;
+            s.m_pattern_bits = 8; s.m_pattern_big_endian = 0; s.m_text_bits = 8; s.m_text_big_endian = 0;
+        };
+        auto check_outputs = [&] {
+            EXPECT(last.n == 2 && last.max_p == 5 && last.max_t == 13 && last.scores == scores32 && last.sources == sources &&
+                   last.sinks == sinks && last.ops == ops && last.ops_stride == 18 && last.n_ops == n_ops &&
+                   last.stream == hip_stream);
+            EXPECT(last.p.words == (const uint32_t *)pat_symbols && last.p.offsets == pat_offsets && last.p.bits == 8 &&
+                   last.t.words == (const uint32_t *)txt_symbols && last.t.offsets == txt_offsets && last.t.bits == 8);
+        };
+        typedef GotohAligner<LOCAL, SubstitutionMatrixScheme> matrix_aligner;
+        typedef TracebackStream<matrix_aligner> matrix_stream;
+        matrix_stream ms(matrix_aligner(scheme), 2, pat_offsets, (const uint32 *)pat_symbols, 5, 9,
+                         (const uint32 *)txt_symbols, 0, scores32, sources, sinks, ops, 18, n_ops);
+        fill(ms);
+        BatchedAlignmentTraceback<0, matrix_stream> mbatch;
+        mbatch.enact(ms, 0u, NULL, hip_stream);
+        EXPECT(n_calls == 7 && last.which == 5 && last.mat.scores == table && last.mat.n == 24);
+        EXPECT(last.al.aligner == GASALX_NV_GOTOH && last.al.type == GASALX_NV_LOCAL && last.al.gap_open == -5 &&
+               last.al.gap_ext == -3);
+        check_outputs();
+        typedef GotohAligner<LOCAL, SimpleGotohScheme> simple_aligner;
+        typedef TracebackStream<simple_aligner> simple_stream;
+        simple_stream ss(simple_aligner(SimpleGotohScheme(1, -1, -5, -3)), 2, pat_offsets, (const uint32 *)pat_symbols, 5, 9,
+                         (const uint32 *)txt_symbols, 0, scores32, sources, sinks, ops, 18, n_ops);
+        fill(ss);
+        BatchedAlignmentTraceback<0, simple_stream> sbatch;
+        sbatch.enact(ss, 0u, NULL, hip_stream);
+        EXPECT(n_calls == 8 && last.which == 4 && last.al.match == 1 && last.al.mismatch == -1 && last.al.gap_open == -5 &&
+               last.al.gap_ext == -3 && last.mat.scores == nullptr);
+        check_outputs();
+    }
+#ifdef CHECK_BANDED_TRACEBACK_OVER_MATRIX_REFUSED
+    {   // static_assert: no banded matrix traceback
         auto al = make_gotoh_aligner<LOCAL, TextBlockingTag>(scheme);
         typedef TracebackStream<decltype(al)> stream_type;
         stream_type s(al, 2, pat_offsets, nullptr, 5, 9, nullptr, 13, scores32, nullptr, nullptr, nullptr, 18, nullptr);
-        BatchedAlignmentTraceback<0, stream_type> batch;
+        BatchedBandedAlignmentTraceback<15, 0, stream_type> batch;
         batch.enact(s);
     }
 #endif

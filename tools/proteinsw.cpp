@@ -1,7 +1,9 @@
 // proteinsw — protein Smith-Waterman through include/nvbio_batched.h: the four batch_alignment_score
 // calls of nvbio's proteinsw example (LOCAL Gotoh with gaps -5 / -3 over n_strings pairs of a 128-symbol
 // pattern and a 1024-symbol text, 8-bit concatenated string sets): a constant scheme and a 24 x 24
-// substitution matrix, each under a PatternBlockingTag and a TextBlockingTag aligner.
+// substitution matrix, each under a PatternBlockingTag and a TextBlockingTag aligner.  A fifth step, which
+// the example does not have, runs the matrix LOCAL traceback of the same batch (BatchedAlignmentTraceback
+// over the matrix aligner), replays the first 16 alignments on the host and prints one of them.
 //
 // No BLOSUM table is shipped: the caller of the library supplies its own.  This tool scores with a
 // seeded random symmetric table with entries in -4..11 (BLOSUM62's range); throughput does not depend
@@ -16,6 +18,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <random>
+#include <string>
 #include <vector>
 
 #include "nvbio_batched.h"
@@ -111,6 +114,85 @@ bool run(const char *label, const Aligner &aligner, const Scheme &check, const B
     return ok;
 }
 
+// The fifth step: the matrix LOCAL traceback of the batch through BatchedAlignmentTraceback.  The first
+// 16 alignments are replayed on the host from sink to source (a run of L equal gap ops costs
+// gap_open + gap_ext * (L - 1); the spans must be the reported ones) and their scores printed beside the
+// returned ones; the first is printed as pattern, marks and text.
+bool run_traceback(const aln::SubstitutionMatrixScheme &scheme, const Batch &b) {
+    typedef aln::GotohAligner<aln::LOCAL, aln::SubstitutionMatrixScheme> aligner_type;
+    typedef aln::TracebackStream<aligner_type> stream_type;
+    const uint32 stride = kP + kT;
+    uint32 *d_sources, *d_n_ops;
+    uint8 *d_ops;
+    HIP_OK(hipMalloc(&d_sources, (size_t)b.n * 8));
+    HIP_OK(hipMalloc(&d_n_ops, (size_t)b.n * 4));
+    HIP_OK(hipMalloc(&d_ops, (size_t)b.n * stride));
+    stream_type s(aligner_type(scheme), b.n, b.d_poff, reinterpret_cast<const uint32 *>(b.d_pat), kP, b.n * kP,
+                  reinterpret_cast<const uint32 *>(b.d_txt), 0, b.d_scores, d_sources, b.d_sinks, d_ops, stride, d_n_ops);
+    s.m_text_offsets = b.d_toff; s.m_max_text_len = kT;
+    s.m_pattern_bits = 8; s.m_pattern_big_endian = 0; s.m_text_bits = 8; s.m_text_big_endian = 0;
+    aln::BatchedAlignmentTraceback<0, stream_type> batch;
+    const auto t0 = std::chrono::steady_clock::now();
+    batch.enact(s);
+    HIP_OK(hipDeviceSynchronize());
+    const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    printf("  traceback (Matrix/P): %.1f GCUPS, %.3f s, workspace %.1f MB\n",
+           1.0e-9 * double(kP) * double(kT) * double(b.n) / sec, sec,
+           1.0e-6 * double(aln::BatchedAlignmentTraceback<0, stream_type>::max_temp_storage(kP, kT, b.n)));
+
+    const uint32 n_check = std::min<uint32>(16, b.n);
+    std::vector<int32> scores(n_check);
+    std::vector<uint32> sources(2 * n_check), sinks(2 * n_check), n_ops(n_check);
+    std::vector<uint8> ops((size_t)n_check * stride);
+    HIP_OK(hipMemcpy(scores.data(), b.d_scores, n_check * 4, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(sources.data(), d_sources, n_check * 8, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(sinks.data(), b.d_sinks, n_check * 8, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(n_ops.data(), d_n_ops, n_check * 4, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(ops.data(), d_ops, ops.size(), hipMemcpyDeviceToHost));
+    HIP_OK(hipFree(d_sources)); HIP_OK(hipFree(d_n_ops)); HIP_OK(hipFree(d_ops));
+
+    static const char letters[] = "ARNDCQEGHILKMFPSTWYVBZX*";
+    const int32 go = scheme.pattern_gap_open(), ge = scheme.pattern_gap_extension();
+    uint32 equal = 0;
+    std::string line_p, line_m, line_t;
+    for (uint32 k = 0; k < n_check; ++k) {
+        const uint8 *pat = &b.pat[(size_t)k * kP], *txt = &b.txt[(size_t)k * kT];
+        uint32 x = sinks[2 * k], y = sinks[2 * k + 1];
+        bool inside = x <= kT && y <= kP && n_ops[k] <= stride;
+        int32 total = 0;
+        uint8 prev = aln::SUBSTITUTION;
+        for (uint32 i = 0; inside && i < n_ops[k]; ++i) {
+            const uint8 op = ops[(size_t)k * stride + i];
+            char cp = '-', ct = '-', cm = ' ';
+            if (op == aln::SUBSTITUTION) {
+                if (x == 0 || y == 0) { inside = false; break; }
+                --x; --y;
+                total += scheme.substitution(x, y, txt[x], pat[y]);
+                cp = letters[pat[y]]; ct = letters[txt[x]]; cm = pat[y] == txt[x] ? '|' : '.';
+            } else if (op == aln::INSERTION) {
+                if (y == 0) { inside = false; break; }
+                --y;
+                total += prev == op ? ge : go;
+                cp = letters[pat[y]];
+            } else {
+                if (x == 0) { inside = false; break; }
+                --x;
+                total += prev == op ? ge : go;
+                ct = letters[txt[x]];
+            }
+            prev = op;
+            if (k == 0) { line_p.insert(line_p.begin(), cp); line_m.insert(line_m.begin(), cm); line_t.insert(line_t.begin(), ct); }
+        }
+        const bool same = inside && x == sources[2 * k] && y == sources[2 * k + 1] && total == scores[k];
+        equal += same;
+        printf("  pair %2u: text %u..%u, pattern %u..%u, %u ops, score %d, replayed %d%s\n", k, sources[2 * k], sinks[2 * k],
+               sources[2 * k + 1], sinks[2 * k + 1], n_ops[k], scores[k], total, same ? "" : "  MISMATCH");
+    }
+    printf("  pair 0:\n    %s\n    %s\n    %s\n", line_p.c_str(), line_m.c_str(), line_t.c_str());
+    printf("  replays equal: %u of %u\n", equal, n_check);
+    return equal == n_check;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -156,6 +238,7 @@ int main(int argc, char **argv) {
                   aln::DeviceThreadBlockScheduler<128, 1>(), n_tests);
         ok &= run("Matrix/T", aln::make_gotoh_aligner<aln::LOCAL, aln::TextBlockingTag>(scoring), scoring, b, true,
                   aln::DeviceThreadBlockScheduler<128, 1>(), n_tests);
+        ok &= run_traceback(scoring, b);
     }
     HIP_OK(hipFree(b.d_pat)); HIP_OK(hipFree(b.d_txt)); HIP_OK(hipFree(b.d_poff)); HIP_OK(hipFree(b.d_toff));
     HIP_OK(hipFree(b.d_scores)); HIP_OK(hipFree(b.d_sinks));
