@@ -227,18 +227,18 @@ static int launch_int32(const Plan &pl, WfFn fn, const WfArgs &A, hipStream_t st
 #ifdef GX_WF16_STAMP
 // Probe builds only (wavefront16.hpp GX_WF16_STAMP; never the library that is benchmarked): with
 // GASALX_STAMP_OUT=FILE the packed launch's waves stamp their phases, and the call waits for the
-// launch and writes the 5 words per wave to FILE (the last launch's; tools/stamp_summary.py reads it).
+// launch and writes the kStampWords words per wave to FILE (the last launch's; tools/stamp_summary.py reads it).
 static hipError_t stamp_begin(uint32_t waves, unsigned long long **buf) {
     *buf = nullptr;
     if (!std::getenv("GASALX_STAMP_OUT")) return hipSuccess;
-    hipError_t e = hipMalloc((void **)buf, (size_t)waves * 5 * 8);
-    if (e == hipSuccess) e = hipMemset(*buf, 0, (size_t)waves * 5 * 8);
+    hipError_t e = hipMalloc((void **)buf, (size_t)waves * kStampWords * 8);
+    if (e == hipSuccess) e = hipMemset(*buf, 0, (size_t)waves * kStampWords * 8);
     if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(gx_wf16_stamp), buf, sizeof *buf);
     return e;
 }
 static hipError_t stamp_end(uint32_t waves, unsigned long long *buf, hipStream_t st) {
     if (!buf) return hipSuccess;
-    std::vector<unsigned long long> h((size_t)waves * 5);
+    std::vector<unsigned long long> h((size_t)waves * kStampWords);
     unsigned long long *none = nullptr;
     hipError_t e = hipStreamSynchronize(st);
     if (e == hipSuccess) e = hipMemcpy(h.data(), buf, h.size() * 8, hipMemcpyDeviceToHost);

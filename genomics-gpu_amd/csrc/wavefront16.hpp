@@ -678,12 +678,14 @@ __host__ __device__ constexpr int wf16_waves(int algo, int R) {
 #ifdef GX_WF16_STAMP
 // Probe builds only (make variants VARIANTS=stamp:-DGX_WF16_STAMP, dispatch.hip stamp_begin): lane 0
 // of every wave stores wall_clock64() at entry, after the block's vote, after the sweep and at exit,
-// then its hardware ids, 5 words per wave at [tile * kWavesPerBlock + wave].  Null: no stamps.
+// then its hardware ids, then the clock on reaching the vote: kStampWords words per wave at
+// [tile * kWavesPerBlock + wave].  Null: no stamps.
+constexpr int kStampWords = 6;
 static __device__ unsigned long long *gx_wf16_stamp;
 #define GX_WF16_STAMP_AT(i)                                                               \
     do {                                                                                  \
         if (gx_wf16_stamp && lane == 0)                                                   \
-            gx_wf16_stamp[((size_t)wf16_bid * kWavesPerBlock + wave) * 5 + (i)] = wall_clock64(); \
+            gx_wf16_stamp[((size_t)wf16_bid * kWavesPerBlock + wave) * kStampWords + (i)] = wall_clock64(); \
     } while (0)
 #else
 #define GX_WF16_STAMP_AT(i) do { } while (0)

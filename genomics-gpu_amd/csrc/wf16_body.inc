@@ -37,7 +37,7 @@
 #ifdef GX_WF16_STAMP
     // HW_ID (wave, SIMD, CU, SE) and XCC_ID of the wave, for the per-SIMD occupancy over time
     if (gx_wf16_stamp && lane == 0)
-        gx_wf16_stamp[((size_t)wf16_bid * kWavesPerBlock + wave) * 5 + 4] =
+        gx_wf16_stamp[((size_t)wf16_bid * kWavesPerBlock + wave) * kStampWords + 4] =
             (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) |
             ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32);
 #endif
@@ -51,6 +51,14 @@
     uint32_t pr[2], xl[2], yl[2], xo[2], yo[2], xpad[2], ypad[2];
     bool valid[2];
     const uint8_t *X = TR ? A.t : A.q, *Y = TR ? A.q : A.t;
+    // The plain LOCAL score kernels run from their first global load to the block's vote at wave
+    // priority 3 and their sweep at 0.  A SIMD's VALU issue goes by priority, then age: at equal
+    // priority a new wave, the youngest of three, builds its tables in the slots two sweeping waves
+    // leave over (a median 61 us from entry to the vote on config 2, 16 us with the raise), and the
+    // SIMD runs with one sweeper for a quarter of its time (profiles/prio/README.md).  A declined
+    // block returns at the raised priority.  The sibling kernels have not been measured with it.
+    constexpr bool PRIO = ALGO_ == WF_LOCAL;
+    if constexpr (PRIO) __builtin_amdgcn_s_setprio(3);
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         const uint32_t idx = pair0 + 2 * slot + h;   // slot; the pair is perm[slot] when sorted
@@ -211,6 +219,7 @@
 #pragma unroll
         for (int h = 0; h < 2; ++h) other |= valid[h] && xpad[h] > (uint32_t)(G * R);
     }
+    GX_WF16_STAMP_AT(5);
     const bool fast = A.fast16 && !A.force_exact && !__syncthreads_or(other);
     if constexpr (TQ) {
         // flags per slot: class launches cover slot ranges that need not align to blocks
@@ -223,6 +232,7 @@
     }
     if (!fast) return;                           // the int32 kernel takes this block
     GX_WF16_STAMP_AT(1);
+    if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
 
     const uint32_t nsteps = ymaxw + G - 1;
     const uint2 *tcol = wl + slot * words;
