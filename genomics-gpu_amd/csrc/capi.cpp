@@ -202,17 +202,22 @@ int hmm_stage_quals(gasalx_engine *eng, const gasalx_hmm_qual_batch *hb, hipStre
     return in.rc;
 }
 
-// nvbio string pair: patterns and texts (one shared text has no offsets).
-int nv_stage_strings(gasalx_engine *eng, uint32_t n, const gasalx_nv_strings *pat, uint64_t pat_words,
-                     const gasalx_nv_strings *txt, uint64_t txt_words, hipStream_t st, gasalx_nv_strings &dp,
-                     gasalx_nv_strings &dt) {
-    dp = *pat;
-    dt = *txt;
+// nvbio string pair: patterns and texts (one shared text has no offsets) as a host form takes them,
+// and their device image with the longest pattern and text (a shared text's length).
+struct NvHostIn { uint32_t n; const gasalx_nv_strings *pat; uint64_t pat_words; const gasalx_nv_strings *txt; uint64_t txt_words; };
+struct NvStaged { gasalx_nv_strings pat, txt; uint32_t max_p, max_t; };
+void nv_host_spans(const NvHostIn &h, NvStaged &s) {
+    s.max_p = max_span(h.pat->offsets, h.n);
+    s.max_t = h.txt->offsets ? max_span(h.txt->offsets, h.n) : h.txt->length;
+}
+int nv_stage_strings(gasalx_engine *eng, const NvHostIn &h, hipStream_t st, NvStaged &s) {
+    s.pat = *h.pat;
+    s.txt = *h.txt;
     Stager in{eng, st};
-    in(B_NV_PW, dp.words, pat_words);
-    in(B_NV_PO, dp.offsets, (size_t)n + 1);
-    in(B_NV_TW, dt.words, txt_words);
-    in(B_NV_TO, dt.offsets, (size_t)n + 1);
+    in(B_NV_PW, s.pat.words, h.pat_words);
+    in(B_NV_PO, s.pat.offsets, (size_t)h.n + 1);
+    in(B_NV_TW, s.txt.words, h.txt_words);
+    in(B_NV_TO, s.txt.offsets, (size_t)h.n + 1);
     return in.rc;
 }
 
@@ -617,12 +622,99 @@ int nv_tb_chunks(gasalx_engine *eng, const gasalx_nv_aligner *al, const gasalx_n
     return GASALX_OK;
 }
 
-// The traceback host forms after staging: the five device outputs reserved, the device form
-// (band 0: the full DP; mat: its substitution-matrix form, NULL otherwise) run on them, the results
-// copied to the caller's arrays `h`.
-int nv_tb_host_run(gasalx_engine *eng, const gasalx_nv_aligner *al, const gasalx_nv_matrix *mat, uint32_t band, uint32_t n,
-                   const gasalx_nv_strings *dp, const gasalx_nv_strings *dt, uint32_t max_p, uint32_t max_t,
-                   const NvTbOut &h, hipStream_t st) {
+// ---- The gasalx_nv_* entry points: each family's call sequence, written once.  An entry point keeps
+//      its own argument test, its pre-checks in their order, and the one gx:: call that is its own; a
+//      new score pair is an output list and a callable, not a copy of its neighbour. ----
+
+int nv_null() { gx::set_error("null argument"); return GASALX_EINVAL; }
+
+// What every host form (and gasalx_nv_matrix_traceback_device) needs of its two string sets, and
+// the traceback host forms of their outputs.
+bool nv_sets_ok(const gasalx_nv_strings *pat, const gasalx_nv_strings *txt) {
+    return pat && txt && pat->words && pat->offsets && txt->words;
+}
+bool nv_tb_out_ok(const NvTbOut &o) { return o.scores && o.sources && o.sinks && o.ops && o.n_ops; }
+
+// A device form's start: enter, then the bounds the caller left zero read back from the offsets.
+enum NvBounds {
+    NV_BOTH,              // the longest pattern and, for per-pair texts, the longest text
+    NV_BOTH_SHARED,       // the same, and one shared text's length replaces the caller's max_t (traceback)
+    NV_PATTERN,           // the longest pattern alone (banded traceback)
+    NV_PATTERN_IF_OFFSETS // the same, unless the pattern set has no offsets to read (the banded scorers)
+};
+int nv_device_enter(gasalx_engine *eng, void *stream, NvBounds which, uint32_t n, const gasalx_nv_strings *pat,
+                    const gasalx_nv_strings *txt, uint32_t *max_p, uint32_t *max_t, hipStream_t *st) {
+    int rc = enter(eng, stream, st);
+    if (rc) return rc;
+    const bool both = which == NV_BOTH || which == NV_BOTH_SHARED;
+    if (which != NV_PATTERN_IF_OFFSETS || pat->offsets)
+        if ((rc = device_max_spans(pat, both ? txt : nullptr, n, *st, max_p, both ? max_t : nullptr))) return rc;
+    if (which == NV_BOTH_SHARED && !txt->offsets) *max_t = txt->length;
+    return GASALX_OK;
+}
+
+// The score host forms: the sets staged, the wanted outputs reserved, launch(staged sets and bounds,
+// the outputs' device pointers in `out`'s order (NULL where the caller's is), stream), the results back.
+// An output: the caller's array (NULL: not wanted), the engine buffer that stages it, bytes per pair.
+struct NvOut { void *host; Buf buf; size_t per_pair; };
+template <class Launch>
+int nv_score_host_run(gasalx_engine *eng, const NvHostIn &h, const NvOut (&out)[2], Launch launch) {
+    if (h.n == 0) return GASALX_OK;
+    hipStream_t st;
+    int rc = enter(eng, nullptr, &st);
+    if (rc) return rc;
+    NvStaged s;
+    nv_host_spans(h, s);
+    if ((rc = nv_stage_strings(eng, h, st, s))) return rc;
+    void *d[2] = {nullptr, nullptr};
+    for (int k = 0; k < 2; k++)
+        if (out[k].host) {
+            CK(eng->buf[out[k].buf].reserve(h.n * out[k].per_pair));
+            d[k] = eng->buf[out[k].buf].p;
+        }
+    rc = launch(s, d, st);
+    return host_finish(st, rc, {{out[0].host, d[0], h.n * out[0].per_pair}, {out[1].host, d[1], h.n * out[1].per_pair}});
+}
+
+// Bytes per pair of the traceback workspace: the full DP's flags of every cell and its one DP row,
+// the banded form's flags (gasalx_nv_*traceback_workspace and the device forms' reserves).
+uint64_t nv_tb_dir_bytes(uint32_t max_p, uint32_t max_t) { return (uint64_t)((max_p + 7) / 8) * 8 * max_t; }
+uint64_t nv_tb_row_bytes(uint32_t max_t) { return (uint64_t)max_t * 8; }
+uint64_t nv_btb_dir_bytes(uint32_t max_p, uint32_t band) { return (uint64_t)max_p * ((band + 3) / 4) * 4; }
+
+// The full-DP traceback device forms (mat: the substitution-matrix form, NULL otherwise) after their
+// argument tests; `ranged` is the aligner nv_tb_checks takes.
+int nv_tb_device_run(gasalx_engine *eng, const gasalx_nv_aligner *al, const gasalx_nv_matrix *mat,
+                     const gasalx_nv_aligner *ranged, uint32_t n, const gasalx_nv_strings *pat,
+                     const gasalx_nv_strings *txt, uint32_t max_p, uint32_t max_t, const NvTbOut &o, void *stream) {
+    if (n == 0) return GASALX_OK;
+    hipStream_t st;
+    int rc = nv_device_enter(eng, stream, NV_BOTH_SHARED, n, pat, txt, &max_p, &max_t, &st);
+    if (rc) return rc;
+    if ((rc = nv_tb_checks(ranged, max_p, max_t, o.ops_stride))) return rc;
+    // the batch runs in chunks whose workspace (flags of every cell + one row per pair) stays
+    // within nv_tb_budget() (ADVICE r05: 1 M 150 x 182 pairs would otherwise take 28 GB of HBM)
+    const uint32_t chunk = (uint32_t)nv_tb_chunk(n, gasalx_nv_traceback_workspace(max_p, max_t, 1));
+    CK(eng->buf[B_NV_DIR].reserve((size_t)nv_tb_dir_bytes(max_p, max_t) * chunk + 64));
+    CK(eng->buf[B_NV_ROW].reserve((size_t)nv_tb_row_bytes(max_t) * chunk + 64));
+    return nv_tb_chunks(eng, al, mat, 0, n, pat, txt, max_p, max_t, o, chunk, st);
+}
+
+// The traceback host forms after their argument tests (band 0: the full DP, refused by nv_tb_checks
+// over `ranged` before anything is staged; mat: its substitution-matrix form, NULL otherwise; the
+// banded form has made its checks): the sets staged, the five device outputs reserved, the device
+// form run on them, the results copied to the caller's arrays `h`.
+int nv_tb_host_run(gasalx_engine *eng, const gasalx_nv_aligner *al, const gasalx_nv_matrix *mat, uint32_t band,
+                   const gasalx_nv_aligner *ranged, const NvHostIn &in, const NvTbOut &h) {
+    const uint32_t n = in.n;
+    if (n == 0) return GASALX_OK;
+    hipStream_t st;
+    int rc = enter(eng, nullptr, &st);
+    if (rc) return rc;
+    NvStaged d;
+    nv_host_spans(in, d);
+    if (!band && (rc = nv_tb_checks(ranged, d.max_p, d.max_t, h.ops_stride))) return rc;
+    if ((rc = nv_stage_strings(eng, in, st, d))) return rc;
     gx::DevBuf &s = eng->buf[B_NV_S], &src = eng->buf[B_NV_SRC], &snk = eng->buf[B_NV_SNK], &ops = eng->buf[B_NV_OPS],
                &nops = eng->buf[B_NV_NOPS];
     CK(s.reserve((size_t)n * 4));
@@ -630,17 +722,40 @@ int nv_tb_host_run(gasalx_engine *eng, const gasalx_nv_aligner *al, const gasalx
     CK(snk.reserve((size_t)n * 8));
     CK(ops.reserve((size_t)n * h.ops_stride + 64));
     CK(nops.reserve((size_t)n * 4));
-    const int rc =
-        band ? gasalx_nv_banded_traceback_device(eng, al, band, n, dp, dt, max_p, s.as<int32_t>(), src.as<uint32_t>(),
-                                                 snk.as<uint32_t>(), ops.as<uint8_t>(), h.ops_stride, nops.as<uint32_t>(), st)
-        : mat ? gasalx_nv_matrix_traceback_device(eng, al, mat, n, dp, dt, max_p, max_t, s.as<int32_t>(),
+    rc = band ? gasalx_nv_banded_traceback_device(eng, al, band, n, &d.pat, &d.txt, d.max_p, s.as<int32_t>(),
                                                   src.as<uint32_t>(), snk.as<uint32_t>(), ops.as<uint8_t>(), h.ops_stride,
                                                   nops.as<uint32_t>(), st)
-              : gasalx_nv_traceback_device(eng, al, n, dp, dt, max_p, max_t, s.as<int32_t>(), src.as<uint32_t>(),
-                                           snk.as<uint32_t>(), ops.as<uint8_t>(), h.ops_stride, nops.as<uint32_t>(), st);
+         : mat ? gasalx_nv_matrix_traceback_device(eng, al, mat, n, &d.pat, &d.txt, d.max_p, d.max_t, s.as<int32_t>(),
+                                                   src.as<uint32_t>(), snk.as<uint32_t>(), ops.as<uint8_t>(), h.ops_stride,
+                                                   nops.as<uint32_t>(), st)
+               : gasalx_nv_traceback_device(eng, al, n, &d.pat, &d.txt, d.max_p, d.max_t, s.as<int32_t>(),
+                                            src.as<uint32_t>(), snk.as<uint32_t>(), ops.as<uint8_t>(), h.ops_stride,
+                                            nops.as<uint32_t>(), st);
     return host_finish(st, rc, {{h.scores, s.p, (size_t)n * 4}, {h.sources, src.p, (size_t)n * 8},
                                 {h.sinks, snk.p, (size_t)n * 8}, {h.ops, ops.p, (size_t)n * h.ops_stride},
                                 {h.n_ops, nops.p, (size_t)n * 4}});
+}
+
+// The matrix traceback forms' checks after the null arguments: the aligner and the table's size, the
+// table and the symbol bits (before anything is read back or staged); `ranged` is then the aligner
+// nv_tb_checks takes, the largest |entry| standing for match and mismatch (the aligner's own match,
+// mismatch, deletion and insertion are never read)
+int nv_mtb_checks(const gasalx_nv_aligner *al, const gasalx_nv_matrix *mat, const gasalx_nv_strings *pat,
+                  const gasalx_nv_strings *txt, gasalx_nv_aligner *ranged) {
+    int32_t mag = 0;
+    if (int rc = gx::nv_matrix_traceback_check(*al, *mat, *pat, *txt, &mag)) return rc;
+    *ranged = {al->aligner, al->type, mag, mag, al->gap_open, al->gap_ext, 0, 0};
+    return GASALX_OK;
+}
+
+// The describe functions: name(s) puts the plan's name into s or returns the code that refuses it.
+template <class Name>
+int nv_describe(bool args_ok, char *buf, uint32_t buf_len, Name name) {
+    if (!args_ok || !buf || buf_len == 0) return nv_null();
+    std::string s;
+    if (int rc = name(s)) return rc;
+    std::snprintf(buf, buf_len, "%s", s.c_str());
+    return GASALX_OK;
 }
 
 }  // namespace
@@ -1037,250 +1152,168 @@ int gasalx_pairhmm_quals_log10_host(gasalx_engine *eng, const gasalx_hmm_qual_ba
 int gasalx_nv_score_device(gasalx_engine *eng, const gasalx_nv_aligner *al, uint32_t n, const gasalx_nv_strings *pat,
                            const gasalx_nv_strings *txt, int32_t *scores, int16_t *scores16, uint32_t max_p,
                            uint32_t max_t, void *stream) {
-    if (!eng || !al || !pat || !txt) { gx::set_error("null argument"); return GASALX_EINVAL; }
+    if (!eng || !al || !pat || !txt) return nv_null();
     hipStream_t st;
-    int rc = enter(eng, stream, &st);
-    if (rc) return rc;
-    if ((rc = device_max_spans(pat, txt, n, st, &max_p, &max_t))) return rc;
+    if (int rc = nv_device_enter(eng, stream, NV_BOTH, n, pat, txt, &max_p, &max_t, &st)) return rc;
     return gx::nv_score_device(*al, n, *pat, *txt, scores, scores16, max_p, max_t, st);
 }
 
 int gasalx_nv_describe_plan(const gasalx_nv_aligner *al, uint32_t max_p, uint32_t max_t, int per_pair,
                             uint32_t text_bits, char *buf, uint32_t buf_len) {
-    if (!al || !buf || buf_len == 0) { gx::set_error("null argument"); return GASALX_EINVAL; }
-    std::snprintf(buf, buf_len, "%s", gx::nv_plan_name(*al, max_p, max_t, per_pair != 0, text_bits).c_str());
-    return GASALX_OK;
+    return nv_describe(al, buf, buf_len, [&](std::string &s) {
+        s = gx::nv_plan_name(*al, max_p, max_t, per_pair != 0, text_bits);
+        return GASALX_OK;
+    });
 }
 
 int gasalx_nv_score_host(gasalx_engine *eng, const gasalx_nv_aligner *al, uint32_t n, const gasalx_nv_strings *pat,
                          uint64_t pat_words, const gasalx_nv_strings *txt, uint64_t txt_words, int32_t *scores,
                          int16_t *scores16) {
-    if (!eng || !al || !pat || !txt || !pat->words || !pat->offsets || !txt->words || (!scores && !scores16)) {
-        gx::set_error("null argument");
-        return GASALX_EINVAL;
-    }
-    if (n == 0) return GASALX_OK;
-    hipStream_t st;
-    int rc = enter(eng, nullptr, &st);
-    if (rc) return rc;
-    const uint32_t max_p = max_span(pat->offsets, n);
-    const uint32_t max_t = txt->offsets ? max_span(txt->offsets, n) : txt->length;
-    gasalx_nv_strings dp, dt;
-    if ((rc = nv_stage_strings(eng, n, pat, pat_words, txt, txt_words, st, dp, dt))) return rc;
-    int32_t *ds = nullptr;
-    int16_t *ds16 = nullptr;
-    if (scores) { CK(eng->buf[B_NV_S].reserve((size_t)n * 4)); ds = eng->buf[B_NV_S].as<int32_t>(); }
-    if (scores16) { CK(eng->buf[B_NV_S16].reserve((size_t)n * 2)); ds16 = eng->buf[B_NV_S16].as<int16_t>(); }
-    rc = gx::nv_score_device(*al, n, dp, dt, ds, ds16, max_p, max_t, st);
-    return host_finish(st, rc, {{scores, ds, (size_t)n * 4}, {scores16, ds16, (size_t)n * 2}});
+    if (!eng || !al || !nv_sets_ok(pat, txt) || (!scores && !scores16)) return nv_null();
+    return nv_score_host_run(eng, {n, pat, pat_words, txt, txt_words}, {{scores, B_NV_S, 4}, {scores16, B_NV_S16, 2}},
+                             [&](const NvStaged &s, void *const *d, hipStream_t st) {
+                                 return gx::nv_score_device(*al, n, s.pat, s.txt, (int32_t *)d[0], (int16_t *)d[1],
+                                                            s.max_p, s.max_t, st);
+                             });
 }
 
 int gasalx_nv_score_sinks_device(gasalx_engine *eng, const gasalx_nv_aligner *al, uint32_t n,
                                  const gasalx_nv_strings *pat, const gasalx_nv_strings *txt, int32_t *scores,
                                  uint32_t *sinks, uint32_t max_p, uint32_t max_t, void *stream) {
-    if (!eng || !al || !pat || !txt) { gx::set_error("null argument"); return GASALX_EINVAL; }
+    if (!eng || !al || !pat || !txt) return nv_null();
     hipStream_t st;
-    int rc = enter(eng, stream, &st);
-    if (rc) return rc;
-    if ((rc = device_max_spans(pat, txt, n, st, &max_p, &max_t))) return rc;
+    if (int rc = nv_device_enter(eng, stream, NV_BOTH, n, pat, txt, &max_p, &max_t, &st)) return rc;
     return gx::nv_score_sinks_device(*al, n, *pat, *txt, scores, sinks, max_p, max_t, st);
 }
 
 int gasalx_nv_describe_sinks_plan(const gasalx_nv_aligner *al, uint32_t max_p, uint32_t max_t, int per_pair,
                                   uint32_t text_bits, char *buf, uint32_t buf_len) {
-    if (!al || !buf || buf_len == 0) { gx::set_error("null argument"); return GASALX_EINVAL; }
-    std::snprintf(buf, buf_len, "%s", gx::nv_sinks_plan_name(*al, max_p, max_t, per_pair != 0, text_bits).c_str());
-    return GASALX_OK;
+    return nv_describe(al, buf, buf_len, [&](std::string &s) {
+        s = gx::nv_sinks_plan_name(*al, max_p, max_t, per_pair != 0, text_bits);
+        return GASALX_OK;
+    });
 }
 
 int gasalx_nv_score_sinks_host(gasalx_engine *eng, const gasalx_nv_aligner *al, uint32_t n,
                                const gasalx_nv_strings *pat, uint64_t pat_words, const gasalx_nv_strings *txt,
                                uint64_t txt_words, int32_t *scores, uint32_t *sinks) {
-    if (!eng || !al || !pat || !txt || !pat->words || !pat->offsets || !txt->words || (!scores && !sinks)) {
-        gx::set_error("null argument");
-        return GASALX_EINVAL;
-    }
-    if (n == 0) return GASALX_OK;
-    hipStream_t st;
-    int rc = enter(eng, nullptr, &st);
-    if (rc) return rc;
-    const uint32_t max_p = max_span(pat->offsets, n);
-    const uint32_t max_t = txt->offsets ? max_span(txt->offsets, n) : txt->length;
-    gasalx_nv_strings dp, dt;
-    if ((rc = nv_stage_strings(eng, n, pat, pat_words, txt, txt_words, st, dp, dt))) return rc;
-    int32_t *ds = nullptr;
-    uint32_t *dk = nullptr;
-    if (scores) { CK(eng->buf[B_NV_S].reserve((size_t)n * 4)); ds = eng->buf[B_NV_S].as<int32_t>(); }
-    if (sinks) { CK(eng->buf[B_NV_SNK].reserve((size_t)n * 8)); dk = eng->buf[B_NV_SNK].as<uint32_t>(); }
-    rc = gx::nv_score_sinks_device(*al, n, dp, dt, ds, dk, max_p, max_t, st);
-    return host_finish(st, rc, {{scores, ds, (size_t)n * 4}, {sinks, dk, (size_t)n * 8}});
+    if (!eng || !al || !nv_sets_ok(pat, txt) || (!scores && !sinks)) return nv_null();
+    return nv_score_host_run(eng, {n, pat, pat_words, txt, txt_words}, {{scores, B_NV_S, 4}, {sinks, B_NV_SNK, 8}},
+                             [&](const NvStaged &s, void *const *d, hipStream_t st) {
+                                 return gx::nv_score_sinks_device(*al, n, s.pat, s.txt, (int32_t *)d[0], (uint32_t *)d[1],
+                                                                  s.max_p, s.max_t, st);
+                             });
 }
 
 int gasalx_nv_matrix_score_device(gasalx_engine *eng, const gasalx_nv_aligner *al, const gasalx_nv_matrix *mat,
                                   uint32_t n, const gasalx_nv_strings *pat, const gasalx_nv_strings *txt,
                                   int32_t *scores, uint32_t *sinks, uint32_t max_p, uint32_t max_t, void *stream) {
-    if (!eng || !al || !mat || !pat || !txt) { gx::set_error("null argument"); return GASALX_EINVAL; }
+    if (!eng || !al || !mat || !pat || !txt) return nv_null();
     hipStream_t st;
-    int rc = enter(eng, stream, &st);
-    if (rc) return rc;
-    if ((rc = device_max_spans(pat, txt, n, st, &max_p, &max_t))) return rc;
+    if (int rc = nv_device_enter(eng, stream, NV_BOTH, n, pat, txt, &max_p, &max_t, &st)) return rc;
     return gx::nv_matrix_score_device(*al, *mat, n, *pat, *txt, scores, sinks, max_p, max_t, st);
 }
 
 int gasalx_nv_describe_matrix_plan(const gasalx_nv_aligner *al, uint32_t matrix_n, uint32_t max_p, uint32_t max_t,
                                    int per_pair, int want_sinks, char *buf, uint32_t buf_len) {
-    if (!al || !buf || buf_len == 0) { gx::set_error("null argument"); return GASALX_EINVAL; }
-    std::string name;
-    if (int rc = gx::nv_matrix_plan_name(*al, matrix_n, max_p, max_t, per_pair != 0, want_sinks != 0, name)) return rc;
-    std::snprintf(buf, buf_len, "%s", name.c_str());
-    return GASALX_OK;
+    return nv_describe(al, buf, buf_len, [&](std::string &s) {
+        return gx::nv_matrix_plan_name(*al, matrix_n, max_p, max_t, per_pair != 0, want_sinks != 0, s);
+    });
 }
 
 int gasalx_nv_matrix_score_host(gasalx_engine *eng, const gasalx_nv_aligner *al, const gasalx_nv_matrix *mat,
                                 uint32_t n, const gasalx_nv_strings *pat, uint64_t pat_words,
                                 const gasalx_nv_strings *txt, uint64_t txt_words, int32_t *scores, uint32_t *sinks) {
-    if (!eng || !al || !mat || !pat || !txt || !pat->words || !pat->offsets || !txt->words || (!scores && !sinks)) {
-        gx::set_error("null argument");
-        return GASALX_EINVAL;
-    }
-    if (n == 0) return GASALX_OK;
-    hipStream_t st;
-    int rc = enter(eng, nullptr, &st);
-    if (rc) return rc;
-    const uint32_t max_p = max_span(pat->offsets, n);
-    const uint32_t max_t = txt->offsets ? max_span(txt->offsets, n) : txt->length;
-    gasalx_nv_strings dp, dt;
-    if ((rc = nv_stage_strings(eng, n, pat, pat_words, txt, txt_words, st, dp, dt))) return rc;
-    int32_t *ds = nullptr;
-    uint32_t *dk = nullptr;
-    if (scores) { CK(eng->buf[B_NV_S].reserve((size_t)n * 4)); ds = eng->buf[B_NV_S].as<int32_t>(); }
-    if (sinks) { CK(eng->buf[B_NV_SNK].reserve((size_t)n * 8)); dk = eng->buf[B_NV_SNK].as<uint32_t>(); }
-    rc = gx::nv_matrix_score_device(*al, *mat, n, dp, dt, ds, dk, max_p, max_t, st);
-    return host_finish(st, rc, {{scores, ds, (size_t)n * 4}, {sinks, dk, (size_t)n * 8}});
+    if (!eng || !al || !mat || !nv_sets_ok(pat, txt) || (!scores && !sinks)) return nv_null();
+    return nv_score_host_run(eng, {n, pat, pat_words, txt, txt_words}, {{scores, B_NV_S, 4}, {sinks, B_NV_SNK, 8}},
+                             [&](const NvStaged &s, void *const *d, hipStream_t st) {
+                                 return gx::nv_matrix_score_device(*al, *mat, n, s.pat, s.txt, (int32_t *)d[0],
+                                                                   (uint32_t *)d[1], s.max_p, s.max_t, st);
+                             });
 }
 
 int gasalx_nv_banded_score_device(gasalx_engine *eng, const gasalx_nv_aligner *al, uint32_t band, uint32_t n,
                                   const gasalx_nv_strings *pat, const gasalx_nv_strings *txt, int32_t *scores,
                                   uint32_t max_p, void *stream) {
-    if (!eng || !al || !pat || !txt) { gx::set_error("null argument"); return GASALX_EINVAL; }
+    if (!eng || !al || !pat || !txt) return nv_null();
     hipStream_t st;
-    int rc = enter(eng, stream, &st);
-    if (rc) return rc;
-    if (pat->offsets && (rc = device_max_spans(pat, nullptr, n, st, &max_p, nullptr))) return rc;
+    if (int rc = nv_device_enter(eng, stream, NV_PATTERN_IF_OFFSETS, n, pat, txt, &max_p, nullptr, &st)) return rc;
     return gx::nv_banded_score_device(*al, band, n, *pat, *txt, scores, st, max_p);
 }
 
 int gasalx_nv_banded_score_host(gasalx_engine *eng, const gasalx_nv_aligner *al, uint32_t band, uint32_t n,
                                 const gasalx_nv_strings *pat, uint64_t pat_words, const gasalx_nv_strings *txt,
                                 uint64_t txt_words, int32_t *scores) {
-    if (!eng || !al || !pat || !txt || !pat->words || !pat->offsets || !txt->words || !scores) {
-        gx::set_error("null argument");
-        return GASALX_EINVAL;
-    }
+    if (!eng || !al || !nv_sets_ok(pat, txt) || !scores) return nv_null();
     if (band < 2 || band > 32) { gx::set_error("band length must be 2..32"); return GASALX_EINVAL; }
-    if (n == 0) return GASALX_OK;
-    hipStream_t st;
-    int rc = enter(eng, nullptr, &st);
-    if (rc) return rc;
-    gasalx_nv_strings dp, dt;
-    if ((rc = nv_stage_strings(eng, n, pat, pat_words, txt, txt_words, st, dp, dt))) return rc;
-    gx::DevBuf &ds = eng->buf[B_NV_S];
-    CK(ds.reserve((size_t)n * 4));
-    rc = gx::nv_banded_score_device(*al, band, n, dp, dt, ds.as<int32_t>(), st, max_span(pat->offsets, n));
-    return host_finish(st, rc, {{scores, ds.p, (size_t)n * 4}});
+    return nv_score_host_run(eng, {n, pat, pat_words, txt, txt_words}, {{scores, B_NV_S, 4}, {nullptr, B_NV_SNK, 0}},
+                             [&](const NvStaged &s, void *const *d, hipStream_t st) {
+                                 return gx::nv_banded_score_device(*al, band, n, s.pat, s.txt, (int32_t *)d[0], st, s.max_p);
+                             });
 }
 
 int gasalx_nv_banded_score_sinks_device(gasalx_engine *eng, const gasalx_nv_aligner *al, uint32_t band, uint32_t n,
                                         const gasalx_nv_strings *pat, const gasalx_nv_strings *txt, int32_t *scores,
                                         uint32_t *sinks, uint32_t max_p, void *stream) {
-    if (!eng || !al || !pat || !txt) { gx::set_error("null argument"); return GASALX_EINVAL; }
+    if (!eng || !al || !pat || !txt) return nv_null();
     hipStream_t st;
-    int rc = enter(eng, stream, &st);
-    if (rc) return rc;
-    if (pat->offsets && (rc = device_max_spans(pat, nullptr, n, st, &max_p, nullptr))) return rc;
+    if (int rc = nv_device_enter(eng, stream, NV_PATTERN_IF_OFFSETS, n, pat, txt, &max_p, nullptr, &st)) return rc;
     return gx::nv_banded_score_sinks_device(*al, band, n, *pat, *txt, scores, sinks, st, max_p);
 }
 
 int gasalx_nv_describe_banded_sinks_plan(const gasalx_nv_aligner *al, uint32_t band, uint32_t max_p,
                                          uint32_t text_bits, char *buf, uint32_t buf_len) {
-    if (!al || !buf || buf_len == 0) { gx::set_error("null argument"); return GASALX_EINVAL; }
-    std::string name;
-    if (int rc = gx::nv_banded_sinks_plan_name(*al, band, max_p, text_bits, name)) return rc;
-    std::snprintf(buf, buf_len, "%s", name.c_str());
-    return GASALX_OK;
+    return nv_describe(al, buf, buf_len, [&](std::string &s) {
+        return gx::nv_banded_sinks_plan_name(*al, band, max_p, text_bits, s);
+    });
 }
 
 int gasalx_nv_banded_score_sinks_host(gasalx_engine *eng, const gasalx_nv_aligner *al, uint32_t band, uint32_t n,
                                       const gasalx_nv_strings *pat, uint64_t pat_words, const gasalx_nv_strings *txt,
                                       uint64_t txt_words, int32_t *scores, uint32_t *sinks) {
-    if (!eng || !al || !pat || !txt || !pat->words || !pat->offsets || !txt->words || (!scores && !sinks)) {
-        gx::set_error("null argument");
-        return GASALX_EINVAL;
-    }
+    if (!eng || !al || !nv_sets_ok(pat, txt) || (!scores && !sinks)) return nv_null();
     if (band < 2 || band > 32) { gx::set_error("band length must be 2..32"); return GASALX_EINVAL; }
-    if (n == 0) return GASALX_OK;
-    hipStream_t st;
-    int rc = enter(eng, nullptr, &st);
-    if (rc) return rc;
-    gasalx_nv_strings dp, dt;
-    if ((rc = nv_stage_strings(eng, n, pat, pat_words, txt, txt_words, st, dp, dt))) return rc;
-    int32_t *ds = nullptr;
-    uint32_t *dk = nullptr;
-    if (scores) { CK(eng->buf[B_NV_S].reserve((size_t)n * 4)); ds = eng->buf[B_NV_S].as<int32_t>(); }
-    if (sinks) { CK(eng->buf[B_NV_SNK].reserve((size_t)n * 8)); dk = eng->buf[B_NV_SNK].as<uint32_t>(); }
-    rc = gx::nv_banded_score_sinks_device(*al, band, n, dp, dt, ds, dk, st, max_span(pat->offsets, n));
-    return host_finish(st, rc, {{scores, ds, (size_t)n * 4}, {sinks, dk, (size_t)n * 8}});
+    return nv_score_host_run(eng, {n, pat, pat_words, txt, txt_words}, {{scores, B_NV_S, 4}, {sinks, B_NV_SNK, 8}},
+                             [&](const NvStaged &s, void *const *d, hipStream_t st) {
+                                 return gx::nv_banded_score_sinks_device(*al, band, n, s.pat, s.txt, (int32_t *)d[0],
+                                                                         (uint32_t *)d[1], st, s.max_p);
+                             });
 }
 
 int gasalx_nv_banded_myers_device(gasalx_engine *eng, int32_t type, uint32_t alphabet, uint32_t band, uint32_t n,
                                   const gasalx_nv_strings *pat, const gasalx_nv_strings *txt, int32_t *scores,
                                   uint32_t *sinks, uint32_t max_p, void *stream) {
     (void)max_p;   // the kernel has no value window to size: the bound is not needed, nothing is read back
-    if (!eng || !pat || !txt) { gx::set_error("null argument"); return GASALX_EINVAL; }
+    if (!eng || !pat || !txt) return nv_null();
     hipStream_t st;
-    int rc = enter(eng, stream, &st);
-    if (rc) return rc;
+    if (int rc = enter(eng, stream, &st)) return rc;
     return gx::nv_banded_myers_device(type, alphabet, band, n, *pat, *txt, scores, sinks, st);
 }
 
 int gasalx_nv_describe_myers_plan(int32_t type, uint32_t alphabet, uint32_t band, char *buf, uint32_t buf_len) {
-    if (!buf || buf_len == 0) { gx::set_error("null argument"); return GASALX_EINVAL; }
-    std::string name;
-    if (int rc = gx::nv_myers_plan_name(type, alphabet, band, name)) return rc;
-    std::snprintf(buf, buf_len, "%s", name.c_str());
-    return GASALX_OK;
+    return nv_describe(true, buf, buf_len, [&](std::string &s) { return gx::nv_myers_plan_name(type, alphabet, band, s); });
 }
 
 int gasalx_nv_banded_myers_host(gasalx_engine *eng, int32_t type, uint32_t alphabet, uint32_t band, uint32_t n,
                                 const gasalx_nv_strings *pat, uint64_t pat_words, const gasalx_nv_strings *txt,
                                 uint64_t txt_words, int32_t *scores, uint32_t *sinks) {
-    if (!eng || !pat || !txt || !pat->words || !pat->offsets || !txt->words || (!scores && !sinks)) {
-        gx::set_error("null argument");
-        return GASALX_EINVAL;
-    }
+    if (!eng || !nv_sets_ok(pat, txt) || (!scores && !sinks)) return nv_null();
     // refused before anything is staged, with the device path's own codes and texts
     std::string name;
     if (int rc = gx::nv_myers_plan_name(type, alphabet, band, name)) return rc;
-    if (n == 0) return GASALX_OK;
-    hipStream_t st;
-    int rc = enter(eng, nullptr, &st);
-    if (rc) return rc;
-    gasalx_nv_strings dp, dt;
-    if ((rc = nv_stage_strings(eng, n, pat, pat_words, txt, txt_words, st, dp, dt))) return rc;
-    int32_t *ds = nullptr;
-    uint32_t *dk = nullptr;
-    if (scores) { CK(eng->buf[B_NV_S].reserve((size_t)n * 4)); ds = eng->buf[B_NV_S].as<int32_t>(); }
-    if (sinks) { CK(eng->buf[B_NV_SNK].reserve((size_t)n * 8)); dk = eng->buf[B_NV_SNK].as<uint32_t>(); }
-    rc = gx::nv_banded_myers_device(type, alphabet, band, n, dp, dt, ds, dk, st);
-    return host_finish(st, rc, {{scores, ds, (size_t)n * 4}, {sinks, dk, (size_t)n * 8}});
+    return nv_score_host_run(eng, {n, pat, pat_words, txt, txt_words}, {{scores, B_NV_S, 4}, {sinks, B_NV_SNK, 8}},
+                             [&](const NvStaged &s, void *const *d, hipStream_t st) {
+                                 return gx::nv_banded_myers_device(type, alphabet, band, n, s.pat, s.txt, (int32_t *)d[0],
+                                                                   (uint32_t *)d[1], st);
+                             });
 }
 
 uint64_t gasalx_nv_traceback_workspace(uint32_t max_p, uint32_t max_t, uint32_t n) {
-    const uint64_t per = (uint64_t)((max_p + 7) / 8) * 8 * max_t + (uint64_t)max_t * 8;
+    const uint64_t per = nv_tb_dir_bytes(max_p, max_t) + nv_tb_row_bytes(max_t);
     return per * nv_tb_chunk(n, per) + 128;
 }
 uint64_t gasalx_nv_banded_traceback_workspace(uint32_t max_p, uint32_t band, uint32_t n) {
-    const uint64_t per = (uint64_t)max_p * ((band + 3) / 4) * 4;
+    const uint64_t per = nv_btb_dir_bytes(max_p, band);
     return per * nv_tb_chunk(n, per) + 64;
 }
 
@@ -1288,52 +1321,17 @@ int gasalx_nv_traceback_device(gasalx_engine *eng, const gasalx_nv_aligner *al, 
                                const gasalx_nv_strings *pat, const gasalx_nv_strings *txt, uint32_t max_p,
                                uint32_t max_t, int32_t *scores, uint32_t *sources, uint32_t *sinks, uint8_t *ops,
                                uint32_t ops_stride, uint32_t *n_ops, void *stream) {
-    if (!eng || !al || !pat || !txt) { gx::set_error("null argument"); return GASALX_EINVAL; }
-    if (n == 0) return GASALX_OK;
-    hipStream_t st;
-    int rc = enter(eng, stream, &st);
-    if (rc) return rc;
-    if ((rc = device_max_spans(pat, txt, n, st, &max_p, &max_t))) return rc;
-    if (!txt->offsets) max_t = txt->length;
-    if ((rc = nv_tb_checks(al, max_p, max_t, ops_stride))) return rc;
-    // the batch runs in chunks whose workspace (flags of every cell + one row per pair) stays
-    // within nv_tb_budget() (ADVICE r05: 1 M 150 x 182 pairs would otherwise take 28 GB of HBM)
-    const uint32_t chunk = (uint32_t)nv_tb_chunk(n, gasalx_nv_traceback_workspace(max_p, max_t, 1));
-    CK(eng->buf[B_NV_DIR].reserve((size_t)((max_p + 7) / 8) * 8 * max_t * chunk + 64));
-    CK(eng->buf[B_NV_ROW].reserve((size_t)max_t * chunk * 8 + 64));
-    return nv_tb_chunks(eng, al, nullptr, 0, n, pat, txt, max_p, max_t, {scores, sources, sinks, ops, ops_stride, n_ops}, chunk, st);
+    if (!eng || !al || !pat || !txt) return nv_null();
+    return nv_tb_device_run(eng, al, nullptr, al, n, pat, txt, max_p, max_t, {scores, sources, sinks, ops, ops_stride, n_ops},
+                            stream);
 }
 
 int gasalx_nv_traceback_host(gasalx_engine *eng, const gasalx_nv_aligner *al, uint32_t n, const gasalx_nv_strings *pat,
                              uint64_t pat_words, const gasalx_nv_strings *txt, uint64_t txt_words, int32_t *scores,
                              uint32_t *sources, uint32_t *sinks, uint8_t *ops, uint32_t ops_stride, uint32_t *n_ops) {
-    if (!eng || !al || !pat || !txt || !pat->words || !pat->offsets || !txt->words || !scores || !sources || !sinks ||
-        !ops || !n_ops) {
-        gx::set_error("null argument");
-        return GASALX_EINVAL;
-    }
-    if (n == 0) return GASALX_OK;
-    hipStream_t st;
-    int rc = enter(eng, nullptr, &st);
-    if (rc) return rc;
-    const uint32_t max_p = max_span(pat->offsets, n);
-    const uint32_t max_t = txt->offsets ? max_span(txt->offsets, n) : txt->length;
-    if ((rc = nv_tb_checks(al, max_p, max_t, ops_stride))) return rc;
-    gasalx_nv_strings dp, dt;
-    if ((rc = nv_stage_strings(eng, n, pat, pat_words, txt, txt_words, st, dp, dt))) return rc;
-    return nv_tb_host_run(eng, al, nullptr, 0, n, &dp, &dt, max_p, max_t, {scores, sources, sinks, ops, ops_stride, n_ops}, st);
-}
-
-// The matrix form's checks after the null arguments: the aligner and the table's size, the table and
-// the symbol bits (before anything is read back or staged); `ranged` is then the aligner nv_tb_checks
-// takes, the largest |entry| standing for match and mismatch (the aligner's own match, mismatch,
-// deletion and insertion are never read)
-static int nv_mtb_checks(const gasalx_nv_aligner *al, const gasalx_nv_matrix *mat, const gasalx_nv_strings *pat,
-                         const gasalx_nv_strings *txt, gasalx_nv_aligner *ranged) {
-    int32_t mag = 0;
-    if (int rc = gx::nv_matrix_traceback_check(*al, *mat, *pat, *txt, &mag)) return rc;
-    *ranged = {al->aligner, al->type, mag, mag, al->gap_open, al->gap_ext, 0, 0};
-    return GASALX_OK;
+    const NvTbOut out = {scores, sources, sinks, ops, ops_stride, n_ops};
+    if (!eng || !al || !nv_sets_ok(pat, txt) || !nv_tb_out_ok(out)) return nv_null();
+    return nv_tb_host_run(eng, al, nullptr, 0, al, {n, pat, pat_words, txt, txt_words}, out);
 }
 
 int gasalx_nv_matrix_traceback_device(gasalx_engine *eng, const gasalx_nv_aligner *al, const gasalx_nv_matrix *mat,
@@ -1341,26 +1339,11 @@ int gasalx_nv_matrix_traceback_device(gasalx_engine *eng, const gasalx_nv_aligne
                                       uint32_t max_p, uint32_t max_t, int32_t *scores, uint32_t *sources,
                                       uint32_t *sinks, uint8_t *ops, uint32_t ops_stride, uint32_t *n_ops,
                                       void *stream) {
-    if (!eng || !al || !mat || !pat || !txt || !pat->words || !pat->offsets || !txt->words || !scores || !sources ||
-        !sinks || !ops || !n_ops) {
-        gx::set_error("null argument");
-        return GASALX_EINVAL;
-    }
+    const NvTbOut out = {scores, sources, sinks, ops, ops_stride, n_ops};
+    if (!eng || !al || !mat || !nv_sets_ok(pat, txt) || !nv_tb_out_ok(out)) return nv_null();
     gasalx_nv_aligner ranged;
-    int rc = nv_mtb_checks(al, mat, pat, txt, &ranged);
-    if (rc) return rc;
-    if (n == 0) return GASALX_OK;
-    hipStream_t st;
-    if ((rc = enter(eng, stream, &st))) return rc;
-    if ((rc = device_max_spans(pat, txt, n, st, &max_p, &max_t))) return rc;
-    if (!txt->offsets) max_t = txt->length;
-    if ((rc = nv_tb_checks(&ranged, max_p, max_t, ops_stride))) return rc;
-    // gasalx_nv_traceback_device's workspace and chunks
-    const uint32_t chunk = (uint32_t)nv_tb_chunk(n, gasalx_nv_traceback_workspace(max_p, max_t, 1));
-    CK(eng->buf[B_NV_DIR].reserve((size_t)((max_p + 7) / 8) * 8 * max_t * chunk + 64));
-    CK(eng->buf[B_NV_ROW].reserve((size_t)max_t * chunk * 8 + 64));
-    return nv_tb_chunks(eng, al, mat, 0, n, pat, txt, max_p, max_t, {scores, sources, sinks, ops, ops_stride, n_ops}, chunk,
-                        st);
+    if (int rc = nv_mtb_checks(al, mat, pat, txt, &ranged)) return rc;
+    return nv_tb_device_run(eng, al, mat, &ranged, n, pat, txt, max_p, max_t, out, stream);
 }
 
 int gasalx_nv_matrix_traceback_host(gasalx_engine *eng, const gasalx_nv_aligner *al, const gasalx_nv_matrix *mat,
@@ -1368,38 +1351,25 @@ int gasalx_nv_matrix_traceback_host(gasalx_engine *eng, const gasalx_nv_aligner 
                                     const gasalx_nv_strings *txt, uint64_t txt_words, int32_t *scores,
                                     uint32_t *sources, uint32_t *sinks, uint8_t *ops, uint32_t ops_stride,
                                     uint32_t *n_ops) {
-    if (!eng || !al || !mat || !pat || !txt || !pat->words || !pat->offsets || !txt->words || !scores || !sources ||
-        !sinks || !ops || !n_ops) {
-        gx::set_error("null argument");
-        return GASALX_EINVAL;
-    }
+    const NvTbOut out = {scores, sources, sinks, ops, ops_stride, n_ops};
+    if (!eng || !al || !mat || !nv_sets_ok(pat, txt) || !nv_tb_out_ok(out)) return nv_null();
     gasalx_nv_aligner ranged;
-    int rc = nv_mtb_checks(al, mat, pat, txt, &ranged);
-    if (rc) return rc;
-    if (n == 0) return GASALX_OK;
-    hipStream_t st;
-    if ((rc = enter(eng, nullptr, &st))) return rc;
-    const uint32_t max_p = max_span(pat->offsets, n);
-    const uint32_t max_t = txt->offsets ? max_span(txt->offsets, n) : txt->length;
-    if ((rc = nv_tb_checks(&ranged, max_p, max_t, ops_stride))) return rc;
-    gasalx_nv_strings dp, dt;
-    if ((rc = nv_stage_strings(eng, n, pat, pat_words, txt, txt_words, st, dp, dt))) return rc;
-    return nv_tb_host_run(eng, al, mat, 0, n, &dp, &dt, max_p, max_t, {scores, sources, sinks, ops, ops_stride, n_ops}, st);
+    if (int rc = nv_mtb_checks(al, mat, pat, txt, &ranged)) return rc;
+    return nv_tb_host_run(eng, al, mat, 0, &ranged, {n, pat, pat_words, txt, txt_words}, out);
 }
 
 int gasalx_nv_banded_traceback_device(gasalx_engine *eng, const gasalx_nv_aligner *al, uint32_t band, uint32_t n,
                                       const gasalx_nv_strings *pat, const gasalx_nv_strings *txt, uint32_t max_p,
                                       int32_t *scores, uint32_t *sources, uint32_t *sinks, uint8_t *ops,
                                       uint32_t ops_stride, uint32_t *n_ops, void *stream) {
-    if (!eng || !al || !pat || !txt) { gx::set_error("null argument"); return GASALX_EINVAL; }
+    if (!eng || !al || !pat || !txt) return nv_null();
     if (n == 0) return GASALX_OK;
     hipStream_t st;
-    int rc = enter(eng, stream, &st);
+    int rc = nv_device_enter(eng, stream, NV_PATTERN, n, pat, txt, &max_p, nullptr, &st);
     if (rc) return rc;
-    if ((rc = device_max_spans(pat, nullptr, n, st, &max_p, nullptr))) return rc;
     if ((rc = nv_btb_checks(al, band, max_p, ops_stride))) return rc;
     const uint32_t chunk = (uint32_t)nv_tb_chunk(n, gasalx_nv_banded_traceback_workspace(max_p, band, 1));
-    CK(eng->buf[B_NV_DIR].reserve((size_t)max_p * ((band + 3) / 4) * 4 * chunk + 64));
+    CK(eng->buf[B_NV_DIR].reserve((size_t)nv_btb_dir_bytes(max_p, band) * chunk + 64));
     return nv_tb_chunks(eng, al, nullptr, band, n, pat, txt, max_p, 0, {scores, sources, sinks, ops, ops_stride, n_ops}, chunk, st);
 }
 
@@ -1407,20 +1377,10 @@ int gasalx_nv_banded_traceback_host(gasalx_engine *eng, const gasalx_nv_aligner 
                                     const gasalx_nv_strings *pat, uint64_t pat_words, const gasalx_nv_strings *txt,
                                     uint64_t txt_words, int32_t *scores, uint32_t *sources, uint32_t *sinks,
                                     uint8_t *ops, uint32_t ops_stride, uint32_t *n_ops) {
-    if (!eng || !al || !pat || !txt || !pat->words || !pat->offsets || !txt->words || !scores || !sources || !sinks ||
-        !ops || !n_ops) {
-        gx::set_error("null argument");
-        return GASALX_EINVAL;
-    }
-    const uint32_t max_p = n ? max_span(pat->offsets, n) : 0;
-    int rc = nv_btb_checks(al, band, max_p, ops_stride);
-    if (rc) return rc;
-    if (n == 0) return GASALX_OK;
-    hipStream_t st;
-    if ((rc = enter(eng, nullptr, &st))) return rc;
-    gasalx_nv_strings dp, dt;
-    if ((rc = nv_stage_strings(eng, n, pat, pat_words, txt, txt_words, st, dp, dt))) return rc;
-    return nv_tb_host_run(eng, al, nullptr, band, n, &dp, &dt, max_p, 0, {scores, sources, sinks, ops, ops_stride, n_ops}, st);
+    const NvTbOut out = {scores, sources, sinks, ops, ops_stride, n_ops};
+    if (!eng || !al || !nv_sets_ok(pat, txt) || !nv_tb_out_ok(out)) return nv_null();
+    if (int rc = nv_btb_checks(al, band, max_span(pat->offsets, n), ops_stride)) return rc;
+    return nv_tb_host_run(eng, al, nullptr, band, nullptr, {n, pat, pat_words, txt, txt_words}, out);
 }
 
 int gasalx_pairhmm_params(const uint8_t *bq, const uint8_t *iq, const uint8_t *dq, uint32_t n, float *qm,

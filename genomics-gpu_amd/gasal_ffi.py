@@ -243,6 +243,44 @@ def _p(a):
     return None if a is None else ctypes.c_void_p(a.ctypes.data)
 
 
+_u32 = ctypes.c_uint32
+
+
+def _vp(address: int):
+    """a device address or stream as a pointer argument, 0 as NULL"""
+    return ctypes.c_void_p(address or None)
+
+
+def _ref(x):
+    """byref of a C struct, or of the one an NvAligner / NvMatrix / PackedSet stands for"""
+    return ctypes.byref(x.cstruct() if hasattr(x, "cstruct") else x)
+
+
+def _nv_strings(d: dict) -> CNvStrings:
+    """a device string set, {"words": ptr, "offsets": ptr or 0, "length": int, "bits": int, "big_endian": bool}"""
+    return CNvStrings(d["words"], d.get("offsets") or None, d.get("length", 0), d["bits"],
+                      int(d.get("big_endian", False)))
+
+
+def _nv_host_sets(patterns: "PackedSet", texts: "PackedSet") -> tuple:
+    """the batch of an nv host call: patterns, their word count, texts, their word count"""
+    return (_ref(patterns), ctypes.c_uint64(len(patterns.words)), _ref(texts), ctypes.c_uint64(len(texts.words)))
+
+
+def _nv_score_outs(n: int, scores: bool, sinks: bool) -> tuple:
+    """the optional outputs of an nv score call: the two pointer arguments (NULL where not wanted) and
+    what the method returns, (scores int32[n] or None, sinks uint32[n, 2] or None)"""
+    sc = np.zeros(n, np.int32) if scores else None
+    sk = np.zeros(2 * n, np.uint32) if sinks else None
+    return _p(sc), _p(sk), (sc, sk.reshape(n, 2) if sinks else None)
+
+
+def _nv_traceback_ptrs(outs: dict, ops_stride: int) -> tuple:
+    """the outputs of an nv traceback device call, outs = {"score", "source", "sink", "ops", "n_ops"}"""
+    return (_vp(outs["score"]), _vp(outs["source"]), _vp(outs["sink"]), _vp(outs["ops"]), _u32(ops_stride),
+            _vp(outs["n_ops"]))
+
+
 SENTINEL = -(2 ** 31) + 7
 OUT_FIELDS = ("score", "q_end", "t_end", "q_start", "t_start", "score2", "q_end2", "t_end2")
 
@@ -458,17 +496,42 @@ class Engine:
         _check(lib().gasalx_pairhmm_quals_host(self._h, ctypes.byref(hb), _p(res)), "pairhmm_quals_host")
         return res
 
+    # ---- nvbio front-end.  Every call goes through _nv_call; a host form's batch is _nv_host_sets, its
+    #      optional score / sink outputs _nv_score_outs, a traceback's outputs _nv_traceback_host; a device
+    #      form's string sets are _nv_strings.  A new pair is written with these, not copied. ----
+
+    def _nv_call(self, name: str, *args):
+        _check(getattr(lib(), "gasalx_" + name)(self._h, *args), name)
+
+    def _nv_traceback_host(self, name: str, lead: tuple, patterns: "PackedSet", texts: "PackedSet", band: int = 0,
+                           ops_stride: int = None):
+        """The traceback host forms: `name` called with `lead` in front of the batch size and five output
+        arrays at ops_stride (None: the minimum, max pattern + max text length, or 2 x max pattern + band
+        with a band), and the result dict."""
+        n = patterns.n
+        po = np.asarray(patterns.offsets, np.int64)
+        max_p = int((po[1:] - po[:-1]).max(initial=0))
+        if texts.offsets is not None:
+            to = np.asarray(texts.offsets, np.int64)
+            max_t = int((to[1:] - to[:-1]).max(initial=0))
+        else:
+            max_t = int(texts.length) if n else 0
+        stride = int(ops_stride) if ops_stride is not None else 2 * max_p + int(band) if band else max_p + max_t
+        sc, nops = np.zeros(n, np.int32), np.zeros(n, np.uint32)
+        src, snk = np.zeros(2 * n, np.uint32), np.zeros(2 * n, np.uint32)
+        ops = np.zeros(max(n * stride, 1), np.uint8)
+        self._nv_call(name, *lead, _u32(n), *_nv_host_sets(patterns, texts), _p(sc), _p(src), _p(snk), _p(ops),
+                      _u32(stride), _p(nops))
+        return dict(score=sc, source=src.reshape(n, 2), sink=snk.reshape(n, 2),
+                    ops=[ops[k * stride:k * stride + int(nops[k])].copy() for k in range(n)])
+
     def nv_score_host(self, aligner: "NvAligner", patterns: "PackedSet", texts: "PackedSet", int16=False):
         """nvbio-style batched scores (gasalx_nv_score_host): patterns[i] against texts[i]
         (or the one shared text).  int16: also return sw-benchmark's int16 score vector."""
         n = patterns.n
         sc = np.zeros(n, np.int32)
         s16 = np.zeros(n, np.int16) if int16 else None
-        ca = aligner.cstruct()
-        _check(lib().gasalx_nv_score_host(self._h, ctypes.byref(ca), ctypes.c_uint32(n),
-                                          ctypes.byref(patterns.cstruct()), ctypes.c_uint64(len(patterns.words)),
-                                          ctypes.byref(texts.cstruct()), ctypes.c_uint64(len(texts.words)), _p(sc),
-                                          _p(s16)), "nv_score_host")
+        self._nv_call("nv_score_host", _ref(aligner), _u32(n), *_nv_host_sets(patterns, texts), _p(sc), _p(s16))
         return (sc, s16) if int16 else sc
 
     def nv_score_sinks_host(self, aligner: "NvAligner", patterns: "PackedSet", texts: "PackedSet", scores=True,
@@ -479,29 +542,17 @@ class Engine:
         a pair that reports no cell.  scores=False / sinks=False pass NULL for that output and
         return None in its place."""
         n = patterns.n
-        sc = np.zeros(n, np.int32) if scores else None
-        sk = np.zeros(2 * n, np.uint32) if sinks else None
-        ca = aligner.cstruct()
-        _check(lib().gasalx_nv_score_sinks_host(self._h, ctypes.byref(ca), ctypes.c_uint32(n),
-                                                ctypes.byref(patterns.cstruct()), ctypes.c_uint64(len(patterns.words)),
-                                                ctypes.byref(texts.cstruct()), ctypes.c_uint64(len(texts.words)),
-                                                _p(sc), _p(sk)), "nv_score_sinks_host")
-        return sc, (sk.reshape(n, 2) if sinks else None)
+        sc, sk, ret = _nv_score_outs(n, scores, sinks)
+        self._nv_call("nv_score_sinks_host", _ref(aligner), _u32(n), *_nv_host_sets(patterns, texts), sc, sk)
+        return ret
 
     def nv_score_sinks_device_ptrs(self, aligner: "NvAligner", n: int, pat: dict, txt: dict, scores_ptr: int = 0,
                                    sinks_ptr: int = 0, max_pattern_len: int = 0, max_text_len: int = 0,
                                    stream: int = 0):
         """Device-resident scores and sinks (gasalx_nv_score_sinks_device); pat/txt as
         nv_score_device_ptrs, scores_ptr n int32, sinks_ptr 2n uint32 (either may be 0)."""
-        mk = lambda d: CNvStrings(d["words"], d.get("offsets") or None, d.get("length", 0), d["bits"],
-                                  int(d.get("big_endian", False)))
-        ca = aligner.cstruct()
-        _check(lib().gasalx_nv_score_sinks_device(self._h, ctypes.byref(ca), ctypes.c_uint32(n),
-                                                  ctypes.byref(mk(pat)), ctypes.byref(mk(txt)),
-                                                  ctypes.c_void_p(scores_ptr or None),
-                                                  ctypes.c_void_p(sinks_ptr or None),
-                                                  ctypes.c_uint32(max_pattern_len), ctypes.c_uint32(max_text_len),
-                                                  ctypes.c_void_p(stream or None)), "nv_score_sinks_device")
+        self._nv_call("nv_score_sinks_device", _ref(aligner), _u32(n), _ref(_nv_strings(pat)), _ref(_nv_strings(txt)),
+                      _vp(scores_ptr), _vp(sinks_ptr), _u32(max_pattern_len), _u32(max_text_len), _vp(stream))
 
     def nv_matrix_score_host(self, aligner: "NvAligner", matrix: "NvMatrix", patterns: "PackedSet",
                              texts: "PackedSet", scores=True, sinks=True):
@@ -511,14 +562,10 @@ class Engine:
         sinks=False pass NULL for that output and return None in its place (sinks=False runs the
         score-only kernel)."""
         n = patterns.n
-        sc = np.zeros(n, np.int32) if scores else None
-        sk = np.zeros(2 * n, np.uint32) if sinks else None
-        ca, cm = aligner.cstruct(), matrix.cstruct()
-        _check(lib().gasalx_nv_matrix_score_host(self._h, ctypes.byref(ca), ctypes.byref(cm), ctypes.c_uint32(n),
-                                                 ctypes.byref(patterns.cstruct()), ctypes.c_uint64(len(patterns.words)),
-                                                 ctypes.byref(texts.cstruct()), ctypes.c_uint64(len(texts.words)),
-                                                 _p(sc), _p(sk)), "nv_matrix_score_host")
-        return sc, (sk.reshape(n, 2) if sinks else None)
+        sc, sk, ret = _nv_score_outs(n, scores, sinks)
+        self._nv_call("nv_matrix_score_host", _ref(aligner), _ref(matrix), _u32(n), *_nv_host_sets(patterns, texts),
+                      sc, sk)
+        return ret
 
     def nv_matrix_score_device_ptrs(self, aligner: "NvAligner", matrix: "NvMatrix", n: int, pat: dict, txt: dict,
                                     scores_ptr: int = 0, sinks_ptr: int = 0, max_pattern_len: int = 0,
@@ -526,26 +573,17 @@ class Engine:
         """Device-resident strings and outputs (gasalx_nv_matrix_score_device); the table stays a
         host array.  pat/txt as nv_score_device_ptrs, scores_ptr n int32, sinks_ptr 2n uint32
         (either may be 0)."""
-        mk = lambda d: CNvStrings(d["words"], d.get("offsets") or None, d.get("length", 0), d["bits"],
-                                  int(d.get("big_endian", False)))
-        ca, cm = aligner.cstruct(), matrix.cstruct()
-        _check(lib().gasalx_nv_matrix_score_device(self._h, ctypes.byref(ca), ctypes.byref(cm), ctypes.c_uint32(n),
-                                                   ctypes.byref(mk(pat)), ctypes.byref(mk(txt)),
-                                                   ctypes.c_void_p(scores_ptr or None),
-                                                   ctypes.c_void_p(sinks_ptr or None),
-                                                   ctypes.c_uint32(max_pattern_len), ctypes.c_uint32(max_text_len),
-                                                   ctypes.c_void_p(stream or None)), "nv_matrix_score_device")
+        self._nv_call("nv_matrix_score_device", _ref(aligner), _ref(matrix), _u32(n), _ref(_nv_strings(pat)),
+                      _ref(_nv_strings(txt)), _vp(scores_ptr), _vp(sinks_ptr), _u32(max_pattern_len),
+                      _u32(max_text_len), _vp(stream))
 
     def nv_banded_score_host(self, aligner: "NvAligner", band: int, patterns: "PackedSet", texts: "PackedSet"):
         """nvbio BatchedBandedAlignmentScore<band> (gasalx_nv_banded_score_host): BestSink
         score per pair, INT32_MIN where a text is shorter than its pattern."""
         n = patterns.n
         sc = np.zeros(n, np.int32)
-        ca = aligner.cstruct()
-        _check(lib().gasalx_nv_banded_score_host(self._h, ctypes.byref(ca), ctypes.c_uint32(band), ctypes.c_uint32(n),
-                                                 ctypes.byref(patterns.cstruct()),
-                                                 ctypes.c_uint64(len(patterns.words)), ctypes.byref(texts.cstruct()),
-                                                 ctypes.c_uint64(len(texts.words)), _p(sc)), "nv_banded_score_host")
+        self._nv_call("nv_banded_score_host", _ref(aligner), _u32(band), _u32(n), *_nv_host_sets(patterns, texts),
+                      _p(sc))
         return sc
 
     def nv_banded_score_sinks_host(self, aligner: "NvAligner", band: int, patterns: "PackedSet", texts: "PackedSet",
@@ -554,31 +592,18 @@ class Engine:
         int32[n], sinks uint32[n, 2]) as nv_banded_myers_host returns them, the score and sink of
         nv_banded_traceback_host; INT32_MIN and the empty sink where nothing is reported."""
         n = patterns.n
-        sc = np.zeros(n, np.int32) if scores else None
-        sk = np.zeros(2 * n, np.uint32) if sinks else None
-        ca = aligner.cstruct()
-        _check(lib().gasalx_nv_banded_score_sinks_host(self._h, ctypes.byref(ca), ctypes.c_uint32(band),
-                                                       ctypes.c_uint32(n), ctypes.byref(patterns.cstruct()),
-                                                       ctypes.c_uint64(len(patterns.words)),
-                                                       ctypes.byref(texts.cstruct()), ctypes.c_uint64(len(texts.words)),
-                                                       _p(sc), _p(sk)), "nv_banded_score_sinks_host")
-        return sc, (sk.reshape(n, 2) if sinks else None)
+        sc, sk, ret = _nv_score_outs(n, scores, sinks)
+        self._nv_call("nv_banded_score_sinks_host", _ref(aligner), _u32(band), _u32(n),
+                      *_nv_host_sets(patterns, texts), sc, sk)
+        return ret
 
     def nv_banded_score_sinks_device_ptrs(self, aligner: "NvAligner", band: int, n: int, pat: dict, txt: dict,
                                           scores_ptr: int = 0, sinks_ptr: int = 0, max_pattern_len: int = 0,
                                           stream: int = 0):
         """Device-resident form (gasalx_nv_banded_score_sinks_device); pat/txt as nv_score_device_ptrs,
         scores_ptr n int32, sinks_ptr 2n uint32 (either may be 0)."""
-        mk = lambda d: CNvStrings(d["words"], d.get("offsets") or None, d.get("length", 0), d["bits"],
-                                  int(d.get("big_endian", False)))
-        ca = aligner.cstruct()
-        _check(lib().gasalx_nv_banded_score_sinks_device(self._h, ctypes.byref(ca), ctypes.c_uint32(band),
-                                                         ctypes.c_uint32(n), ctypes.byref(mk(pat)),
-                                                         ctypes.byref(mk(txt)), ctypes.c_void_p(scores_ptr or None),
-                                                         ctypes.c_void_p(sinks_ptr or None),
-                                                         ctypes.c_uint32(max_pattern_len),
-                                                         ctypes.c_void_p(stream or None)),
-               "nv_banded_score_sinks_device")
+        self._nv_call("nv_banded_score_sinks_device", _ref(aligner), _u32(band), _u32(n), _ref(_nv_strings(pat)),
+                      _ref(_nv_strings(txt)), _vp(scores_ptr), _vp(sinks_ptr), _u32(max_pattern_len), _vp(stream))
 
     def nv_banded_myers_host(self, type_: int, alphabet: int, band: int, patterns: "PackedSet", texts: "PackedSet",
                              scores=True, sinks=True):
@@ -587,172 +612,75 @@ class Engine:
         uint32[n, 2]) as nv_score_sinks_host returns them; INT32_MIN and the empty sink where a text
         is shorter than its pattern.  The sets' word arrays are passed as they are."""
         n = patterns.n
-        sc = np.zeros(n, np.int32) if scores else None
-        sk = np.zeros(2 * n, np.uint32) if sinks else None
-        _check(lib().gasalx_nv_banded_myers_host(self._h, ctypes.c_int32(type_), ctypes.c_uint32(alphabet),
-                                                 ctypes.c_uint32(band), ctypes.c_uint32(n),
-                                                 ctypes.byref(patterns.cstruct()), ctypes.c_uint64(len(patterns.words)),
-                                                 ctypes.byref(texts.cstruct()), ctypes.c_uint64(len(texts.words)),
-                                                 _p(sc), _p(sk)), "nv_banded_myers_host")
-        return sc, (sk.reshape(n, 2) if sinks else None)
+        sc, sk, ret = _nv_score_outs(n, scores, sinks)
+        self._nv_call("nv_banded_myers_host", ctypes.c_int32(type_), _u32(alphabet), _u32(band), _u32(n),
+                      *_nv_host_sets(patterns, texts), sc, sk)
+        return ret
 
     def nv_banded_myers_device_ptrs(self, type_: int, alphabet: int, band: int, n: int, pat: dict, txt: dict,
                                     scores_ptr: int = 0, sinks_ptr: int = 0, max_pattern_len: int = 0,
                                     stream: int = 0):
         """Device-resident banded Myers scoring (gasalx_nv_banded_myers_device); pat/txt as
         nv_score_device_ptrs, scores_ptr n int32, sinks_ptr 2n uint32 (either may be 0)."""
-        mk = lambda d: CNvStrings(d["words"], d.get("offsets") or None, d.get("length", 0), d["bits"],
-                                  int(d.get("big_endian", False)))
-        _check(lib().gasalx_nv_banded_myers_device(self._h, ctypes.c_int32(type_), ctypes.c_uint32(alphabet),
-                                                   ctypes.c_uint32(band), ctypes.c_uint32(n), ctypes.byref(mk(pat)),
-                                                   ctypes.byref(mk(txt)), ctypes.c_void_p(scores_ptr or None),
-                                                   ctypes.c_void_p(sinks_ptr or None),
-                                                   ctypes.c_uint32(max_pattern_len), ctypes.c_void_p(stream or None)),
-               "nv_banded_myers_device")
+        self._nv_call("nv_banded_myers_device", ctypes.c_int32(type_), _u32(alphabet), _u32(band), _u32(n),
+                      _ref(_nv_strings(pat)), _ref(_nv_strings(txt)), _vp(scores_ptr), _vp(sinks_ptr),
+                      _u32(max_pattern_len), _vp(stream))
 
     def nv_traceback_host(self, aligner: "NvAligner", patterns: "PackedSet", texts: "PackedSet"):
         """nvbio BatchedAlignmentTraceback (gasalx_nv_traceback_host): per pair the BestSink score, the
         Alignment's source and sink ((x, y) = (text, pattern)) and the backtracker's pushes in push
         order (0 'M', 1 'I', 2 'D') -- the dict oracle.nv_traceback returns."""
-        n = patterns.n
-        po = np.asarray(patterns.offsets, np.int64)
-        plen = po[1:] - po[:-1]
-        if texts.offsets is not None:
-            to = np.asarray(texts.offsets, np.int64)
-            tlen = to[1:] - to[:-1]
-        else:
-            tlen = np.full(n, int(texts.length), np.int64)
-        stride = int(plen.max(initial=0) + tlen.max(initial=0))
-        sc = np.zeros(n, np.int32)
-        src = np.zeros(2 * n, np.uint32)
-        snk = np.zeros(2 * n, np.uint32)
-        ops = np.zeros(max(n * stride, 1), np.uint8)
-        nops = np.zeros(n, np.uint32)
-        ca = aligner.cstruct()
-        _check(lib().gasalx_nv_traceback_host(self._h, ctypes.byref(ca), ctypes.c_uint32(n),
-                                              ctypes.byref(patterns.cstruct()), ctypes.c_uint64(len(patterns.words)),
-                                              ctypes.byref(texts.cstruct()), ctypes.c_uint64(len(texts.words)),
-                                              _p(sc), _p(src), _p(snk), _p(ops), ctypes.c_uint32(stride), _p(nops)),
-               "nv_traceback_host")
-        return dict(score=sc, source=src.reshape(n, 2), sink=snk.reshape(n, 2),
-                    ops=[ops[k * stride:k * stride + int(nops[k])].copy() for k in range(n)])
+        return self._nv_traceback_host("nv_traceback_host", (_ref(aligner),), patterns, texts)
 
     def nv_traceback_device_ptrs(self, aligner: "NvAligner", n: int, pat: dict, txt: dict, outs: dict,
                                  ops_stride: int, max_pattern_len: int = 0, max_text_len: int = 0, stream: int = 0):
         """Device-resident traceback (gasalx_nv_traceback_device); pat/txt as nv_score_device_ptrs, outs =
         {"score", "source", "sink", "ops", "n_ops"} device addresses."""
-        mk = lambda d: CNvStrings(d["words"], d.get("offsets") or None, d.get("length", 0), d["bits"],
-                                  int(d.get("big_endian", False)))
-        ca = aligner.cstruct()
-        v = lambda k: ctypes.c_void_p(outs[k] or None)
-        _check(lib().gasalx_nv_traceback_device(self._h, ctypes.byref(ca), ctypes.c_uint32(n), ctypes.byref(mk(pat)),
-                                                ctypes.byref(mk(txt)), ctypes.c_uint32(max_pattern_len),
-                                                ctypes.c_uint32(max_text_len), v("score"), v("source"), v("sink"),
-                                                v("ops"), ctypes.c_uint32(ops_stride), v("n_ops"),
-                                                ctypes.c_void_p(stream or None)), "nv_traceback_device")
+        self._nv_call("nv_traceback_device", _ref(aligner), _u32(n), _ref(_nv_strings(pat)), _ref(_nv_strings(txt)),
+                      _u32(max_pattern_len), _u32(max_text_len), *_nv_traceback_ptrs(outs, ops_stride), _vp(stream))
 
     def nv_matrix_traceback_host(self, aligner: "NvAligner", matrix: "NvMatrix", patterns: "PackedSet",
                                  texts: "PackedSet", ops_stride: int = None):
         """The full-DP Gotoh traceback with a substitution matrix (gasalx_nv_matrix_traceback_host): S(p, t)
         = matrix.scores[p, t], symbols >= n read as n - 1, aligner.match / mismatch ignored.  The dict
         nv_traceback_host returns; ops_stride defaults to its minimum, max pattern + max text length."""
-        n = patterns.n
-        po = np.asarray(patterns.offsets, np.int64)
-        plen = po[1:] - po[:-1]
-        if texts.offsets is not None:
-            to = np.asarray(texts.offsets, np.int64)
-            tlen = to[1:] - to[:-1]
-        else:
-            tlen = np.full(n, int(texts.length), np.int64)
-        stride = int(plen.max(initial=0) + tlen.max(initial=0)) if ops_stride is None else int(ops_stride)
-        sc = np.zeros(n, np.int32)
-        src = np.zeros(2 * n, np.uint32)
-        snk = np.zeros(2 * n, np.uint32)
-        ops = np.zeros(max(n * stride, 1), np.uint8)
-        nops = np.zeros(n, np.uint32)
-        ca, cm = aligner.cstruct(), matrix.cstruct()
-        _check(lib().gasalx_nv_matrix_traceback_host(self._h, ctypes.byref(ca), ctypes.byref(cm), ctypes.c_uint32(n),
-                                                     ctypes.byref(patterns.cstruct()), ctypes.c_uint64(len(patterns.words)),
-                                                     ctypes.byref(texts.cstruct()), ctypes.c_uint64(len(texts.words)),
-                                                     _p(sc), _p(src), _p(snk), _p(ops), ctypes.c_uint32(stride), _p(nops)),
-               "nv_matrix_traceback_host")
-        return dict(score=sc, source=src.reshape(n, 2), sink=snk.reshape(n, 2),
-                    ops=[ops[k * stride:k * stride + int(nops[k])].copy() for k in range(n)])
+        return self._nv_traceback_host("nv_matrix_traceback_host", (_ref(aligner), _ref(matrix)), patterns, texts,
+                                       ops_stride=ops_stride)
 
     def nv_matrix_traceback_device_ptrs(self, aligner: "NvAligner", matrix: "NvMatrix", n: int, pat: dict, txt: dict,
                                         outs: dict, ops_stride: int, max_pattern_len: int = 0, max_text_len: int = 0,
                                         stream: int = 0):
         """Device-resident form (gasalx_nv_matrix_traceback_device); the table stays a host array, the
         other arguments as nv_traceback_device_ptrs."""
-        mk = lambda d: CNvStrings(d["words"], d.get("offsets") or None, d.get("length", 0), d["bits"],
-                                  int(d.get("big_endian", False)))
-        ca, cm = aligner.cstruct(), matrix.cstruct()
-        v = lambda k: ctypes.c_void_p(outs[k] or None)
-        _check(lib().gasalx_nv_matrix_traceback_device(self._h, ctypes.byref(ca), ctypes.byref(cm), ctypes.c_uint32(n),
-                                                       ctypes.byref(mk(pat)), ctypes.byref(mk(txt)),
-                                                       ctypes.c_uint32(max_pattern_len), ctypes.c_uint32(max_text_len),
-                                                       v("score"), v("source"), v("sink"), v("ops"),
-                                                       ctypes.c_uint32(ops_stride), v("n_ops"),
-                                                       ctypes.c_void_p(stream or None)), "nv_matrix_traceback_device")
+        self._nv_call("nv_matrix_traceback_device", _ref(aligner), _ref(matrix), _u32(n), _ref(_nv_strings(pat)),
+                      _ref(_nv_strings(txt)), _u32(max_pattern_len), _u32(max_text_len),
+                      *_nv_traceback_ptrs(outs, ops_stride), _vp(stream))
 
     def nv_banded_traceback_host(self, aligner: "NvAligner", band: int, patterns: "PackedSet", texts: "PackedSet"):
         """nvbio BatchedBandedAlignmentTraceback<band> (gasalx_nv_banded_traceback_host): the dict
         oracle.nv_banded_traceback returns."""
-        n = patterns.n
-        po = np.asarray(patterns.offsets, np.int64)
-        stride = 2 * int((po[1:] - po[:-1]).max(initial=0)) + int(band)
-        sc = np.zeros(n, np.int32)
-        src = np.zeros(2 * n, np.uint32)
-        snk = np.zeros(2 * n, np.uint32)
-        ops = np.zeros(max(n * stride, 1), np.uint8)
-        nops = np.zeros(n, np.uint32)
-        ca = aligner.cstruct()
-        _check(lib().gasalx_nv_banded_traceback_host(self._h, ctypes.byref(ca), ctypes.c_uint32(band), ctypes.c_uint32(n),
-                                                     ctypes.byref(patterns.cstruct()), ctypes.c_uint64(len(patterns.words)),
-                                                     ctypes.byref(texts.cstruct()), ctypes.c_uint64(len(texts.words)),
-                                                     _p(sc), _p(src), _p(snk), _p(ops), ctypes.c_uint32(stride), _p(nops)),
-               "nv_banded_traceback_host")
-        return dict(score=sc, source=src.reshape(n, 2), sink=snk.reshape(n, 2),
-                    ops=[ops[k * stride:k * stride + int(nops[k])].copy() for k in range(n)])
+        return self._nv_traceback_host("nv_banded_traceback_host", (_ref(aligner), _u32(band)), patterns, texts,
+                                       band=band)
 
     def nv_banded_traceback_device_ptrs(self, aligner: "NvAligner", band: int, n: int, pat: dict, txt: dict,
                                         outs: dict, ops_stride: int, max_pattern_len: int = 0, stream: int = 0):
         """Device-resident banded traceback (gasalx_nv_banded_traceback_device); arguments as
         nv_traceback_device_ptrs."""
-        mk = lambda d: CNvStrings(d["words"], d.get("offsets") or None, d.get("length", 0), d["bits"],
-                                  int(d.get("big_endian", False)))
-        ca = aligner.cstruct()
-        v = lambda k: ctypes.c_void_p(outs[k] or None)
-        _check(lib().gasalx_nv_banded_traceback_device(self._h, ctypes.byref(ca), ctypes.c_uint32(band), ctypes.c_uint32(n),
-                                                       ctypes.byref(mk(pat)), ctypes.byref(mk(txt)),
-                                                       ctypes.c_uint32(max_pattern_len), v("score"), v("source"),
-                                                       v("sink"), v("ops"), ctypes.c_uint32(ops_stride), v("n_ops"),
-                                                       ctypes.c_void_p(stream or None)), "nv_banded_traceback_device")
+        self._nv_call("nv_banded_traceback_device", _ref(aligner), _u32(band), _u32(n), _ref(_nv_strings(pat)),
+                      _ref(_nv_strings(txt)), _u32(max_pattern_len), *_nv_traceback_ptrs(outs, ops_stride), _vp(stream))
 
     def nv_banded_score_device_ptrs(self, aligner: "NvAligner", band: int, n: int, pat: dict, txt: dict,
                                     scores_ptr: int, stream: int = 0, max_pattern_len: int = 0):
         """Device-resident banded scoring (gasalx_nv_banded_score_device); pat/txt as nv_score_device_ptrs."""
-        mk = lambda d: CNvStrings(d["words"], d.get("offsets") or None, d.get("length", 0), d["bits"],
-                                  int(d.get("big_endian", False)))
-        ca = aligner.cstruct()
-        _check(lib().gasalx_nv_banded_score_device(self._h, ctypes.byref(ca), ctypes.c_uint32(band), ctypes.c_uint32(n),
-                                                   ctypes.byref(mk(pat)), ctypes.byref(mk(txt)),
-                                                   ctypes.c_void_p(scores_ptr or None), ctypes.c_uint32(max_pattern_len),
-                                                   ctypes.c_void_p(stream or None)),
-               "nv_banded_score_device")
+        self._nv_call("nv_banded_score_device", _ref(aligner), _u32(band), _u32(n), _ref(_nv_strings(pat)),
+                      _ref(_nv_strings(txt)), _vp(scores_ptr), _u32(max_pattern_len), _vp(stream))
 
     def nv_score_device_ptrs(self, aligner: "NvAligner", n: int, pat: dict, txt: dict, scores_ptr: int = 0,
                              scores16_ptr: int = 0, max_pattern_len: int = 0, max_text_len: int = 0, stream: int = 0):
         """Device-resident nvbio-style scoring: pat/txt = {"words": ptr, "offsets": ptr or 0, "length": int,
         "bits": int, "big_endian": bool} with device addresses."""
-        mk = lambda d: CNvStrings(d["words"], d.get("offsets") or None, d.get("length", 0), d["bits"],
-                                  int(d.get("big_endian", False)))
-        ca = aligner.cstruct()
-        _check(lib().gasalx_nv_score_device(self._h, ctypes.byref(ca), ctypes.c_uint32(n), ctypes.byref(mk(pat)),
-                                            ctypes.byref(mk(txt)), ctypes.c_void_p(scores_ptr or None),
-                                            ctypes.c_void_p(scores16_ptr or None), ctypes.c_uint32(max_pattern_len),
-                                            ctypes.c_uint32(max_text_len), ctypes.c_void_p(stream or None)),
-               "nv_score_device")
+        self._nv_call("nv_score_device", _ref(aligner), _u32(n), _ref(_nv_strings(pat)), _ref(_nv_strings(txt)),
+                      _vp(scores_ptr), _vp(scores16_ptr), _u32(max_pattern_len), _u32(max_text_len), _vp(stream))
 
     def pairhmm_device_ptrs(self, ptrs: dict, read_bytes: int, hap_bytes: int, n: int, max_r: int, max_h: int,
                             result_ptr: int, stream: int = 0):

@@ -14,7 +14,7 @@ import oracle as O
 
 pytestmark = pytest.mark.gpu
 
-OK, EINVAL, ERANGE = 0, -1, -2
+OK, EINVAL, ERANGE, EUNSUPPORTED = 0, -1, -2, -5
 NULLARG = "null argument"
 BAND = "band length must be 2..32"
 ENG = object()                       # stands for the engine's handle in a case's arguments
@@ -80,6 +80,18 @@ def aligner(kind=G.NV_GOTOH, mag=2, type_=G.NV_GLOBAL):
     return G.CNvAligner(kind, type_, mag, -1, -2, -1, -1, -1)
 
 
+def matrix(n=4, entry=-1):
+    """an n x n substitution table whose largest |entry| is |entry|"""
+    a = np.full(n * n, entry, np.int8)
+    _keep.append(a)
+    return G.CNvMatrix(ptr(a), n)
+
+
+def shared_text(length, bits=2):
+    """one shared text: no offsets, its length in the struct"""
+    return G.CNvStrings(ptr(Z32), None, length, bits, 0)
+
+
 BATCH_ARRAYS = ("q_batch", "t_batch", "q_offsets", "t_offsets", "q_lens", "t_lens")
 QUAL_ARRAYS = ("reads", "read_offsets", "read_lens", "base_quals", "ins_quals", "del_quals", "haps", "hap_offsets",
                "hap_lens")
@@ -87,25 +99,55 @@ STRING_ARRAYS = ((0, "words"), (0, "offsets"), (1, "words"))        # (pattern /
 o = ptr(OUT)
 
 
-def nv_args(name, n=0, band=16, al=None, pat=None, txt=None, stride=64):
-    """the argument list of an nvbio entry point, and the positions of its pattern and text sets"""
-    al = ref(al or aligner())
+NV_SCORE = ("score", "score_sinks", "matrix_score", "banded_score", "banded_score_sinks", "banded_myers")
+NV_TRACEBACK = ("traceback", "matrix_traceback", "banded_traceback")
+NV_DEVICE = tuple(f"gasalx_nv_{f}_device" for f in NV_SCORE + NV_TRACEBACK)
+NV_HOST = tuple(f"gasalx_nv_{f}_host" for f in NV_SCORE + NV_TRACEBACK)
+NV_FIRST = ("score", "banded_score", "traceback", "banded_traceback")   # the pairs with loops of their own below
+
+
+def nv_args(name, n=0, band=16, al=None, pat=None, txt=None, stride=64, mat=None, myers=(G.NV_SEMI_GLOBAL, 4),
+            max_p=0, max_t=0):
+    """the argument list of an nvbio entry point, and the positions of its pattern and text sets;
+    myers: the Myers forms' (type, alphabet), which stand where the others have their aligner;
+    max_p, max_t: the device forms' bounds"""
+    device = name.endswith("device")
+    family = name[len("gasalx_nv_"):].rsplit("_", 1)[0]
     pat, txt = ref(pat or strings()), ref(txt or strings(bits=2, big=0))
     b = (u32(band),) if "banded" in name else ()
-    head = (ENG, al) + b + (u32(n),)
-    at = len(head)
-    sets = (pat, txt) if name.endswith("device") else (pat, u64(1), txt, u64(1))
-    at_txt = at + (1 if name.endswith("device") else 2)
-    if "traceback" in name:
-        outs = (o, o, o, o, u32(stride), o)
-        maxima = ((u32(0),) if "banded" in name else (u32(0), u32(0))) if name.endswith("device") else ()
-        tail = maxima + outs
-    elif "banded" in name:
-        tail = (o, u32(0)) if name.endswith("device") else (o,)
+    if family == "banded_myers":
+        head = (ENG, C.c_int32(myers[0]), u32(myers[1])) + b + (u32(n),)
     else:
-        tail = (o, None, u32(0), u32(0)) if name.endswith("device") else (o, None)
-    args = head + sets + tail + ((None,) if name.endswith("device") else ())
+        head = (ENG, ref(al or aligner())) + ((ref(mat or matrix()),) if "matrix" in name else ()) + b + (u32(n),)
+    at = len(head)
+    sets = (pat, txt) if device else (pat, u64(1), txt, u64(1))
+    at_txt = at + (1 if device else 2)
+    maxima = ((u32(max_p),) if "banded" in name else (u32(max_p), u32(max_t))) if device else ()
+    if "traceback" in name:
+        tail = maxima + (o, o, o, o, u32(stride), o)
+    elif family == "banded_score":
+        tail = (o,) + maxima                                         # scores
+    elif family == "score":
+        tail = (o, None) + maxima                                    # scores, scores16
+    else:
+        tail = (o, o) + maxima                                       # scores, sinks
+    args = head + sets + tail + ((None,) if device else ())
     return args, at, at_txt
+
+
+def nv_structs(name, at, at_txt):
+    """the positions of an nvbio entry point's engine, aligner (the Myers forms have none), matrix and
+    string sets"""
+    return [0] + ([] if "myers" in name else [1]) + ([2] if "matrix" in name else []) + [at, at_txt]
+
+
+def nv_string_fields(name, args, at, at_txt):
+    """one case per array of the two string sets that a host form needs"""
+    c = []
+    for which, field in STRING_ARRAYS:
+        make = strings if which == 0 else (lambda: strings(bits=2, big=0))
+        c += null_field(name, args, (at, at_txt)[which], make, (field,), tag=("patterns.", "texts.")[which])
+    return c
 
 
 def null_at(name, args, positions, msg=NULLARG):
@@ -171,9 +213,61 @@ def _null_cases():
         for which, field in STRING_ARRAYS:
             make = strings if which == 0 else (lambda: strings(bits=2, big=0))
             c += null_field(name, args, (at, at_txt)[which], make, (field,), tag=("patterns.", "texts.")[which])
+    # the pairs the two loops above leave out: sinks, matrix, banded sinks, Myers, matrix traceback
+    for name in NV_DEVICE:
+        if name[len("gasalx_nv_"):-len("_device")] in NV_FIRST:
+            continue
+        args, at, at_txt = nv_args(name)
+        c += null_at(name, args, nv_structs(name, at, at_txt))
+        if name == "gasalx_nv_matrix_traceback_device":              # the one device form that checks as a host form
+            c += null_at(name, args, [i for i, a in enumerate(args) if a is o])
+            c += nv_string_fields(name, args, at, at_txt)
+    for name in NV_HOST:
+        if name[len("gasalx_nv_"):-len("_host")] in NV_FIRST:
+            continue
+        args, at, at_txt = nv_args(name)
+        outs = [i for i, a in enumerate(args) if a is o]
+        if "traceback" not in name:                                   # scores, sinks: one of them is enough
+            c.append((f"{name}-both-outputs", name, args[:-2] + (None, None), EINVAL, NULLARG))
+            outs = []
+        c += null_at(name, args, nv_structs(name, at, at_txt) + outs)
+        c += nv_string_fields(name, args, at, at_txt)
+    # A NULL table: the traceback forms' own checks refuse it; the score forms leave it to the launcher,
+    # which an empty host batch never reaches.
+    for name in ("gasalx_nv_matrix_score_device", "gasalx_nv_matrix_score_host", "gasalx_nv_matrix_traceback_device",
+                 "gasalx_nv_matrix_traceback_host"):
+        args = nv_args(name, mat=set_field(matrix(), "scores", None))[0]
+        quiet = name == "gasalx_nv_matrix_score_host"
+        c.append((f"{name}-matrix.scores", name, args, OK if quiet else EINVAL, None if quiet else NULLARG))
+    # the five describe functions: NULL aligner (where there is one) and buffer, no room, one good call,
+    # the inputs the three that can refuse do refuse, and the null test before them
     nvp = (ref(aligner()), u32(10), u32(10), C.c_int(0), u32(2), buf, u32(128))
     c += null_at("gasalx_nv_describe_plan", nvp, (0, 5))
     c.append(("nv_describe_plan-len0", "gasalx_nv_describe_plan", nvp[:6] + (u32(0),), EINVAL, NULLARG))
+    al, sw = ref(aligner()), ref(aligner(G.NV_SW))
+    msize, bits, alphabet = "matrix size must be 2..32", "symbol bits must be 2, 4 or 8", "alphabet size must be 2, 4 or 5"
+    for short, good, nulls, bad in (
+            ("sinks_plan", nvp, (0, 5), ()),
+            ("matrix_plan", (al, u32(4), u32(10), u32(10), C.c_int(1), C.c_int(0), buf, u32(128)), (0, 6),
+             (("n33", (al, u32(33)), EINVAL, msize), ("n1", (al, u32(1)), EINVAL, msize),
+              ("type3", (ref(aligner(type_=3)),), EINVAL, "bad aligner"),
+              ("sw", (sw,), EUNSUPPORTED, "only the Gotoh aligner takes a substitution matrix"))),
+            ("banded_sinks_plan", (al, u32(16), u32(10), u32(2), buf, u32(128)), (0, 4),
+             (("band33", (al, u32(33)), EINVAL, BAND), ("band1", (al, u32(1)), EINVAL, BAND),
+              ("bits3", (al, u32(16), u32(10), u32(3)), EINVAL, bits))),
+            ("myers_plan", (C.c_int32(G.NV_SEMI_GLOBAL), u32(4), u32(16), buf, u32(128)), (3,),
+             (("type3", (C.c_int32(3),), EINVAL, "bad aligner"),
+              ("band33", (C.c_int32(G.NV_GLOBAL), u32(4), u32(33)), EINVAL, BAND),
+              ("alphabet3", (C.c_int32(G.NV_GLOBAL), u32(3)), EINVAL, alphabet),
+              ("local", (C.c_int32(G.NV_LOCAL),), EUNSUPPORTED, "banded Myers has no LOCAL form")))):
+        name = "gasalx_nv_describe_" + short
+        c += null_at(name, good, nulls)
+        c.append((f"nv_describe_{short}-len0", name, good[:-1] + (u32(0),), EINVAL, NULLARG))
+        c.append((f"nv_describe_{short}-ok", name, good, OK, None))
+        for tag, lead, rc, msg in bad:
+            c.append((f"nv_describe_{short}-{tag}", name, lead + good[len(lead):], rc, msg))
+            c.append((f"nv_describe_{short}-{tag}-len0", name, lead + good[len(lead):-1] + (u32(0),), EINVAL, NULLARG))
+    c.append(("nv_describe_plan-ok", "gasalx_nv_describe_plan", nvp, OK, None))
     # the rest
     h, t = u64(0), u64(0)
     c += null_at("gasalx_packed_pairs", (ENG, ref(h), ref(t)), (0, 1, 2), "gasalx_packed_pairs: NULL argument")
@@ -220,6 +314,92 @@ def _range_cases():
             args, _, _ = nv_args("gasalx_nv_banded_score_host", n=n, band=band, pat=strings(offsets(0, 10)),
                                  txt=strings(offsets(0, 20), bits=2, big=0))
             c.append((f"banded_score-band{band}-n{n}", "gasalx_nv_banded_score_host", args, EINVAL, BAND))
+
+    # the matrix traceback: gasalx_nv_traceback_host's rows, the table's largest |entry| (an int8) standing
+    # for match and mismatch: 256 * 128 = 32768 is refused, 1057 * 31 = 32767 passes on to the stride check
+    def mtb(tag, entry, p, t, stride, rc, msg):
+        args, _, _ = nv_args("gasalx_nv_matrix_traceback_host", n=1, mat=matrix(entry=entry),
+                             pat=strings(offsets(0, p)), txt=strings(offsets(0, t), bits=2, big=0), stride=stride)
+        c.append((f"matrix_traceback-{tag}", "gasalx_nv_matrix_traceback_host", args, rc, msg))
+
+    assert (127 + 127 + 2) * 128 == 32768 and (500 + 555 + 2) * 31 == 32767
+    mtb("int16-above", -128, 127, 127, 254, ERANGE, "int16 columns")
+    mtb("int16-exact", -31, 500, 555, 1054, EINVAL, "ops_stride < max pattern")
+    mtb("stride-short", -1, 100, 100, 199, EINVAL, "ops_stride < max pattern")
+    mtb("cells", -1, 4097, 4097, 8194, ERANGE, "16 M cells")
+    mtb("cells-4096-stride", -1, 4096, 4096, 8191, EINVAL, "ops_stride < max pattern")
+    return c
+
+
+def _order_cases():
+    """which checks come before the early return for an empty batch, entry point by entry point"""
+    c = []
+    pat10, txt20 = (lambda: strings(offsets(0, 10))), (lambda: strings(offsets(0, 20), bits=2, big=0))
+    # both banded score host forms: the band (gasalx_nv_banded_score_host has its rows in _range_cases)
+    name = "gasalx_nv_banded_score_sinks_host"
+    for band in (1, 33):
+        for n in (0, 1):
+            args = nv_args(name, n=n, band=band, pat=pat10(), txt=txt20())[0]
+            c.append((f"banded_score_sinks-band{band}-n{n}", name, args, EINVAL, BAND))
+    # the Myers host form: nv_myers_plan_name's codes and texts
+    name = "gasalx_nv_banded_myers_host"
+    for tag, myers, band, rc, msg in (("type3", (3, 4), 16, EINVAL, "bad aligner"),
+                                      ("band1", (G.NV_GLOBAL, 4), 1, EINVAL, BAND),
+                                      ("band33", (G.NV_GLOBAL, 4), 33, EINVAL, BAND),
+                                      ("alphabet3", (G.NV_GLOBAL, 3), 16, EINVAL, "alphabet size must be 2, 4 or 5"),
+                                      ("local", (G.NV_LOCAL, 4), 16, EUNSUPPORTED, "banded Myers has no LOCAL form")):
+        for n in (0, 1):
+            args = nv_args(name, n=n, band=band, myers=myers, pat=pat10(), txt=txt20())[0]
+            c.append((f"banded_myers-{tag}-n{n}", name, args, rc, msg))
+    # the banded traceback host form: nv_btb_checks with a longest pattern of 0
+    name = "gasalx_nv_banded_traceback_host"
+    assert (0 + 16 + 3) * 1724 > 32736 >= (0 + 16 + 3) * 1722
+    c.append(("banded_traceback-n0-int16", name, nv_args(name, al=aligner(mag=1724))[0], ERANGE, "int16 checkpoints"))
+    c.append(("banded_traceback-n0-int16-below", name, nv_args(name, al=aligner(mag=1722))[0], OK, None))
+    c.append(("banded_traceback-n0-stride", name, nv_args(name, stride=15)[0], EINVAL, "ops_stride < 2 x max pattern"))
+    c.append(("banded_traceback-n0-stride-exact", name, nv_args(name, stride=16)[0], OK, None))
+    # both matrix traceback forms: nv_mtb_checks (aligner, table size, table, symbol bits) in that order,
+    # after the null test
+    for name in ("gasalx_nv_matrix_traceback_host", "gasalx_nv_matrix_traceback_device"):
+        short = name[len("gasalx_nv_"):]
+        for tag, kw, rc, msg in (
+                ("type3", lambda: dict(al=aligner(type_=3)), EINVAL, "bad aligner"),
+                ("sw", lambda: dict(al=aligner(G.NV_SW)), EUNSUPPORTED, "only the Gotoh aligner takes a substitution matrix"),
+                ("n1", lambda: dict(mat=matrix(1)), EINVAL, "matrix size must be 2..32"),
+                ("n33", lambda: dict(mat=matrix(33)), EINVAL, "matrix size must be 2..32"),
+                ("bits3", lambda: dict(pat=strings(bits=3)), EINVAL, "symbol bits must be 2, 4 or 8"),
+                ("sw-n33", lambda: dict(al=aligner(G.NV_SW), mat=matrix(33)), EUNSUPPORTED, "only the Gotoh aligner"),
+                ("n33-bits3", lambda: dict(mat=matrix(33), pat=strings(bits=3)), EINVAL, "matrix size must be 2..32")):
+            for n in (0, 1):
+                c.append((f"{short}-{tag}-n{n}", name, nv_args(name, n=n, **kw())[0], rc, msg))
+        args = nv_args(name, al=aligner(G.NV_SW))[0]
+        last = max(i for i, a in enumerate(args) if a is o)
+        c.append((f"{short}-sw-null-output", name, args[:last] + (None,) + args[last + 1:], EINVAL, NULLARG))
+    # The score device forms have no early return of their own.  The launcher's comes first in the two
+    # full-DP score forms and after its checks in the others, which refuse an empty batch with a bad
+    # band, alphabet or table size.
+    for tag, name, kw, msg in (("band33", "gasalx_nv_banded_score_device", dict(band=33), BAND),
+                               ("band33", "gasalx_nv_banded_score_sinks_device", dict(band=33), BAND),
+                               ("band33", "gasalx_nv_banded_myers_device", dict(band=33), BAND),
+                               ("alphabet3", "gasalx_nv_banded_myers_device", dict(myers=(G.NV_GLOBAL, 3)),
+                                "alphabet size must be 2, 4 or 5"),
+                               ("n33", "gasalx_nv_matrix_score_device", dict(mat=matrix(33)), "matrix size must be 2..32")):
+        c.append((f"{name}-n0-{tag}", name, nv_args(name, **kw)[0], EINVAL, msg))
+    for name in ("gasalx_nv_score_device", "gasalx_nv_score_sinks_device"):
+        c.append((f"{name}-n0-type3", name, nv_args(name, al=aligner(type_=3))[0], OK, None))
+    # Patterns without offsets and no bound: both banded score device forms skip the read-back, and the
+    # launcher refuses the set.  (The banded traceback form has no such guard; no row calls it that way.)
+    for name in ("gasalx_nv_banded_score_device", "gasalx_nv_banded_score_sinks_device"):
+        args = nv_args(name, n=1, pat=set_field(strings(), "offsets", None))[0]
+        c.append((f"{name}-no-offsets", name, args, EINVAL, NULLARG))
+    # One shared text: the full-DP traceback device forms take its length, not the caller's max_t.
+    # 100 + 100 + 2 at |score| 163 leaves the int16 range; with the caller's 5 it would not, and the
+    # call would be refused for its stride instead.
+    assert (100 + 100 + 2) * 163 > 32767 >= (100 + 5 + 2) * 163
+    for name in ("gasalx_nv_traceback_device", "gasalx_nv_matrix_traceback_device"):
+        gap = G.CNvAligner(G.NV_GOTOH, G.NV_GLOBAL, 1, -1, -163, -1, -1, -1)
+        args = nv_args(name, n=1, al=gap, txt=shared_text(100), max_p=100, max_t=5, stride=104)[0]
+        c.append((f"{name}-shared-text-length", name, args, ERANGE, "int16 columns"))
     return c
 
 
@@ -241,10 +421,25 @@ def _empty_cases():
     for name in ("gasalx_nv_traceback_device", "gasalx_nv_banded_traceback_device"):
         args = tuple(None if a is o else a for a in nv_args(name)[0])
         c.append((f"{name}-n0-null-outputs", name, args, OK, None))
+    # every other nv entry point returns OK for an empty batch as well
+    done = {case[1] for case in c}
+    for name in NV_DEVICE + NV_HOST:
+        if name not in done:
+            c.append((f"{name}-n0", name, nv_args(name)[0], OK, None))
+    # the score device forms: NULL outputs reach the launcher, which returns for an empty batch
+    for name in NV_DEVICE[:len(NV_SCORE)]:
+        args = tuple(None if a is o else a for a in nv_args(name)[0])
+        c.append((f"{name}-n0-null-outputs", name, args, OK, None))
+    # two outputs of which one is enough: either alone
+    for name in NV_HOST[:len(NV_SCORE)]:
+        if name != "gasalx_nv_banded_score_host":
+            args = nv_args(name)[0]
+            c.append((f"{name}-n0-first-output-only", name, args[:-1] + (None,), OK, None))
+            c.append((f"{name}-n0-second-output-only", name, args[:-2] + (None, o), OK, None))
     return c
 
 
-CASES = _null_cases() + _range_cases() + _empty_cases()
+CASES = _null_cases() + _range_cases() + _order_cases() + _empty_cases()
 
 
 @pytest.fixture(scope="module", autouse=True)

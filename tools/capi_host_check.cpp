@@ -91,6 +91,56 @@ int main() {
         EXPECT(gasalx_nv_describe_plan(&al, 150, 182, 1, 2, exact.data(), (uint32_t)exact.size()) == GASALX_OK);
         EXPECT(null_arg(gasalx_nv_describe_plan(nullptr, 1, 1, 0, 2, buf, sizeof(buf))));
         EXPECT(null_arg(gasalx_nv_describe_plan(&al, 1, 1, 0, 2, buf, 0)));
+        EXPECT(null_arg(gasalx_nv_describe_plan(&al, 1, 1, 0, 2, nullptr, 8)));
+    }
+    // the other four gasalx_nv_describe_*_plan: NULL aligner (where there is one) and buffer, no room, a
+    // buffer that fits exactly and one byte, and what the three that can refuse do refuse, with its text
+    {
+        const gasalx_nv_aligner al = {GASALX_NV_GOTOH, GASALX_NV_LOCAL, 2, -1, -2, -1, 0, 0};
+        const gasalx_nv_aligner sw = {GASALX_NV_SW, GASALX_NV_LOCAL, 2, -1, 0, 0, -1, -1};
+        const gasalx_nv_aligner type3 = {GASALX_NV_GOTOH, 3, 2, -1, -2, -1, 0, 0};
+        char buf[128];
+        auto refused = [](int rc, int want, const char *text) { return rc == want && std::strstr(gasalx_last_error(), text); };
+        auto fits = [&](auto describe) {   // describe(buffer, length): OK into 128 bytes, into the exact size, into one byte
+            EXPECT(describe(buf, (uint32_t)sizeof(buf)) == GASALX_OK && buf[0]);
+            std::vector<char> exact(std::strlen(buf) + 1), one(1, 'x');
+            EXPECT(describe(exact.data(), (uint32_t)exact.size()) == GASALX_OK && std::strcmp(exact.data(), buf) == 0);
+            EXPECT(describe(one.data(), 1) == GASALX_OK && one[0] == 0);
+            EXPECT(null_arg(describe(nullptr, 8)));
+            EXPECT(null_arg(describe(buf, 0)));
+        };
+        fits([&](char *b, uint32_t len) { return gasalx_nv_describe_sinks_plan(&al, 150, 182, 1, 2, b, len); });
+        EXPECT(null_arg(gasalx_nv_describe_sinks_plan(nullptr, 150, 182, 1, 2, buf, sizeof(buf))));
+
+        fits([&](char *b, uint32_t len) { return gasalx_nv_describe_matrix_plan(&al, 24, 150, 182, 1, 1, b, len); });
+        EXPECT(null_arg(gasalx_nv_describe_matrix_plan(nullptr, 24, 150, 182, 1, 1, buf, sizeof(buf))));
+        EXPECT(gasalx_nv_describe_matrix_plan(&al, 24, 5000, 182, 1, 0, buf, sizeof(buf)) == GASALX_OK && !std::strcmp(buf, "none"));
+        for (uint32_t bad : {0u, 1u, 33u})
+            EXPECT(refused(gasalx_nv_describe_matrix_plan(&al, bad, 150, 182, 1, 0, buf, sizeof(buf)), GASALX_EINVAL,
+                           "matrix size must be 2..32"));
+        EXPECT(refused(gasalx_nv_describe_matrix_plan(&type3, 24, 150, 182, 1, 0, buf, sizeof(buf)), GASALX_EINVAL, "bad aligner"));
+        EXPECT(refused(gasalx_nv_describe_matrix_plan(&sw, 24, 150, 182, 1, 0, buf, sizeof(buf)), GASALX_EUNSUPPORTED,
+                       "only the Gotoh aligner takes a substitution matrix"));
+        EXPECT(null_arg(gasalx_nv_describe_matrix_plan(&sw, 33, 150, 182, 1, 0, buf, 0)));   // the null test comes first
+
+        fits([&](char *b, uint32_t len) { return gasalx_nv_describe_banded_sinks_plan(&al, 16, 150, 2, b, len); });
+        EXPECT(null_arg(gasalx_nv_describe_banded_sinks_plan(nullptr, 16, 150, 2, buf, sizeof(buf))));
+        for (uint32_t bad : {1u, 33u})
+            EXPECT(refused(gasalx_nv_describe_banded_sinks_plan(&al, bad, 150, 2, buf, sizeof(buf)), GASALX_EINVAL,
+                           "band length must be 2..32"));
+        EXPECT(refused(gasalx_nv_describe_banded_sinks_plan(&al, 16, 150, 3, buf, sizeof(buf)), GASALX_EINVAL,
+                       "symbol bits must be 2, 4 or 8"));
+        EXPECT(null_arg(gasalx_nv_describe_banded_sinks_plan(&al, 33, 150, 2, buf, 0)));
+
+        fits([&](char *b, uint32_t len) { return gasalx_nv_describe_myers_plan(GASALX_NV_SEMI_GLOBAL, 5, 31, b, len); });
+        EXPECT(refused(gasalx_nv_describe_myers_plan(3, 4, 16, buf, sizeof(buf)), GASALX_EINVAL, "bad aligner"));
+        EXPECT(refused(gasalx_nv_describe_myers_plan(GASALX_NV_GLOBAL, 4, 33, buf, sizeof(buf)), GASALX_EINVAL,
+                       "band length must be 2..32"));
+        EXPECT(refused(gasalx_nv_describe_myers_plan(GASALX_NV_GLOBAL, 3, 16, buf, sizeof(buf)), GASALX_EINVAL,
+                       "alphabet size must be 2, 4 or 5"));
+        EXPECT(refused(gasalx_nv_describe_myers_plan(GASALX_NV_LOCAL, 4, 16, buf, sizeof(buf)), GASALX_EUNSUPPORTED,
+                       "banded Myers has no LOCAL form"));
+        EXPECT(null_arg(gasalx_nv_describe_myers_plan(GASALX_NV_LOCAL, 4, 16, nullptr, 8)));
     }
     // every engine entry point without an engine
     {
@@ -136,6 +186,21 @@ int main() {
                                                           u32.data(), u8.data(), 24, u32.data(), nullptr)));
         EXPECT(null_arg(gasalx_nv_banded_traceback_host(nullptr, &al, 16, 1, &s, 1, &s, 1, i32.data(), u32.data(),
                                                         u32.data(), u8.data(), 24, u32.data())));
+        const int8_t tab[4] = {1, -1, -1, 1};
+        gasalx_nv_matrix m = {tab, 2};
+        EXPECT(null_arg(gasalx_nv_score_sinks_device(nullptr, &al, 1, &s, &s, i32.data(), u32.data(), 0, 0, nullptr)));
+        EXPECT(null_arg(gasalx_nv_score_sinks_host(nullptr, &al, 1, &s, 1, &s, 1, i32.data(), u32.data())));
+        EXPECT(null_arg(gasalx_nv_matrix_score_device(nullptr, &al, &m, 1, &s, &s, i32.data(), u32.data(), 0, 0, nullptr)));
+        EXPECT(null_arg(gasalx_nv_matrix_score_host(nullptr, &al, &m, 1, &s, 1, &s, 1, i32.data(), u32.data())));
+        EXPECT(null_arg(gasalx_nv_banded_score_sinks_device(nullptr, &al, 16, 1, &s, &s, i32.data(), u32.data(), 0, nullptr)));
+        EXPECT(null_arg(gasalx_nv_banded_score_sinks_host(nullptr, &al, 16, 1, &s, 1, &s, 1, i32.data(), u32.data())));
+        EXPECT(null_arg(gasalx_nv_banded_myers_device(nullptr, GASALX_NV_GLOBAL, 4, 16, 1, &s, &s, i32.data(), u32.data(), 0,
+                                                      nullptr)));
+        EXPECT(null_arg(gasalx_nv_banded_myers_host(nullptr, GASALX_NV_GLOBAL, 4, 16, 1, &s, 1, &s, 1, i32.data(), u32.data())));
+        EXPECT(null_arg(gasalx_nv_matrix_traceback_device(nullptr, &al, &m, 1, &s, &s, 0, 0, i32.data(), u32.data(), u32.data(),
+                                                          u8.data(), 8, u32.data(), nullptr)));
+        EXPECT(null_arg(gasalx_nv_matrix_traceback_host(nullptr, &al, &m, 1, &s, 1, &s, 1, i32.data(), u32.data(), u32.data(),
+                                                        u8.data(), 8, u32.data())));
         EXPECT(gasalx_packed_pairs(nullptr, &h, &t) == GASALX_EINVAL && h == 9 && t == 9);
         EXPECT(gasalx_engine_create(0, nullptr) == GASALX_EINVAL);
         EXPECT(gasalx_engine_destroy(nullptr) == GASALX_OK);

@@ -9,7 +9,8 @@
 
 Two builds launch the same sequence when their lists are equal line for line
 (profiles/dispatch_refactor/README.md, profiles/capi_refactor/README.md,
-profiles/nv_launcher_refactor/README.md, profiles/planner_refactor/README.md).
+profiles/nv_launcher_refactor/README.md, profiles/planner_refactor/README.md,
+profiles/nv_capi_refactor/README.md).
 """
 import csv
 import glob
@@ -106,6 +107,15 @@ def run():
     P199, T199 = G.PackedSet.pack(pats[:199]), G.PackedSet.pack(txts[:199], bits=2, big_endian=False)
     eng.nv_score_host(al, P199, T199)                                             # an odd n: the packed grids round up
     eng.nv_banded_score_host(al, 16, P199, T199)
+
+    # the nv host forms no call above makes (profiles/nv_capi_refactor/README.md)
+    mat = G.NvMatrix(np.where(np.eye(4, dtype=bool), 2, -1))
+    eng.nv_matrix_score_host(al, mat, P, T)
+    eng.nv_banded_score_sinks_host(al, 16, P, T)
+    eng.nv_banded_myers_host(G.NV_SEMI_GLOBAL, 4, 16, P, T)
+    os.environ["GASALX_NV_TB_BUDGET"] = str(70 * G.nv_traceback_workspace(max_p, max_p + 20, 1))   # three chunks
+    eng.nv_matrix_traceback_host(al, mat, P, T)
+    del os.environ["GASALX_NV_TB_BUDGET"]
 
     # planner branches the calls above miss (profiles/planner_refactor/README.md)
     device_call(G.Batch.synth(3, 60_000, 0x7A32), ("aln_score",), algo=G.GLOBAL)  # GLOBAL score: its tail shape
