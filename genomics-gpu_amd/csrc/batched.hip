@@ -22,6 +22,7 @@
 #include "nvmyers.hpp"
 #include "nvmatrix.hpp"
 #include "nvmatrix_trace.hpp"
+#include "nvbanded_qual.hpp"
 
 namespace gx {
 
@@ -614,5 +615,137 @@ int nv_banded_traceback_device(const gasalx_nv_aligner &al, uint32_t band, uint3
     return launch_checked(fn, (n + 255) / 256, st, A);
 }
 #undef GX_BAND_PICK
+
+// ---- The banded Gotoh kernels under a quality-aware scheme (nvbanded_qual.hpp): the scorer with
+//      sinks, packed or int32 by nvb16_ok's rule over the tables' extremes, and the banded traceback
+//      with its exact 7 / 15 / 31 instances.  Both families make their checks in nv_qual_check. ----
+namespace {
+
+// the two tables as the kernels read them, and what the planner and the range rules need of them
+struct NvQualPlan {
+    NvQualTable tab;
+    int32_t max_match = 0, min_mismatch = 0, entry_mag = 0;
+    bool byte_steps = true;   // at every level match >= mismatch and match - mismatch <= 255
+};
+
+// The checks both families share, in the order gasalx.h states: the struct and its tables (the
+// quality bytes too where a call reads them), the aligner and type, the Gotoh aligner alone, the
+// number of levels, the band, the symbol bits.  The range rules follow in the callers.
+int nv_qual_check(const gasalx_nv_aligner &al, const gasalx_nv_quals *q, bool bytes, uint32_t band,
+                  const gasalx_nv_strings &pat, const gasalx_nv_strings &txt, NvQualPlan &P) {
+    if (!q || !q->match || !q->mismatch || (bytes && !q->quals)) return nv_fail(GASALX_EINVAL, "null argument");
+    if (al.aligner < 0 || al.aligner > 2 || al.type < 0 || al.type > 2) return nv_fail(GASALX_EINVAL, "bad aligner");
+    if (al.aligner != NV_GOTOH)
+        return nv_fail(GASALX_EUNSUPPORTED, "only the Gotoh aligner scores with qualities: edit distance has no scheme, "
+                                            "and nothing in the tree drives Smith-Waterman with qualities");
+    if (q->levels < 1 || q->levels > kNvQualLevels) return nv_fail(GASALX_EINVAL, "quality levels must be 1..256");
+    if (int rc = nv_check(al, "bad aligner", "bad aligner", &band, pat, txt)) return rc;
+    P.max_match = q->match[0]; P.min_mismatch = q->mismatch[0];
+    for (uint32_t b = 0; b < kNvQualLevels; b++) {
+        const uint32_t l = std::min(b, q->levels - 1);   // a quality byte >= levels reads the last entry
+        const int32_t m = q->match[l], x = q->mismatch[l];
+        P.tab.tab[b] = (uint32_t)(uint16_t)m | ((uint32_t)(uint16_t)x << 16);
+        P.max_match = std::max(P.max_match, m); P.min_mismatch = std::min(P.min_mismatch, x);
+        P.entry_mag = std::max({P.entry_mag, std::abs(m), std::abs(x)});
+        if (m < x || m - x > 255) P.byte_steps = false;
+    }
+    return GASALX_OK;
+}
+
+// the packed kernel: nvb16_ok with the largest match and the smallest mismatch (every entry lies
+// between them when each level has match >= mismatch), and a step that fits a byte at every level
+bool nvq16_ok(const gasalx_nv_aligner &al, const NvQualPlan &P, uint32_t text_bits, uint32_t max_p, uint32_t band,
+              uint32_t *base) {
+    const NvScheme s = {P.max_match, P.min_mismatch, al.gap_open, al.gap_ext, al.deletion, al.insertion};
+    return max_p && P.byte_steps && nvb16_ok(s, text_bits, max_p, band, base);
+}
+
+}  // namespace
+
+int nv_banded_qual_check(const gasalx_nv_aligner &al, const gasalx_nv_quals *q, bool bytes, uint32_t band,
+                         const gasalx_nv_strings &pat, const gasalx_nv_strings &txt, int32_t *entry_mag) {
+    NvQualPlan P;
+    if (int rc = nv_qual_check(al, q, bytes, band, pat, txt, P)) return rc;
+    if (entry_mag) *entry_mag = P.entry_mag;
+    return GASALX_OK;
+}
+
+int nv_banded_qual_plan_name(const gasalx_nv_aligner &al, const gasalx_nv_quals *q, uint32_t band, uint32_t max_p,
+                             uint32_t text_bits, bool traceback, std::string &name) {
+    static const char *tn[] = {"global", "local", "semi"};
+    const gasalx_nv_strings pat = {nullptr, nullptr, 0, 2, 0}, txt = {nullptr, nullptr, 0, text_bits, 0};
+    NvQualPlan P;
+    if (int rc = nv_qual_check(al, q, false, band, pat, txt, P)) return rc;
+    if (traceback) {
+        const bool exact = band == 7 || band == 15 || band == 31;
+        name = std::string("nvbio_banded_qual_traceback_gotoh_") + tn[al.type] + "_b" +
+               std::to_string(exact ? band : band <= 8 ? 8 : band <= 16 ? 16 : 32);
+        return GASALX_OK;
+    }
+    uint32_t base = 0;
+    name = std::string(nvq16_ok(al, P, text_bits, max_p, band, &base) ? "nvbio_banded16_qual_gotoh_" : "nvbio_banded_qual_gotoh_") +
+           tn[al.type] + "_b" + std::to_string(band <= 8 ? 8 : band <= 16 ? 16 : 32) + "_sink";
+    return GASALX_OK;
+}
+
+#define GX_QBAND_PICK(K, t, ex) (band <= 8 ? &K<t, 8, ex> : band <= 16 ? &K<t, 16, ex> : &K<t, 32, ex>)
+
+int nv_banded_qual_score_device(const gasalx_nv_aligner &al, const gasalx_nv_quals *q, uint32_t band, uint32_t n,
+                                const gasalx_nv_strings &pat, const gasalx_nv_strings &txt, int32_t *scores,
+                                uint32_t *sinks, hipStream_t st, uint32_t max_p) {
+    NvQualPlan P;
+    if (int rc = nv_qual_check(al, q, true, band, pat, txt, P)) return rc;
+    if (n == 0) return GASALX_OK;
+    if (int rc = nv_check_ptrs(pat, txt, scores || sinks)) return rc;
+    const NvScheme s = {0, 0, al.gap_open, al.gap_ext, al.deletion, al.insertion};   // match / mismatch: the tables
+    const bool ex = band == 8 || band == 16 || band == 32;
+    uint32_t base = 0;
+    if (nvq16_ok(al, P, txt.bits, max_p, band, &base)) {
+        NvBand16QualArgs D;
+        nv_fill(D.s.a, pat, txt, s, n);
+        D.s.a.score = scores; D.s.a.n_lanes = (n + 1) / 2; D.s.a.band = band; D.s.a.base = base; D.s.sinks = sinks;
+        D.quals = q->quals; D.q = P.tab;
+        using Fn = void (*)(NvBand16QualArgs);
+        const Fn fn = nv_static(NV_GOTOH, al.type, ex, [band](auto, auto t, auto e) -> Fn {
+            return GX_QBAND_PICK(nv_banded16_qual_sink_kernel, t, e); });
+        return launch_checked(fn, (D.s.a.n_lanes + 255) / 256, st, D);
+    }
+    NvBandQualArgs A;
+    nv_fill(A.s.a, pat, txt, s, n);
+    A.s.a.score = scores; A.s.a.band = band; A.s.sinks = sinks;
+    A.quals = q->quals; A.q = P.tab;
+    using Fn = void (*)(NvBandQualArgs);
+    const Fn fn = nv_static(NV_GOTOH, al.type, ex, [band](auto, auto t, auto e) -> Fn {
+        return GX_QBAND_PICK(nv_banded_qual_sink_kernel, t, e); });
+    return launch_checked(fn, (n + 255) / 256, st, A);
+}
+
+// workspace and outputs as nv_banded_traceback_device
+int nv_banded_qual_traceback_device(const gasalx_nv_aligner &al, const gasalx_nv_quals *q, uint32_t band, uint32_t n,
+                                    const gasalx_nv_strings &pat, const gasalx_nv_strings &txt, uint32_t max_p,
+                                    uint32_t *dir, int32_t *score, uint32_t *src, uint32_t *snk, uint8_t *ops,
+                                    uint32_t ops_stride, uint32_t *n_ops, hipStream_t st) {
+    NvQualPlan P;
+    if (int rc = nv_qual_check(al, q, true, band, pat, txt, P)) return rc;
+    if (n == 0) return GASALX_OK;
+    if (int rc = nv_check_ptrs(pat, txt, score && src && snk && ops && n_ops && dir)) return rc;
+    NvBandTbQualArgs B;
+    NvBandTbArgs &A = B.t;
+    nv_fill(A, pat, txt, NvScheme{0, 0, al.gap_open, al.gap_ext, 0, 0}, n);
+    A.band = band; A.words = (band + 3) / 4; A.max_m = max_p;
+    A.dir = dir; A.score = score; A.src = src; A.snk = snk; A.ops = ops; A.ops_stride = ops_stride; A.n_ops = n_ops;
+    B.quals = q->quals; B.q = P.tab;
+    using Fn = void (*)(NvBandTbQualArgs);
+    const bool exact = band == 7 || band == 15 || band == 31;
+    const Fn fn = nv_static(NV_GOTOH, al.type, exact, [band](auto, auto t, auto ex) -> Fn {
+        if constexpr (ex)
+            return band == 7 ? &nv_banded_qual_traceback_kernel<t, 7, true>
+                 : band == 15 ? &nv_banded_qual_traceback_kernel<t, 15, true> : &nv_banded_qual_traceback_kernel<t, 31, true>;
+        else
+            return GX_QBAND_PICK(nv_banded_qual_traceback_kernel, t, false);
+    });
+    return launch_checked(fn, (n + 255) / 256, st, B);
+}
+#undef GX_QBAND_PICK
 
 }  // namespace gx

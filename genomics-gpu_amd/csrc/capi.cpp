@@ -47,6 +47,8 @@ enum Buf {
     B_NV_PW, B_NV_PO, B_NV_TW, B_NV_TO, B_NV_S, B_NV_S16, B_NV_SRC, B_NV_SNK, B_NV_OPS, B_NV_NOPS,
     // nvbio traceback, device forms too: flags of every cell, one DP row per pair
     B_NV_DIR, B_NV_ROW,
+    // nvbio quality host forms: one quality byte per pattern symbol
+    B_NV_Q,
     B_COUNT
 };
 
@@ -218,6 +220,21 @@ int nv_stage_strings(gasalx_engine *eng, const NvHostIn &h, hipStream_t st, NvSt
     in(B_NV_PO, s.pat.offsets, (size_t)h.n + 1);
     in(B_NV_TW, s.txt.words, h.txt_words);
     in(B_NV_TO, s.txt.offsets, (size_t)h.n + 1);
+    return in.rc;
+}
+
+// the quality bytes of a host batch (one per pattern symbol, offsets[n] of them) as a device array;
+// the tables stay the caller's host arrays
+int nv_stage_quals(gasalx_engine *eng, const NvHostIn &h, const gasalx_nv_quals *q, hipStream_t st, gasalx_nv_quals &dq) {
+    dq = *q;
+    const size_t bytes = h.pat->offsets[h.n];
+    if (!bytes) {   // a batch of empty patterns: a pointer the kernels never read through
+        CK(eng->buf[B_NV_Q].reserve(16));
+        dq.quals = eng->buf[B_NV_Q].as<uint8_t>();
+        return GASALX_OK;
+    }
+    Stager in{eng, st};
+    in(B_NV_Q, dq.quals, bytes);
     return in.rc;
 }
 
@@ -595,9 +612,11 @@ struct NvTbOut {
 };
 
 // A traceback batch in chunks of `chunk` pairs over the engine's workspace (band 0: the full DP;
-// mat: its substitution-matrix form, NULL otherwise): the chunk from pair s on works on
-// offsets + s, scores + s, sources + 2s, sinks + 2s, ops + s * ops_stride and n_ops + s.
-int nv_tb_chunks(gasalx_engine *eng, const gasalx_nv_aligner *al, const gasalx_nv_matrix *mat, uint32_t band, uint32_t n,
+// mat: its substitution-matrix form, NULL otherwise; q: the banded form under a quality scheme, NULL
+// otherwise): the chunk from pair s on works on offsets + s, scores + s, sources + 2s, sinks + 2s,
+// ops + s * ops_stride and n_ops + s (the quality bytes follow the offsets' own values).
+int nv_tb_chunks(gasalx_engine *eng, const gasalx_nv_aligner *al, const gasalx_nv_matrix *mat,
+                 const gasalx_nv_quals *q, uint32_t band, uint32_t n,
                  const gasalx_nv_strings *pat, const gasalx_nv_strings *txt, uint32_t max_p, uint32_t max_t,
                  const NvTbOut &o, uint32_t chunk, hipStream_t st) {
     gx::DevBuf &dir = eng->buf[B_NV_DIR];
@@ -609,7 +628,9 @@ int nv_tb_chunks(gasalx_engine *eng, const gasalx_nv_aligner *al, const gasalx_n
         int32_t *scores = o.scores + s;
         uint32_t *sources = o.sources + 2ull * s, *sinks = o.sinks + 2ull * s, *n_ops = o.n_ops + s;
         uint8_t *ops = o.ops + (size_t)s * o.ops_stride;
-        const int rc = band ? gx::nv_banded_traceback_device(*al, band, m, p, t, max_p, dir.as<uint32_t>(), scores, sources,
+        const int rc = q    ? gx::nv_banded_qual_traceback_device(*al, q, band, m, p, t, max_p, dir.as<uint32_t>(), scores,
+                                                                  sources, sinks, ops, o.ops_stride, n_ops, st)
+                     : band ? gx::nv_banded_traceback_device(*al, band, m, p, t, max_p, dir.as<uint32_t>(), scores, sources,
                                                              sinks, ops, o.ops_stride, n_ops, st)
                      : mat  ? gx::nv_matrix_traceback_device(*al, *mat, m, p, t, max_p, max_t, dir.as<uint8_t>(),
                                                              eng->buf[B_NV_ROW].as<int32_t>(), scores, sources, sinks,
@@ -697,15 +718,17 @@ int nv_tb_device_run(gasalx_engine *eng, const gasalx_nv_aligner *al, const gasa
     const uint32_t chunk = (uint32_t)nv_tb_chunk(n, gasalx_nv_traceback_workspace(max_p, max_t, 1));
     CK(eng->buf[B_NV_DIR].reserve((size_t)nv_tb_dir_bytes(max_p, max_t) * chunk + 64));
     CK(eng->buf[B_NV_ROW].reserve((size_t)nv_tb_row_bytes(max_t) * chunk + 64));
-    return nv_tb_chunks(eng, al, mat, 0, n, pat, txt, max_p, max_t, o, chunk, st);
+    return nv_tb_chunks(eng, al, mat, nullptr, 0, n, pat, txt, max_p, max_t, o, chunk, st);
 }
 
 // The traceback host forms after their argument tests (band 0: the full DP, refused by nv_tb_checks
 // over `ranged` before anything is staged; mat: its substitution-matrix form, NULL otherwise; the
 // banded form has made its checks): the sets staged, the five device outputs reserved, the device
-// form run on them, the results copied to the caller's arrays `h`.
+// form run on them, the results copied to the caller's arrays `h`.  q: the banded form under a
+// quality scheme (NULL otherwise), its quality bytes staged beside the sets.
 int nv_tb_host_run(gasalx_engine *eng, const gasalx_nv_aligner *al, const gasalx_nv_matrix *mat, uint32_t band,
-                   const gasalx_nv_aligner *ranged, const NvHostIn &in, const NvTbOut &h) {
+                   const gasalx_nv_aligner *ranged, const NvHostIn &in, const NvTbOut &h,
+                   const gasalx_nv_quals *q = nullptr) {
     const uint32_t n = in.n;
     if (n == 0) return GASALX_OK;
     hipStream_t st;
@@ -715,6 +738,8 @@ int nv_tb_host_run(gasalx_engine *eng, const gasalx_nv_aligner *al, const gasalx
     nv_host_spans(in, d);
     if (!band && (rc = nv_tb_checks(ranged, d.max_p, d.max_t, h.ops_stride))) return rc;
     if ((rc = nv_stage_strings(eng, in, st, d))) return rc;
+    gasalx_nv_quals dq = {};
+    if (q && (rc = nv_stage_quals(eng, in, q, st, dq))) return rc;
     gx::DevBuf &s = eng->buf[B_NV_S], &src = eng->buf[B_NV_SRC], &snk = eng->buf[B_NV_SNK], &ops = eng->buf[B_NV_OPS],
                &nops = eng->buf[B_NV_NOPS];
     CK(s.reserve((size_t)n * 4));
@@ -722,7 +747,10 @@ int nv_tb_host_run(gasalx_engine *eng, const gasalx_nv_aligner *al, const gasalx
     CK(snk.reserve((size_t)n * 8));
     CK(ops.reserve((size_t)n * h.ops_stride + 64));
     CK(nops.reserve((size_t)n * 4));
-    rc = band ? gasalx_nv_banded_traceback_device(eng, al, band, n, &d.pat, &d.txt, d.max_p, s.as<int32_t>(),
+    rc = q    ? gasalx_nv_banded_qual_traceback_device(eng, al, &dq, band, n, &d.pat, &d.txt, d.max_p, s.as<int32_t>(),
+                                                       src.as<uint32_t>(), snk.as<uint32_t>(), ops.as<uint8_t>(),
+                                                       h.ops_stride, nops.as<uint32_t>(), st)
+       : band ? gasalx_nv_banded_traceback_device(eng, al, band, n, &d.pat, &d.txt, d.max_p, s.as<int32_t>(),
                                                   src.as<uint32_t>(), snk.as<uint32_t>(), ops.as<uint8_t>(), h.ops_stride,
                                                   nops.as<uint32_t>(), st)
          : mat ? gasalx_nv_matrix_traceback_device(eng, al, mat, n, &d.pat, &d.txt, d.max_p, d.max_t, s.as<int32_t>(),
@@ -745,6 +773,17 @@ int nv_mtb_checks(const gasalx_nv_aligner *al, const gasalx_nv_matrix *mat, cons
     int32_t mag = 0;
     if (int rc = gx::nv_matrix_traceback_check(*al, *mat, *pat, *txt, &mag)) return rc;
     *ranged = {al->aligner, al->type, mag, mag, al->gap_open, al->gap_ext, 0, 0};
+    return GASALX_OK;
+}
+
+// The quality forms' checks after the null arguments, in gasalx.h's order (before anything is read
+// back or staged); `ranged` is then the aligner nv_btb_checks takes, the largest |entry| standing
+// for match and mismatch
+int nv_qual_checks(const gasalx_nv_aligner *al, const gasalx_nv_quals *q, uint32_t band, const gasalx_nv_strings *pat,
+                   const gasalx_nv_strings *txt, gasalx_nv_aligner *ranged) {
+    int32_t mag = 0;
+    if (int rc = gx::nv_banded_qual_check(*al, q, true, band, *pat, *txt, &mag)) return rc;
+    if (ranged) *ranged = {al->aligner, al->type, mag, mag, al->gap_open, al->gap_ext, 0, 0};
     return GASALX_OK;
 }
 
@@ -1370,7 +1409,7 @@ int gasalx_nv_banded_traceback_device(gasalx_engine *eng, const gasalx_nv_aligne
     if ((rc = nv_btb_checks(al, band, max_p, ops_stride))) return rc;
     const uint32_t chunk = (uint32_t)nv_tb_chunk(n, gasalx_nv_banded_traceback_workspace(max_p, band, 1));
     CK(eng->buf[B_NV_DIR].reserve((size_t)nv_btb_dir_bytes(max_p, band) * chunk + 64));
-    return nv_tb_chunks(eng, al, nullptr, band, n, pat, txt, max_p, 0, {scores, sources, sinks, ops, ops_stride, n_ops}, chunk, st);
+    return nv_tb_chunks(eng, al, nullptr, nullptr, band, n, pat, txt, max_p, 0, {scores, sources, sinks, ops, ops_stride, n_ops}, chunk, st);
 }
 
 int gasalx_nv_banded_traceback_host(gasalx_engine *eng, const gasalx_nv_aligner *al, uint32_t band, uint32_t n,
@@ -1381,6 +1420,73 @@ int gasalx_nv_banded_traceback_host(gasalx_engine *eng, const gasalx_nv_aligner 
     if (!eng || !al || !nv_sets_ok(pat, txt) || !nv_tb_out_ok(out)) return nv_null();
     if (int rc = nv_btb_checks(al, band, max_span(pat->offsets, n), ops_stride)) return rc;
     return nv_tb_host_run(eng, al, nullptr, band, nullptr, {n, pat, pat_words, txt, txt_words}, out);
+}
+
+int gasalx_nv_banded_qual_score_device(gasalx_engine *eng, const gasalx_nv_aligner *al, const gasalx_nv_quals *q,
+                                       uint32_t band, uint32_t n, const gasalx_nv_strings *pat,
+                                       const gasalx_nv_strings *txt, int32_t *scores, uint32_t *sinks, uint32_t max_p,
+                                       void *stream) {
+    if (!eng || !al || !q || !pat || !txt) return nv_null();
+    if (int rc = nv_qual_checks(al, q, band, pat, txt, nullptr)) return rc;
+    hipStream_t st;
+    if (int rc = nv_device_enter(eng, stream, NV_PATTERN_IF_OFFSETS, n, pat, txt, &max_p, nullptr, &st)) return rc;
+    return gx::nv_banded_qual_score_device(*al, q, band, n, *pat, *txt, scores, sinks, st, max_p);
+}
+
+int gasalx_nv_describe_banded_qual_plan(const gasalx_nv_aligner *al, const gasalx_nv_quals *q, uint32_t band,
+                                        uint32_t max_p, uint32_t text_bits, int want_traceback, char *buf,
+                                        uint32_t buf_len) {
+    return nv_describe(al && q, buf, buf_len, [&](std::string &s) {
+        return gx::nv_banded_qual_plan_name(*al, q, band, max_p, text_bits, want_traceback != 0, s);
+    });
+}
+
+int gasalx_nv_banded_qual_score_host(gasalx_engine *eng, const gasalx_nv_aligner *al, const gasalx_nv_quals *q,
+                                     uint32_t band, uint32_t n, const gasalx_nv_strings *pat, uint64_t pat_words,
+                                     const gasalx_nv_strings *txt, uint64_t txt_words, int32_t *scores,
+                                     uint32_t *sinks) {
+    if (!eng || !al || !q || !nv_sets_ok(pat, txt) || (!scores && !sinks)) return nv_null();
+    if (int rc = nv_qual_checks(al, q, band, pat, txt, nullptr)) return rc;
+    const NvHostIn in = {n, pat, pat_words, txt, txt_words};
+    return nv_score_host_run(eng, in, {{scores, B_NV_S, 4}, {sinks, B_NV_SNK, 8}},
+                             [&](const NvStaged &s, void *const *d, hipStream_t st) {
+                                 gasalx_nv_quals dq;
+                                 if (int rc = nv_stage_quals(eng, in, q, st, dq)) return rc;
+                                 return gx::nv_banded_qual_score_device(*al, &dq, band, n, s.pat, s.txt, (int32_t *)d[0],
+                                                                        (uint32_t *)d[1], st, s.max_p);
+                             });
+}
+
+int gasalx_nv_banded_qual_traceback_device(gasalx_engine *eng, const gasalx_nv_aligner *al, const gasalx_nv_quals *q,
+                                           uint32_t band, uint32_t n, const gasalx_nv_strings *pat,
+                                           const gasalx_nv_strings *txt, uint32_t max_p, int32_t *scores,
+                                           uint32_t *sources, uint32_t *sinks, uint8_t *ops, uint32_t ops_stride,
+                                           uint32_t *n_ops, void *stream) {
+    if (!eng || !al || !q || !pat || !txt) return nv_null();
+    gasalx_nv_aligner ranged;
+    if (int rc = nv_qual_checks(al, q, band, pat, txt, &ranged)) return rc;
+    if (n == 0) return GASALX_OK;
+    hipStream_t st;
+    int rc = nv_device_enter(eng, stream, NV_PATTERN, n, pat, txt, &max_p, nullptr, &st);
+    if (rc) return rc;
+    if ((rc = nv_btb_checks(&ranged, band, max_p, ops_stride))) return rc;
+    const uint32_t chunk = (uint32_t)nv_tb_chunk(n, gasalx_nv_banded_traceback_workspace(max_p, band, 1));
+    CK(eng->buf[B_NV_DIR].reserve((size_t)nv_btb_dir_bytes(max_p, band) * chunk + 64));
+    return nv_tb_chunks(eng, al, nullptr, q, band, n, pat, txt, max_p, 0, {scores, sources, sinks, ops, ops_stride, n_ops},
+                        chunk, st);
+}
+
+int gasalx_nv_banded_qual_traceback_host(gasalx_engine *eng, const gasalx_nv_aligner *al, const gasalx_nv_quals *q,
+                                         uint32_t band, uint32_t n, const gasalx_nv_strings *pat, uint64_t pat_words,
+                                         const gasalx_nv_strings *txt, uint64_t txt_words, int32_t *scores,
+                                         uint32_t *sources, uint32_t *sinks, uint8_t *ops, uint32_t ops_stride,
+                                         uint32_t *n_ops) {
+    const NvTbOut out = {scores, sources, sinks, ops, ops_stride, n_ops};
+    if (!eng || !al || !q || !nv_sets_ok(pat, txt) || !nv_tb_out_ok(out)) return nv_null();
+    gasalx_nv_aligner ranged;
+    if (int rc = nv_qual_checks(al, q, band, pat, txt, &ranged)) return rc;
+    if (int rc = nv_btb_checks(&ranged, band, max_span(pat->offsets, n), ops_stride)) return rc;
+    return nv_tb_host_run(eng, al, nullptr, band, nullptr, {n, pat, pat_words, txt, txt_words}, out, q);
 }
 
 int gasalx_pairhmm_params(const uint8_t *bq, const uint8_t *iq, const uint8_t *dq, uint32_t n, float *qm,

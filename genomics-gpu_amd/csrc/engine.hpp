@@ -250,6 +250,23 @@ int nv_banded_traceback_device(const gasalx_nv_aligner &al, uint32_t band, uint3
                                hipStream_t st);
 std::string nv_plan_name(const gasalx_nv_aligner &al, uint32_t max_p, uint32_t max_t, bool per_pair_text,
                          uint32_t text_bits);
+// The banded Gotoh scorer (with sinks) and the banded traceback under a quality-aware scheme
+// (nvbanded_qual.hpp): q->quals a device array indexed by the pattern offsets, the two tables host
+// arrays read during the call; al.match / al.mismatch are not read.  Outputs and workspace as
+// nv_banded_score_sinks_device and nv_banded_traceback_device.  The check runs what needs no lengths,
+// in the entry points' order (bytes: the call reads q->quals), and gives the largest |entry|.
+int nv_banded_qual_check(const gasalx_nv_aligner &al, const gasalx_nv_quals *q, bool bytes, uint32_t band,
+                         const gasalx_nv_strings &pat, const gasalx_nv_strings &txt, int32_t *entry_mag);
+int nv_banded_qual_score_device(const gasalx_nv_aligner &al, const gasalx_nv_quals *q, uint32_t band, uint32_t n,
+                                const gasalx_nv_strings &pat, const gasalx_nv_strings &txt, int32_t *scores,
+                                uint32_t *sinks, hipStream_t st, uint32_t max_p);
+int nv_banded_qual_traceback_device(const gasalx_nv_aligner &al, const gasalx_nv_quals *q, uint32_t band, uint32_t n,
+                                    const gasalx_nv_strings &pat, const gasalx_nv_strings &txt, uint32_t max_p,
+                                    uint32_t *dir, int32_t *score, uint32_t *src, uint32_t *snk, uint8_t *ops,
+                                    uint32_t ops_stride, uint32_t *n_ops, hipStream_t st);
+// the kernel's name ("nvbio_banded16_qual_gotoh_local_b16_sink"), or the code the call would return
+int nv_banded_qual_plan_name(const gasalx_nv_aligner &al, const gasalx_nv_quals *q, uint32_t band, uint32_t max_p,
+                             uint32_t text_bits, bool traceback, std::string &name);
 
 // The engine's own stream (capi.cpp; gasalx_engine is opaque elsewhere).
 hipStream_t engine_stream(gasalx_engine *e);

@@ -44,6 +44,9 @@ EXPORTS = (
     "gasalx_nv_traceback_device", "gasalx_nv_traceback_host",
     "gasalx_nv_matrix_traceback_device", "gasalx_nv_matrix_traceback_host",
     "gasalx_nv_banded_traceback_device", "gasalx_nv_banded_traceback_host",
+    "gasalx_nv_banded_qual_score_device", "gasalx_nv_banded_qual_score_host",
+    "gasalx_nv_banded_qual_traceback_device", "gasalx_nv_banded_qual_traceback_host",
+    "gasalx_nv_describe_banded_qual_plan",
     "gasalx_multi_create", "gasalx_multi_destroy", "gasalx_multi_info", "gasalx_multi_engine",
     "gasalx_shard_bounds", "gasalx_multi_align_host", "gasalx_multi_pairhmm_host",
     "gasalx_multi_pairhmm_quals_host", "gasalx_multi_allgather", "gasalx_packed_pairs",
@@ -115,6 +118,11 @@ class CNvStrings(ctypes.Structure):
 
 class CNvMatrix(ctypes.Structure):
     _fields_ = [("scores", ctypes.c_void_p), ("n", ctypes.c_uint32)]
+
+
+class CNvQuals(ctypes.Structure):
+    _fields_ = [("quals", ctypes.c_void_p), ("match", ctypes.c_void_p), ("mismatch", ctypes.c_void_p),
+                ("levels", ctypes.c_uint32)]
 
 
 _lib = None
@@ -669,6 +677,42 @@ class Engine:
         self._nv_call("nv_banded_traceback_device", _ref(aligner), _u32(band), _u32(n), _ref(_nv_strings(pat)),
                       _ref(_nv_strings(txt)), _u32(max_pattern_len), *_nv_traceback_ptrs(outs, ops_stride), _vp(stream))
 
+    def nv_banded_qual_score_host(self, aligner: "NvAligner", quals: "NvQuals", band: int, patterns: "PackedSet",
+                                  texts: "PackedSet", scores=True, sinks=True):
+        """The banded Gotoh scorer under a quality-aware scheme (gasalx_nv_banded_qual_score_host): row i
+        scores match[l] / mismatch[l], l = min(quals[i], levels - 1); (scores int32[n], sinks uint32[n, 2])
+        as nv_banded_score_sinks_host returns them.  quals.quals: one byte per pattern symbol."""
+        n = patterns.n
+        sc, sk, ret = _nv_score_outs(n, scores, sinks)
+        self._nv_call("nv_banded_qual_score_host", _ref(aligner), _ref(quals), _u32(band), _u32(n),
+                      *_nv_host_sets(patterns, texts), sc, sk)
+        return ret
+
+    def nv_banded_qual_score_device_ptrs(self, aligner: "NvAligner", quals: "NvQuals", band: int, n: int, pat: dict,
+                                         txt: dict, scores_ptr: int = 0, sinks_ptr: int = 0,
+                                         max_pattern_len: int = 0, stream: int = 0):
+        """Device-resident form (gasalx_nv_banded_qual_score_device): quals.quals_ptr a device address, the
+        tables host arrays; the other arguments as nv_banded_score_sinks_device_ptrs."""
+        self._nv_call("nv_banded_qual_score_device", _ref(aligner), _ref(quals), _u32(band), _u32(n),
+                      _ref(_nv_strings(pat)), _ref(_nv_strings(txt)), _vp(scores_ptr), _vp(sinks_ptr),
+                      _u32(max_pattern_len), _vp(stream))
+
+    def nv_banded_qual_traceback_host(self, aligner: "NvAligner", quals: "NvQuals", band: int, patterns: "PackedSet",
+                                      texts: "PackedSet", ops_stride: int = None):
+        """The banded traceback under a quality-aware scheme (gasalx_nv_banded_qual_traceback_host): the
+        dict nv_banded_traceback_host returns."""
+        return self._nv_traceback_host("nv_banded_qual_traceback_host", (_ref(aligner), _ref(quals), _u32(band)),
+                                       patterns, texts, band=band, ops_stride=ops_stride)
+
+    def nv_banded_qual_traceback_device_ptrs(self, aligner: "NvAligner", quals: "NvQuals", band: int, n: int,
+                                             pat: dict, txt: dict, outs: dict, ops_stride: int,
+                                             max_pattern_len: int = 0, stream: int = 0):
+        """Device-resident form (gasalx_nv_banded_qual_traceback_device); quals as
+        nv_banded_qual_score_device_ptrs, the other arguments as nv_banded_traceback_device_ptrs."""
+        self._nv_call("nv_banded_qual_traceback_device", _ref(aligner), _ref(quals), _u32(band), _u32(n),
+                      _ref(_nv_strings(pat)), _ref(_nv_strings(txt)), _u32(max_pattern_len),
+                      *_nv_traceback_ptrs(outs, ops_stride), _vp(stream))
+
     def nv_banded_score_device_ptrs(self, aligner: "NvAligner", band: int, n: int, pat: dict, txt: dict,
                                     scores_ptr: int, stream: int = 0, max_pattern_len: int = 0):
         """Device-resident banded scoring (gasalx_nv_banded_score_device); pat/txt as nv_score_device_ptrs."""
@@ -904,6 +948,18 @@ def nv_describe_banded_sinks_plan(aligner: "NvAligner", band: int, max_p: int, t
     return buf.value.decode()
 
 
+def nv_describe_banded_qual_plan(aligner: "NvAligner", quals: "NvQuals", band: int, max_p: int, text_bits: int = 2,
+                                 traceback: bool = False) -> str:
+    """The kernel Engine.nv_banded_qual_score_* (or, with traceback, nv_banded_qual_traceback_*) runs
+    (gasalx_nv_describe_banded_qual_plan); raises what the call would."""
+    buf = ctypes.create_string_buffer(128)
+    al = aligner.cstruct()
+    _check(lib().gasalx_nv_describe_banded_qual_plan(ctypes.byref(al), _ref(quals), ctypes.c_uint32(band),
+                                                     ctypes.c_uint32(max_p), ctypes.c_uint32(text_bits),
+                                                     int(traceback), buf, 128), "nv_describe_banded_qual_plan")
+    return buf.value.decode()
+
+
 def nv_describe_myers_plan(type_: int, alphabet: int, band: int) -> str:
     """The kernel Engine.nv_banded_myers_* runs (gasalx_nv_describe_myers_plan); raises what the call would."""
     buf = ctypes.create_string_buffer(128)
@@ -1013,6 +1069,26 @@ class NvMatrix:
 
     def cstruct(self):
         return CNvMatrix(_p(self.scores), self.n)
+
+
+class NvQuals:
+    """Base qualities and the two score tables of a quality-aware Gotoh scheme (gasalx_nv_quals):
+    quals, one byte per pattern symbol at the pattern set's offsets (a host array, or None with
+    quals_ptr a device address for the *_device_ptrs calls); match[l] / mismatch[l], signed scores at
+    quality level l, len(match) levels (1..256 is checked by the library, int16 here)."""
+
+    def __init__(self, quals, match, mismatch, quals_ptr: int = 0):
+        m, x = np.asarray(match), np.asarray(mismatch)
+        if m.shape != x.shape or m.ndim != 1 or (m.size and (min(m.min(), x.min()) < -32768 or max(m.max(), x.max()) > 32767)):
+            raise ValueError("NvQuals: two tables of equal length, entries in int16")
+        self.quals = None if quals is None else np.ascontiguousarray(quals, np.uint8)
+        self.quals_ptr = quals_ptr
+        self.match, self.mismatch = np.ascontiguousarray(m, np.int16), np.ascontiguousarray(x, np.int16)
+        self.levels = int(m.size)
+
+    def cstruct(self):
+        q = _p(self.quals) if self.quals is not None else _vp(self.quals_ptr)
+        return CNvQuals(q, _p(self.match), _p(self.mismatch), self.levels)
 
 
 @dataclass

@@ -563,6 +563,73 @@ int gasalx_nv_banded_traceback_host(gasalx_engine *eng, const gasalx_nv_aligner 
                                     uint32_t *sources, uint32_t *sinks, uint8_t *ops, uint32_t ops_stride,
                                     uint32_t *n_ops);
 
+/* Quality-aware Gotoh scoring for the banded scorer and the banded traceback: what nvBowtie's
+ * aligners run, GotohAligner over SmithWatermanScoringScheme<QualCost, ConstantCost>
+ * (NvB/nvBowtie/bowtie2/cuda/scoring.h:203-346), whose substitution score depends on the base quality
+ * of the pattern symbol: substitution(r_i, q_j, r, q, qq) = r == q ? m_match(qq) : -m_mmp(qq) (:289).
+ * The banded Gotoh reads the quality once per row (gotoh/gotoh_banded_inl.h:470). */
+typedef struct gasalx_nv_quals {
+    const uint8_t *quals;     /* one byte per pattern symbol, indexed by the pattern set's own symbol
+                                 offsets: quals[offsets[k] + i] belongs to symbol i of pattern k.
+                                 Device memory for *_device, host memory for *_host. */
+    const int16_t *match;     /* HOST: levels entries, the score of r == q at quality level l */
+    const int16_t *mismatch;  /* HOST: levels entries, the score of r != q (signed: penalties negative) */
+    uint32_t levels;          /* 1..256; a quality byte >= levels reads entry levels - 1 */
+} gasalx_nv_quals;
+
+/* gasalx_nv_banded_score_sinks_* and gasalx_nv_banded_traceback_* for the Gotoh aligner with the
+ * substitution score of row i taken from the tables: S(i, j) = text == pattern ? match[l_i] :
+ * mismatch[l_i], l_i = min(quals[i], levels - 1); a text slot past the text's end reads 255 and
+ * mismatches.  The aligner's own match and mismatch are never read; gap_open and gap_ext are used
+ * as given (the banded Gotoh reads the pattern gap scores only, gotoh_banded_inl.h:444-445).
+ * GLOBAL, LOCAL and SEMI_GLOBAL.  Everything else is the plain entry points': the scorer's outputs,
+ * sentinels (INT32_MIN, 0xFFFFFFFF), report order and "x may exceed N" rule, scores or sinks NULL
+ * but not both; the traceback's five outputs, ops_stride rule, workspace
+ * (gasalx_nv_banded_traceback_workspace serves both families) and chunking under
+ * GASALX_NV_TB_BUDGET.  The tables are read during the call and are the caller's again on return;
+ * calls on different streams share nothing.  The scorer runs two pairs per lane in 16-bit halves
+ * for 2-bit texts when gasalx_nv_banded_score_sinks_*'s window rule holds with match = the largest
+ * match entry and mismatch = the smallest mismatch entry, and at every level match >= mismatch and
+ * match - mismatch <= 255 (GASALX_NVB16=0: int32 only); one pair per thread otherwise.
+ * Checks, in this order: a NULL argument, struct or table GASALX_EINVAL; a bad aligner or type
+ * GASALX_EINVAL; an aligner other than GASALX_NV_GOTOH GASALX_EUNSUPPORTED; levels outside 1..256
+ * GASALX_EINVAL; band_len outside 2..32 GASALX_EINVAL; symbol bits other than 2 / 4 / 8
+ * GASALX_EINVAL; then the plain entry points' range rules with the largest |entry| standing for
+ * match and mismatch: for the traceback (max pattern + band + 3) * max(|entry|, |gap_open|,
+ * |gap_ext|) > 32736 GASALX_ERANGE, then ops_stride < 2 x max pattern + band GASALX_EINVAL. */
+int gasalx_nv_banded_qual_score_device(gasalx_engine *eng, const gasalx_nv_aligner *aligner,
+                                       const gasalx_nv_quals *quals, uint32_t band_len, uint32_t n_pairs,
+                                       const gasalx_nv_strings *dev_patterns, const gasalx_nv_strings *dev_texts,
+                                       int32_t *dev_scores, uint32_t *dev_sinks, uint32_t max_pattern_len,
+                                       void *stream);   /* max_pattern_len: 0 = read back */
+int gasalx_nv_banded_qual_score_host(gasalx_engine *eng, const gasalx_nv_aligner *aligner,
+                                     const gasalx_nv_quals *quals, uint32_t band_len, uint32_t n_pairs,
+                                     const gasalx_nv_strings *patterns, uint64_t pattern_words,
+                                     const gasalx_nv_strings *texts, uint64_t text_words, int32_t *scores,
+                                     uint32_t *sinks);
+int gasalx_nv_banded_qual_traceback_device(gasalx_engine *eng, const gasalx_nv_aligner *aligner,
+                                           const gasalx_nv_quals *quals, uint32_t band, uint32_t n_pairs,
+                                           const gasalx_nv_strings *dev_patterns,
+                                           const gasalx_nv_strings *dev_texts, uint32_t max_pattern_len,
+                                           int32_t *dev_scores, uint32_t *dev_sources, uint32_t *dev_sinks,
+                                           uint8_t *dev_ops, uint32_t ops_stride, uint32_t *dev_n_ops,
+                                           void *stream);
+int gasalx_nv_banded_qual_traceback_host(gasalx_engine *eng, const gasalx_nv_aligner *aligner,
+                                         const gasalx_nv_quals *quals, uint32_t band, uint32_t n_pairs,
+                                         const gasalx_nv_strings *patterns, uint64_t pattern_words,
+                                         const gasalx_nv_strings *texts, uint64_t text_words, int32_t *scores,
+                                         uint32_t *sources, uint32_t *sinks, uint8_t *ops, uint32_t ops_stride,
+                                         uint32_t *n_ops);
+/* The kernel such a call runs, or the code it would return (the checks above in their order; the
+ * struct's quality bytes are not read and may be NULL).  The scorer (want_traceback 0):
+ * "nvbio_banded16_qual_gotoh_<type>_b<8|16|32>_sink" (two pairs per lane) or
+ * "nvbio_banded_qual_gotoh_<type>_b<8|16|32>_sink" (int32); max_pattern_len 0 takes the int32 kernel.
+ * The traceback: "nvbio_banded_qual_traceback_gotoh_<type>_b<N>", N = 7, 15 or 31 for those band
+ * lengths (exact-length instances), 8, 16 or 32 otherwise. */
+int gasalx_nv_describe_banded_qual_plan(const gasalx_nv_aligner *aligner, const gasalx_nv_quals *quals,
+                                        uint32_t band_len, uint32_t max_pattern_len, uint32_t text_bits,
+                                        int want_traceback, char *buf, uint32_t buf_len);
+
 /* Multi-GPU from one host process.  A group holds one engine per
  * entry of a device list (entries may repeat a device); a host batch is split into
  * contiguous ranges of pairs with equal cell counts (Σ ql·tl; gasalx_shard_bounds),

@@ -48,6 +48,19 @@
  * kernels: all three refuse the scheme at compile time.  ConcatenatedStringSet /
  * make_concatenated_string_set (8-bit symbols) and the free function batch_alignment_score
  * (batched.h:137-150), proteinsw's call, take any aligner the full scorer takes.
+ * Base qualities: a GotohAligner over QualityGotohScheme (two host tables match[l] / mismatch[l] over
+ * quality levels, nvBowtie's SmithWatermanScoringScheme<QualCost, ConstantCost> as its Gotoh aligners
+ * read it, nvBowtie/bowtie2/cuda/scoring.h:286-291; the tables are built on the host by QualCost,
+ * ConstantCost and RoundedQualCost with the reference's arithmetic) is routed by
+ * BatchedBandedAlignmentScore::enact, batch_banded_alignment_score and
+ * BatchedBandedAlignmentTraceback::enact to gasalx_nv_banded_qual_score_* and
+ * gasalx_nv_banded_qual_traceback_* (nvbanded_qual.hpp), with the qualities the stream carries
+ * (AlignmentStream::set_quals: one byte per pattern symbol at the patterns' offsets; a stream without
+ * them is an error at enact).  What nvBowtie calls at score_best_inl.h:179-197, score_all_inl.h:199-217,
+ * score_paired_inl.h:217-235 and traceback_inl.h:239-257, :495-513.  The full-DP BatchedAlignmentScore,
+ * batch_alignment_score and BatchedAlignmentTraceback have no quality kernels and refuse the scheme at
+ * compile time (nvBowtie's score_opposite_inl.h:266 and traceback_inl.h:292 call sites are not covered),
+ * as does SmithWatermanAligner, which nothing in the tree drives with qualities.
  *
  * Header-only C++ over the flat C-ABI (gasalx.h); link with -lgasal.
  */
@@ -174,6 +187,74 @@ template <typename A>
 struct uses_matrix_scheme<A, std::void_t<decltype(std::declval<const A &>().scheme)> >
     : is_matrix_scheme<typename std::decay<decltype(std::declval<const A &>().scheme)>::type> {};
 
+// The three cost functions nvBowtie builds its schemes from, evaluated on the host (float arithmetic
+// included, so no rounding question reaches the device): cost(q) at quality q.
+struct QualCost {        // scoring.h:86-105: min + int(min(q, 40) / 40.0f * (max - min))
+    QualCost(int32 min_val, int32 max_val) : m_min_val(min_val), m_max_val(max_val) {}
+    int32 operator()(const int q) const {
+        const float frac = (float)((q < 40 ? q : 40) / 40.0f);
+        return m_min_val + int32(frac * (m_max_val - m_min_val));
+    }
+    int32 m_min_val, m_max_val;
+};
+struct ConstantCost {    // scoring.h:111-125
+    explicit ConstantCost(int32 v) : m_val(v) {}
+    int32 operator()(const int) const { return m_val; }
+    int32 m_val;
+};
+struct RoundedQualCost { // scoring.h:68-80: phred_to_maq(q), quality_coeffs.h:44-54
+    int32 operator()(const int q) const { return q < 5 ? 0 : q < 15 ? 10 : q < 25 ? 20 : 30; }
+};
+
+// A Gotoh scheme whose substitution score depends on the base quality of the pattern symbol, as
+// nvBowtie's SmithWatermanScoringScheme answers its Gotoh aligners (scoring.h:286-291): two host
+// tables over `levels` quality levels (1..256; a quality >= levels reads the last entry), signed
+// scores, and the pattern gap scores.  Built from a match cost and a mismatch penalty function:
+// match[l] = match_cost(l), mismatch[l] = -mismatch_penalty(l).
+struct QualityGotohScheme {
+    static const uint32 MAX_LEVELS = 256;
+    QualityGotohScheme() {}
+    template <typename MatchCost, typename MismatchCost>
+    QualityGotohScheme(const MatchCost &match_cost, const MismatchCost &mismatch_penalty, int32 gap_open, int32 gap_ext,
+                       uint32 levels = MAX_LEVELS)
+        : m_levels(levels < 1 ? 1 : levels > MAX_LEVELS ? MAX_LEVELS : levels), m_gap_open(gap_open), m_gap_ext(gap_ext) {
+        for (uint32 l = 0; l < m_levels; ++l) {
+            m_match[l] = (int16)match_cost((int)l);
+            m_mismatch[l] = (int16)-mismatch_penalty((int)l);
+        }
+    }
+    // nvBowtie's default scheme (scoring_inl.h:108-122): match 0, mismatch penalty QualCost(2, 6)
+    // (bowtie2's --mp 6,2), read gaps 5 + 3 to open and 3 to extend, i.e. -(const + coeff) and -coeff
+    static QualityGotohScheme nvbowtie_default() {
+        return QualityGotohScheme(ConstantCost(0), QualCost(2, 6), -(5 + 3), -3);
+    }
+    uint32 level(uint8 q) const { return q < m_levels ? q : m_levels - 1; }
+    int32 match(uint8 q = 0) const { return m_match[level(q)]; }
+    int32 mismatch(uint8 q = 0) const { return m_mismatch[level(q)]; }
+    int32 substitution(uint32 /*r_i*/, uint32 /*q_j*/, uint8 r, uint8 q, uint8 qq = 0) const {
+        return r == q ? match(qq) : mismatch(qq);
+    }
+    int32 pattern_gap_open() const { return m_gap_open; }
+    int32 pattern_gap_extension() const { return m_gap_ext; }
+    int32 text_gap_open() const { return m_gap_open; }
+    int32 text_gap_extension() const { return m_gap_ext; }
+    // the tables with a batch's qualities (a device array for the device entry points); the struct
+    // points into this scheme, which must live until the call returns
+    gasalx_nv_quals c_quals(const uint8 *quals = NULL) const {
+        gasalx_nv_quals q = {quals, m_match, m_mismatch, m_levels};
+        return q;
+    }
+    int16 m_match[MAX_LEVELS] = {}, m_mismatch[MAX_LEVELS] = {};
+    uint32 m_levels = 1;
+    int32 m_gap_open = 0, m_gap_ext = 0;
+};
+template <typename T> struct is_quality_scheme : std::false_type {};
+template <> struct is_quality_scheme<QualityGotohScheme> : std::true_type {};
+template <typename A, typename = void> struct uses_quality_scheme : std::false_type {};
+template <typename A>
+struct uses_quality_scheme<A, std::void_t<decltype(std::declval<const A &>().scheme)> >
+    : is_quality_scheme<typename std::decay<decltype(std::declval<const A &>().scheme)>::type> {};
+
 template <AlignmentType T_TYPE, typename AlgorithmType = PatternBlockingTag>
 struct EditDistanceAligner {
     static const AlignmentType TYPE = T_TYPE;
@@ -189,6 +270,9 @@ struct SmithWatermanAligner {
     static_assert(!is_matrix_scheme<scoring_scheme_type>::value,
                   "SubstitutionMatrixScheme is a Gotoh scheme: nvbio's Smith-Waterman (sw/sw_inl.h) reads match() and "
                   "mismatch() only and never calls substitution(); use make_gotoh_aligner");
+    static_assert(!is_quality_scheme<scoring_scheme_type>::value,
+                  "QualityGotohScheme is a Gotoh scheme: nothing in the tree drives Smith-Waterman with qualities, "
+                  "and only the banded Gotoh kernels are built for it; use make_gotoh_aligner");
     static const AlignmentType TYPE = T_TYPE;
     typedef AlgorithmType algorithm_tag;
     SmithWatermanAligner() {}
@@ -208,8 +292,8 @@ struct GotohAligner {
     GotohAligner() {}
     explicit GotohAligner(const scoring_scheme_type s) : scheme(s) {}
     gasalx_nv_aligner c_aligner() const {
-        if constexpr (is_matrix_scheme<scoring_scheme_type>::value) {
-            // match / mismatch are not read by the matrix entry points
+        if constexpr (is_matrix_scheme<scoring_scheme_type>::value || is_quality_scheme<scoring_scheme_type>::value) {
+            // match / mismatch are not read by the matrix and the quality entry points
             gasalx_nv_aligner a = {GASALX_NV_GOTOH, (int32)TYPE, 0, 0, scheme.pattern_gap_open(),
                                    scheme.pattern_gap_extension(), 0, 0};
             return a;
@@ -274,6 +358,10 @@ struct AlignmentStream {
                       "make_*_aligner<TYPE, TextBlockingTag>(...) or score without sinks");
         m_sinks = sinks;
     }
+    // The base qualities of the patterns, for an aligner over QualityGotohScheme: a device array of
+    // one byte per pattern symbol at the patterns' own offsets (quals[offsets[k] + i] is symbol i of
+    // pattern k), what nvbio's banded_alignment_score(aligner, pattern, quals, text, ...) takes.
+    void set_quals(const uint8 *quals) { m_quals = quals; }
 
     aligner_type m_aligner;
     uint32 m_count, m_max_pattern_len, m_total_pattern_len, m_text_len;
@@ -281,6 +369,7 @@ struct AlignmentStream {
     int16 *m_scores;
     int32 *m_scores32 = nullptr;            // optional int32 scores
     uint32 *m_sinks = nullptr;              // optional BestSink positions, 2 x count: set_sinks()
+    const uint8 *m_quals = nullptr;         // base qualities, one per pattern symbol: set_quals()
     const uint32 *m_text_offsets = nullptr; // per-pattern texts instead of the shared one
     uint32 m_pattern_bits = 4, m_pattern_big_endian = 1;   // io::SequenceDataTraits<DNA_N>
     uint32 m_text_bits = 2, m_text_big_endian = 0;         // REF_BITS / REF_BIG_ENDIAN
@@ -317,6 +406,9 @@ struct BatchedAlignmentScore {
         static_assert(!is_myers_tag<typename aligner_type::algorithm_tag>::value,
                       "MyersTag aligners run under BatchedBandedAlignmentScore only: nvbio has the banded Myers "
                       "scorer (myers/myers_banded_inl.h) and no full-DP or traceback form of it");
+        static_assert(!uses_quality_scheme<aligner_type>::value,
+                      "QualityGotohScheme runs under BatchedBandedAlignmentScore / batch_banded_alignment_score and "
+                      "BatchedBandedAlignmentTraceback only: the full-DP scorer and traceback have no quality kernels");
         (void)temp_size; (void)temp;
         const gasalx_nv_aligner a = stream.aligner().c_aligner();
         gasalx_nv_strings p = {stream.m_patterns, stream.m_offsets, 0, stream.m_pattern_bits,
@@ -396,7 +488,17 @@ struct BatchedBandedAlignmentScore {
             return;
         }
         int rc;
-        if (stream.m_sinks) {
+        if constexpr (uses_quality_scheme<aligner_type>::value) {
+            // GotohAligner over QualityGotohScheme: scores and / or sinks, the stream's qualities
+            if (stream.m_quals == NULL) {
+                fprintf(stderr, "BatchedBandedAlignmentScore::enact: a QualityGotohScheme aligner needs the patterns' "
+                                "qualities, call set_quals() on the stream\n");
+                exit(EXIT_FAILURE);
+            }
+            const gasalx_nv_quals q = stream.aligner().scheme.c_quals(stream.m_quals);
+            rc = gasalx_nv_banded_qual_score_device(engine(), &a, &q, BAND_LEN, stream.size(), &p, &t, stream.m_scores32,
+                                                    stream.m_sinks, stream.max_pattern_length(), hip_stream);
+        } else if (stream.m_sinks) {
             // ED, SW and Gotoh with the BestSink positions (scores optional)
             rc = gasalx_nv_banded_score_sinks_device(engine(), &a, BAND_LEN, stream.size(), &p, &t, stream.m_scores32,
                                                      stream.m_sinks, stream.max_pattern_length(), hip_stream);
@@ -438,11 +540,14 @@ struct BestSinks {
 // max_text_length) (batched.h:216-231), the form qmap and fmmap call: patterns[k] against texts[k]
 // on the engine's stream (asynchronous, as nvbio's).  Every aligner takes scores and sinks: a
 // MyersTag aligner through gasalx_nv_banded_myers_*, the ED, SW and Gotoh aligners through
-// gasalx_nv_banded_score_sinks_* (gasalx_nv_banded_score_* when no sinks array is given).
+// gasalx_nv_banded_score_sinks_* (gasalx_nv_banded_score_* when no sinks array is given), a Gotoh
+// aligner over QualityGotohScheme through gasalx_nv_banded_qual_score_* with `quals` (a device array,
+// one byte per pattern symbol at the patterns' offsets; needed by that scheme alone).
 template <uint32 BAND_LEN, typename aligner_type, typename scheduler_type>
 void batch_banded_alignment_score(const aligner_type aligner, const PackedStringSet patterns,
                                   const PackedStringSet texts, BestSinks sinks, const scheduler_type,
-                                  const uint32 max_pattern_length, const uint32 max_text_length) {
+                                  const uint32 max_pattern_length, const uint32 max_text_length,
+                                  const uint8 *quals = NULL) {
     (void)max_text_length;
     AlignmentStream<aligner_type> stream(aligner, patterns.size(), patterns.m_offsets, patterns.m_words,
                                          max_pattern_length, 0, texts.m_words, 0, NULL);
@@ -451,6 +556,7 @@ void batch_banded_alignment_score(const aligner_type aligner, const PackedString
     stream.m_text_bits = texts.m_bits; stream.m_text_big_endian = texts.m_big_endian;
     stream.m_scores32 = sinks.scores;
     stream.m_sinks = sinks.sinks;
+    stream.m_quals = quals;
     BatchedBandedAlignmentScore<BAND_LEN, AlignmentStream<aligner_type>, scheduler_type> batch;
     batch.enact(stream);
 }
@@ -538,6 +644,9 @@ struct BatchedAlignmentTraceback {
         static_assert(!is_myers_tag<typename aligner_type::algorithm_tag>::value,
                       "MyersTag aligners run under BatchedBandedAlignmentScore only: nvbio has the banded Myers "
                       "scorer (myers/myers_banded_inl.h) and no full-DP or traceback form of it");
+        static_assert(!uses_quality_scheme<aligner_type>::value,
+                      "QualityGotohScheme runs under BatchedBandedAlignmentScore / batch_banded_alignment_score and "
+                      "BatchedBandedAlignmentTraceback only: the full-DP scorer and traceback have no quality kernels");
         (void)temp_size; (void)temp;
         const gasalx_nv_aligner a = stream.aligner().c_aligner();
         gasalx_nv_strings p = {stream.m_patterns, stream.m_offsets, 0, stream.m_pattern_bits,
@@ -594,10 +703,24 @@ struct BatchedBandedAlignmentTraceback {
                                stream.m_pattern_big_endian};
         gasalx_nv_strings t = {stream.m_text, stream.m_text_offsets, stream.m_text_len, stream.m_text_bits,
                                stream.m_text_big_endian};
-        const int rc = gasalx_nv_banded_traceback_device(engine(), &a, BAND_LEN, stream.size(), &p, &t,
-                                                         stream.max_pattern_length(), stream.m_scores32,
-                                                         stream.m_sources, stream.m_sinks, stream.m_ops,
-                                                         stream.m_ops_stride, stream.m_n_ops, hip_stream);
+        int rc;
+        if constexpr (uses_quality_scheme<aligner_type>::value) {
+            if (stream.m_quals == NULL) {
+                fprintf(stderr, "BatchedBandedAlignmentTraceback::enact: a QualityGotohScheme aligner needs the "
+                                "patterns' qualities, call set_quals() on the stream\n");
+                exit(EXIT_FAILURE);
+            }
+            const gasalx_nv_quals q = stream.aligner().scheme.c_quals(stream.m_quals);
+            rc = gasalx_nv_banded_qual_traceback_device(engine(), &a, &q, BAND_LEN, stream.size(), &p, &t,
+                                                        stream.max_pattern_length(), stream.m_scores32,
+                                                        stream.m_sources, stream.m_sinks, stream.m_ops,
+                                                        stream.m_ops_stride, stream.m_n_ops, hip_stream);
+        } else {
+            rc = gasalx_nv_banded_traceback_device(engine(), &a, BAND_LEN, stream.size(), &p, &t,
+                                                   stream.max_pattern_length(), stream.m_scores32, stream.m_sources,
+                                                   stream.m_sinks, stream.m_ops, stream.m_ops_stride, stream.m_n_ops,
+                                                   hip_stream);
+        }
         if (rc != GASALX_OK) {
             fprintf(stderr, "BatchedBandedAlignmentTraceback::enact: %s\n", gasalx_last_error());
             exit(EXIT_FAILURE);
