@@ -13,14 +13,18 @@
 //     strictly greater extension; LOCAL: H == 0 -> SINK, :441-442) and sw/sw_inl.h:420-540, 380-400;
 //   * boundaries: gotoh_inl.h:695 and the checkpoint context's init (:247-300), sw_inl.h:660-663,
 //     243-251;
-//   * the sink: BestSink keeps the last maximum in report order (stripes of 8 pattern columns,
-//     then rows, then columns) for LOCAL; SEMI_GLOBAL reports H(i, M-1) per row, GLOBAL H(N-1, M-1)
-//     (utils_inl.h:273-300);
+//   * the sink: BestSink keeps the last maximum in report order (stripes of pattern columns, then
+//     rows, then columns; the stripes 8 wide for Gotoh, gotoh_inl.h:1492-1495, and 16 wide for
+//     Smith-Waterman and edit distance, sw_inl.h:1330-1334) for LOCAL; SEMI_GLOBAL reports H(i, M-1)
+//     per row, GLOBAL H(N-1, M-1) (utils_inl.h:273-300);
 //   * the walk: gotoh_inl.h:1806-1872 (H / E / F states), sw_inl.h:1653-1709, then the first row /
 //     column of alignment_inl.h:442-459.
 // Flags are one byte per cell, 8 cells of a row and stripe per store, interleaved across the
 // launch's threads ([row][stripe][pair]: a wave's stores are contiguous).  The CPU restatement is
 // oracle/nvbio_oracle.c orc_nv_traceback_one, pinned by nvbio-test's alignment_test.cu:778-792.
+// The Smith-Waterman / edit-distance half of both kernels here has a second reference written from
+// the same reference lines, tests/nvbio_sw_traceback_model.py (the Gotoh halves:
+// tests/nvbio_matrix_traceback_model.py and tests/nvbio_qual_model.py).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -161,8 +165,14 @@ __global__ __launch_bounds__(256) void nv_traceback_kernel(NvTbArgs A) {
                 diagH = up;
                 Hb[j] = h;
                 if (j <= 4) flo |= d << (8 * (j - 1)); else fhi |= d << (8 * (j - 5));
-                if (TYPE == 1 && c0 + j <= M && best <= h) {   // report order: stripe, row, column; the last maximum wins
-                    best = h; bx = i + 1; by = c0 + j;
+                if (TYPE == 1 && c0 + j <= M) {   // report order: stripe, row, column; the last maximum wins
+                    bool take = best <= h;
+                    // The SW reference reports per stripe of 16 columns (sw_bandlen_selector, sw_inl.h:1330-1334;
+                    // Gotoh's is 8), and only this order sees the width.  The pass keeps its stripes of 8: in the
+                    // second half of a 16-column stripe an equal best from the first half stands unless this
+                    // cell's row is at or below it.
+                    if (!GOTOH && (c0 & BAND) && best == h && by <= c0 && by + BAND > c0 && bx > i + 1) take = false;
+                    if (take) { best = h; bx = i + 1; by = c0 + j; }
                 }
                 if (c0 + j == M) last_h = h;
             }

@@ -343,7 +343,9 @@ int32_t orc_nv_traceback_one(int aligner, int type, const int32_t prm[6], const 
             Hp[j + 1] = h;
             left = h;
             if (type == ORC_NV_LOCAL) {   /* report order: stripe, row, column; the last maximum wins */
-                const uint32_t blk = j / NV_BAND;
+                /* the stripe is the aligner's BAND_LEN: gotoh_bandlen_selector 8 / DIM (gotoh_inl.h:1492-1495),
+                 * sw_bandlen_selector 16 / DIM (sw_inl.h:1330-1334), DIM = 1 (sw_inl.h:1546, :1595) */
+                const uint32_t blk = j / (gotoh ? NV_BAND : 2 * NV_BAND);
                 if (h > best || (h == best && (blk > bblk || (blk == bblk && (i + 1 > bx || (i + 1 == bx && j + 1 >= by)))))) {
                     best = h; bx = i + 1; by = j + 1; bblk = blk;
                 }
