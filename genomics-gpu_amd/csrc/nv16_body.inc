@@ -5,13 +5,15 @@
 // boundaries is made here too.  The including scope defines the template parameters, A (the
 // arguments), SINK (constexpr bool, true) and sinks (uint32_t *, 2 per pair, or NULL).
 // Both halves of a lane sit on the same row and column, so one report-order key serves both:
-// key(i, c) = (c >> 3) << 13 | i << 3 | (c & 7) (rows < 1024; no pattern length in it).  LOCAL
+// key(i, c) = (c >> SB) << (SB + 10) | i << SB | (c & (2^SB - 1)), SB = 3 for Gotoh and 4 for SW and ED
+// (the report stripe, nvbio_sink.hpp; rows < 1024: 10 bits; no pattern length in it).  LOCAL
 // keeps H << 32 | key per half in place of the packed running maximum; SEMI_GLOBAL a column per
 // half on the lane that owns the half's last row.
     extern __shared__ __attribute__((aligned(16))) uint32_t nvt[];
     constexpr int P = 64 / G;
     constexpr bool GOTOH = ALN == NV_GOTOH;
     constexpr bool FR = GOTOH && TYPE != NV_LOCAL;   // the drift frame (header)
+    constexpr uint32_t SB = GOTOH ? 3 : 4;           // SINK: log2 of the report stripe
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t lg = lane & (G - 1), grp = lane / G;
     const uint32_t pa = 2 * ((blockIdx.x * 4 + wave) * P + grp), pb = pa + 1;
@@ -130,7 +132,7 @@
             const uint32_t T = Ta[c], T1 = SHARED ? VCONST : Tb[c];
             uint32_t lbest = best;
             const bool cina = SHARED || (uint32_t)c < Na, cinb = SHARED || (uint32_t)c < Nb;
-            const uint32_t kb = (((uint32_t)c >> 3) << 13) | ((lg * R) << 3) | ((uint32_t)c & 7u);
+            const uint32_t kb = (((uint32_t)c >> SB) << (SB + 10)) | ((lg * R) << SB) | ((uint32_t)c & ((1u << SB) - 1u));
 #pragma unroll
             for (int k = 0; k < R; ++k) {
                 const uint32_t v = __builtin_amdgcn_perm(T1, T, sel[k]);
@@ -154,7 +156,7 @@
                     if (TYPE == NV_LOCAL) H = pk_max3(H, BB, BB);
                 }
                 if (TYPE == NV_LOCAL && SINK) {
-                    const uint32_t key = kb + 8u * (uint32_t)k;
+                    const uint32_t key = kb + ((uint32_t)k << SB);
                     const long long ca = ((long long)(H & 0xFFFFu) << 32) | (long long)key;
                     const long long cb = ((long long)(H >> 16) << 32) | (long long)key;
                     bca = (cina && (uint32_t)k < nra && ca > bca) ? ca : bca;
@@ -229,8 +231,8 @@
             if (TYPE == NV_LOCAL && bc >= 0) {
                 v = (int32_t)(bc >> 32) - B;
                 const uint32_t key = (uint32_t)bc;
-                x = (key >> 13) * 8 + (key & 7u) + 1;
-                y = ((key >> 3) & 1023u) + 1;
+                x = ((key >> (SB + 10)) << SB) + (key & ((1u << SB) - 1u)) + 1;
+                y = ((key >> SB) & 1023u) + 1;
             }
         }
         if (FR) v -= dl + g * (int32_t)(M + N - 2);   // the frame at (M-1, N-1); SEMI keys: + g*(N-1-c)

@@ -7,6 +7,7 @@
     extern __shared__ __attribute__((aligned(16))) uint16_t nvlds[];
     constexpr int P = 64 / G;
     constexpr bool GOTOH = ALN == NV_GOTOH;
+    constexpr uint32_t SB = GOTOH ? 3 : 4;        // SINK: log2 of the report stripe (nvbio_sink.hpp)
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t lg = lane & (G - 1), slot = lane / G;
     const uint32_t pair = (blockIdx.x * 4 + wave) * P + slot;
@@ -80,8 +81,8 @@
         if (c >= 0 && (uint32_t)c < stride) {
             const uint32_t tc = mine[c];
             const bool cin = (uint32_t)c < N;
-            // SINK: report-order key of (r0, c); row r0 + k adds 8k
-            const uint32_t kb = ((((uint32_t)c >> 3) * M + r0) << 3) | ((uint32_t)c & 7u);
+            // SINK: report-order key of (r0, c); row r0 + k adds k << SB
+            const uint32_t kb = ((((uint32_t)c >> SB) * M + r0) << SB) | ((uint32_t)c & ((1u << SB) - 1u));
 #pragma unroll
             for (int k = 0; k < R; ++k) {
                 const int32_t S = (pc[k] == tc) ? A.match : A.mismatch;
@@ -98,7 +99,7 @@
                 if (TYPE == NV_LOCAL) {
                     H = max(H, 0);
                     if constexpr (SINK) {
-                        const long long cand = ((long long)H << 32) | (long long)(kb + 8u * (uint32_t)k);
+                        const long long cand = ((long long)H << 32) | (long long)(kb + ((uint32_t)k << SB));
                         bc = (cin && (uint32_t)k < nrow && cand > bc) ? cand : bc;
                     } else if (MASK) best = (cin && r0 + k < M) ? max(best, H) : best;
                     else best = max(best, H);
@@ -143,8 +144,8 @@
             if (TYPE == NV_SEMI) x = bcol + 1;
             if (TYPE == NV_LOCAL && bc >= 0) {
                 v = (int32_t)(bc >> 32);
-                const uint32_t key = (uint32_t)bc, q = key >> 3, sb = q / M;   // bc >= 0: a real row, M >= 1
-                x = sb * 8 + (key & 7u) + 1;
+                const uint32_t key = (uint32_t)bc, q = key >> SB, sb = q / M;   // bc >= 0: a real row, M >= 1
+                x = (sb << SB) + (key & ((1u << SB) - 1u)) + 1;
                 y = q - sb * M + 1;
             }
         }

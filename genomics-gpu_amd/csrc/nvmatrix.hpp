@@ -2,7 +2,8 @@
 // GotohAligner runs when its scheme answers substitution(i, j, r, q, qq) from a table
 // (NvB/nvbio/alignment/gotoh/gotoh_inl.h:534, :1042; the proteinsw example's BlosumScheme,
 // m_matrix[r + q*24] with r the text symbol and q the pattern symbol).  Score only, or score and
-// BestSink position in the TextBlockingTag report order with nvbio_sink.hpp's key.
+// BestSink position in the TextBlockingTag report order with nvbio_sink.hpp's key at Gotoh's
+// stripe width (8 columns, SB = 3).
 //
 // nv_kernel's layout and recurrences (nvbio.hpp: G lanes per pair, R pattern rows per lane, the
 // text on the step axis, int32, DPP hand-off); what differs is where S comes from:
@@ -120,7 +121,7 @@ __global__ __launch_bounds__(256) void nv_matrix_kernel(NvMatrixArgs A) {
         if (c >= 0 && (uint32_t)c < stride) {
             const int8_t *const col = tab + mine[c];   // the image's column of this text symbol
             const bool cin = (uint32_t)c < N;
-            // SINK: report-order key of (r0, c); row r0 + k adds 8k (nvbio_sink.hpp)
+            // SINK: report-order key of (r0, c); row r0 + k adds 8k (nvbio_sink.hpp, Gotoh: SB = 3)
             const uint32_t kb = ((((uint32_t)c >> 3) * M + r0) << 3) | ((uint32_t)c & 7u);
 #pragma unroll
             for (int k = 0; k < R; ++k) {

@@ -355,7 +355,8 @@ int gasalx_nv_score_host(gasalx_engine *eng, const gasalx_nv_aligner *aligner, u
  * in a BestSink (sink_inl.h:59-68) under a TextBlockingTag aligner: the score and the cell where
  * it was reached, sinks[2k] = x (text column) and sinks[2k + 1] = y (pattern row), one-based:
  * the coordinates and layout of gasalx_nv_traceback_*'s sinks.  BestSink keeps the last maximum
- * in report order: LOCAL reports every cell, text stripes of 8 columns left to right, inside a
+ * in report order: LOCAL reports every cell, text stripes of 8 columns (Gotoh) or 16 (Smith-Waterman,
+ * edit distance: nvbio's BAND_LEN of the aligner) left to right, inside a
  * stripe the pattern rows top to bottom, inside a row the columns left to right; SEMI_GLOBAL the
  * last pattern row left to right (the rightmost maximum); GLOBAL the cell (N, M).  A pair that
  * reports no cell (an empty text; LOCAL: an empty pattern) gets INT32_MIN and (0xFFFFFFFF,

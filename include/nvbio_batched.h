@@ -349,7 +349,7 @@ struct AlignmentStream {
     // alignment_score(aligner, pattern, text, min_score, sink) leaves in the sink): a device
     // array of 2 x count entries, sinks[2k] = x (text), sinks[2k + 1] = y (pattern), one-based.
     // On ties BestSink keeps the last maximum in the aligner's report order, and the kernels
-    // follow the TextBlockingTag order (text stripes of 8 columns).
+    // follow the TextBlockingTag order (text stripes of the aligner's BAND_LEN columns: 8 for Gotoh, 16 for Smith-Waterman and edit distance).
     void set_sinks(uint32 *sinks) {
         static_assert(std::is_same<typename aligner_type::algorithm_tag, TextBlockingTag>::value ||
                           is_myers_tag<typename aligner_type::algorithm_tag>::value,

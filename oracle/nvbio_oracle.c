@@ -2,7 +2,7 @@
  * nvbio_oracle.c — CPU restatement of nvbio's batched alignment scoring
  * (TEST INFRASTRUCTURE ONLY; see gasal_oracle.h for who may load liborc).
  *
- * Follows the TextBlockingTag score functions literally: 8-column text stripes,
+ * Follows the TextBlockingTag score functions literally: text stripes of NV_BAND columns,
  * pattern rows top to bottom inside a stripe, the stripe's right column carried
  * to the next one as (H, E) (paths under Non-CDP/NvB/nvbio/alignment):
  *   gotoh/gotoh_inl.h:985-1110   update_row (F from above, E from the left, max3, LOCAL clamp,
@@ -42,6 +42,12 @@
 
 #include "gasal_oracle.h"
 
+/* The stripe width of the score functions.  nvbio's is the aligner's BAND_LEN: 8 for Gotoh
+ * (gotoh_inl.h:1492-1495), 16 for Smith-Waterman and edit distance (sw_inl.h:1330-1334, :1397;
+ * ed_inl.h:95).  The width only orders BestSink's reports, and orc_nv_score_one returns the score
+ * alone, which is the maximum of the reported cells under every order: 8 serves all three here.
+ * Where the order decides an output (the LOCAL sink of orc_nv_traceback_batch) the width is taken
+ * per aligner. */
 #define NV_BAND 8
 
 static inline int32_t nmax(int32_t a, int32_t b) { return a > b ? a : b; }

@@ -66,7 +66,7 @@ def pair(al, mat, n, p, t):
     k = (al.type, al.gap_open, al.gap_ext, n, tuple(m), bytes(np.asarray(p, np.uint8)), bytes(np.asarray(t, np.uint8)))
     if k not in _cache:
         top, H = dp_matrix(al, m, n, [int(v) for v in p], [int(v) for v in t])
-        _cache[k] = R.best_sink(al.type, top, H, len(t))
+        _cache[k] = R.best_sink(al.type, top, H, len(t), R.stripe(al))   # a GotohAligner: stripes of 8
     return _cache[k]
 
 

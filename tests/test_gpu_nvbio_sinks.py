@@ -2,8 +2,10 @@
 the C ABI: scores and BestSink positions bit-exact against the plain-Python model of nvbio's
 TextBlockingTag report order (tests/nvbio_sink_model.py, pinned by test_nvbio_sinks_ref.py).
 Pattern lengths sit at the lane-group edges of the planned kernel (G lanes x R rows, read from
-the plan name), text lengths at the 8-column stripe edges, and most inputs are built to tie:
-the rule (the last maximum in report order) is only visible on ties."""
+the plan name), text lengths at the stripe edges (8 columns for Gotoh, 16 for Smith-Waterman and
+edit distance), and most inputs are built to tie: the rule (the last maximum in report order) is
+only visible on ties.  The crossed-tie batches are the ones whose sink depends on the order itself
+(test_nvbio_sinks_ref.py::test_inputs_tell_orders_apart counts on how many pairs)."""
 import re
 
 import numpy as np
@@ -111,6 +113,17 @@ def test_pattern_limit_1024(engine, base, type_):
     _compare(engine, al, pats, texts, P, G.PackedSet.pack(texts, 2, False))
     assert _shape(_sink_plan(al, 1024, 130, True, 4, packed=False)) == (64, 16)
     _compare(engine, al, pats, texts, P, G.PackedSet.pack(texts, 4, True))
+    # a crossed pair at 2L = 1024: the maxima at (520, 1024) and (1040, 512), so the greatest row
+    # (all ten row bits of the packed key, the largest M in the int32 key) against the later
+    # stripe, whose index lies above the row bits
+    pats, texts = [_CROSSED_1024[0]], [_CROSSED_1024[1]]
+    P, T2, T4 = _pack_both(pats, texts)
+    assert _shape(_sink_plan(al, 1024, 1041, True, 2, packed=True)) == (64, 16)
+    _compare(engine, al, pats, texts, P, T2)
+    assert _shape(_sink_plan(al, 1024, 1041, True, 4, packed=False)) == (64, 16)
+    _compare(engine, al, pats, texts, P, T4)
+    if type_ == "local" and base != "ed":
+        assert R.pair(al, pats[0], texts[0]) == (2 * 512, 1040, 512, 2)
 
 
 @pytest.mark.parametrize("base,type_", CASES, ids=IDS)
@@ -127,6 +140,51 @@ def test_shared_text(engine, base, type_):
     _compare(engine, al, pats, texts, P, T4)
 
 
+_CROSSED_1024 = R.crossed_pair(512, 520, 1040, 1041, np.random.default_rng(0xC9))
+
+
+def _pack_both(pats, texts, shared=False):
+    """(P, T2, T4): reads 4-bit big-endian; texts 2-bit little-endian (inside the packed kernel's
+    window) and 4-bit big-endian (outside: the int32 kernel)."""
+    return (G.PackedSet.pack(pats, 4, True), G.PackedSet.pack(texts, 2, False, shared=shared),
+            G.PackedSet.pack(texts, 4, True, shared=shared))
+
+
+@pytest.mark.parametrize("base,type_", CASES, ids=IDS)
+def test_crossed_ties(engine, base, type_):
+    # two equal maxima, one left and low, one right and high: which of them is the sink depends on
+    # the stripe width, on the rows' place in the order and on first-or-last.  L = 3, R and R + 1
+    # of the planned shape: the tied rows L - 1 and 2L - 1 on one lane, on two lanes, and across a
+    # lane edge, where the lanes' (H << 32 | key) meet in the reduction.  Neighbouring pairs have
+    # different winners (the two halves of a packed lane keep different keys) and the batch is odd
+    al = R.aligner(base, type_)
+    Ls = R.crossed_lens(al)
+    r = Ls[1]
+    pats, texts = R.crossed_batch(base, Ls)
+    mp, mt = _max_lens(pats, texts)
+    assert len(pats) % 2 == 1 and mp == 2 * (r + 1) and mt <= R.CROSS_MAX_TEXT
+    P, T2, T4 = _pack_both(pats, texts)
+    assert _shape(_sink_plan(al, mp, mt, True, 2, packed=True))[1] == r
+    n_max = _compare(engine, al, pats, texts, P, T2)
+    assert _shape(_sink_plan(al, mp, mt, True, 4, packed=False))[1] == r
+    _compare(engine, al, pats, texts, P, T4)
+    if type_ == "local" and base != "ed":
+        assert (n_max > 1).mean() >= 0.8
+    if type_ == "local" and base == "ed":     # every cell is 0: the last report, whatever the width
+        sc, sk = engine.nv_score_sinks_host(al, P, T2)
+        assert not sc.any() and [list(v) for v in sk] == [[len(t), len(p)] for p, t in zip(pats, texts)]
+    # one shared text holding nested V and U copies, the patterns cut from it
+    Ls = R.crossed_lens(al, per_pair=False)
+    for L in Ls:
+        for lead in R.CROSS_LEADS:
+            pats, texts = R.crossed_shared(L, lead)
+            P, T2, T4 = _pack_both(pats, texts, shared=True)
+            assert _shape(_sink_plan(al, 2 * L, len(texts[0]), False, 2, packed=True))[1] == Ls[1]
+            _compare(engine, al, pats, texts, P, T2)
+            assert _shape(_sink_plan(al, 2 * L, len(texts[0]), False, 4, packed=False))[1] == Ls[1]
+            _compare(engine, al, pats, texts, P, T4)
+
+
 @pytest.mark.parametrize("al", [G.NvAligner(G.NV_SW, G.NV_LOCAL, 1, 2, 0, 0, 1, -1),
                                 G.NvAligner(G.NV_GOTOH, G.NV_LOCAL, 1, -1, 1, 1),
                                 G.NvAligner(G.NV_GOTOH, G.NV_SEMI_GLOBAL, 5, -4, -10, -1),
@@ -139,6 +197,12 @@ def test_other_schemes(engine, al):
     pats, texts, P, T = R.packed("edge", (1, 8, 9, 20), 0xE4)
     _sink_plan(al, *_max_lens(pats, texts), True, 2, packed=al.match == 5)
     _compare(engine, al, pats, texts, P, T)
+    # the crossed batch: under the positive scores pad cells would outscore real ones, and the
+    # real maxima tie in other cells than the builder's -- the model says which
+    pats, texts = R.crossed_batch("sw" if al.aligner == G.NV_SW else "gotoh", R.crossed_lens(al))
+    P, T2, _ = _pack_both(pats, texts)
+    _sink_plan(al, *_max_lens(pats, texts), True, 2, packed=al.match == 5)
+    _compare(engine, al, pats, texts, P, T2)
 
 
 def test_null_outputs(engine):

@@ -47,12 +47,13 @@ def test_scores_equal_the_c_oracle_shared_text():
         assert np.array_equal(R.batch(al, pats, texts)[0], O.nv_score(al, P, T)), (base, type_)
 
 
-def _later_in_report_order(M, N, x, y):
-    """Mask [M, N] of the cells nvbio reports after (x, y) (one-based): a later stripe, or the same
-    stripe and a lower row, or the same row of the stripe and a column further right."""
+def _later_in_report_order(M, N, x, y, w):
+    """Mask [M, N] of the cells nvbio reports after (x, y) (one-based) in stripes of w columns: a
+    later stripe, or the same stripe and a lower row, or the same row of the stripe and a column
+    further right."""
     i, c = np.meshgrid(np.arange(M), np.arange(N), indexing="ij")
     si, sc = y - 1, x - 1
-    return (c // 8 > sc // 8) | ((c // 8 == sc // 8) & ((i > si) | ((i == si) & (c > sc))))
+    return (c // w > sc // w) | ((c // w == sc // w) & ((i > si) | ((i == si) & (c > sc))))
 
 
 @pytest.mark.parametrize("base,type_", CASES, ids=[f"{b}-{t}" for b, t in CASES])
@@ -78,7 +79,7 @@ def test_sink_properties(base, type_):
         if al.type == G.NV_SEMI_GLOBAL:
             assert y == M and score == Hn[M - 1].max() and not (Hn[M - 1, x:] >= score).any()
         else:
-            assert score == Hn.max() and not (Hn[_later_in_report_order(M, N, x, y)] >= score).any()
+            assert score == Hn.max() and not (Hn[_later_in_report_order(M, N, x, y, R.stripe(al))] >= score).any()
             assert n_max == int((Hn == score).sum())
 
 
@@ -89,6 +90,9 @@ def test_sinks_against_the_traceback_oracle(base, type_):
     (i + 1, block + j) per *pattern* stripe, then text position, then pattern column
     (gotoh_inl.h:575, :582; sw_inl.h:517, :524), so a tied LOCAL maximum may end elsewhere than
     under the TextBlockingTag order (gotoh_inl.h:1083, :1090).  LOCAL: untied pairs only.
+    Both orders now take stripes of 16 for Smith-Waterman and edit distance, but one stripes the
+    pattern and the other the text, so a tie may still end in another cell: the set that must
+    agree is unchanged, the untied pairs (n_max counts cells, whatever the width).
     SEMI_GLOBAL (the last text position holding the row's maximum, utils_inl.h:273-300) and
     GLOBAL agree with the text-stripe order on every pair.  The traceback skips empty strings."""
     al = R.aligner(base, type_)
@@ -111,6 +115,101 @@ def test_tie_share_of_the_inputs():
         for type_ in ("local", "semi"):
             n_max = R.batch(R.aligner(base, type_), pats, texts)[2]
             assert (n_max > 1).mean() >= 0.5, (base, type_, float((n_max > 1).mean()))
+
+
+def test_stripe_widths():
+    # gotoh_bandlen_selector 8 / DIM, sw_bandlen_selector 16 / DIM (edit distance takes it too), DIM = 1
+    assert [R.stripe(R.BASES[b]) for b in ("gotoh", "sw", "ed")] == [8, 16, 16]
+
+
+# Three crossed pairs worked out on paper, L = 2: the pattern is U + V = 0 1 + 2 3, the text
+# 3^k 2 3 0 0 1 0 (V at columns k + 1, k + 2; U at k + 4, k + 5; N = k + 6).  Rows 1 and 2 (0, 1)
+# score 0 left of column k + 3, since no text symbol there is theirs; row 3 (2) matches column k + 1
+# alone, H(3, k + 1) = 2, and row 4 (3) continues it, H(4, k + 2) = 4; row 4 holds 2 in the columns
+# <= k (a single match each, a gap from the one before gives 0).  Row 1 (0) matches columns k + 3 and
+# k + 4 with H = 2 each (and k + 6), row 2 (1) continues the second, H(2, k + 5) = 4.  Every other
+# cell lies below 4 under both schemes (Smith-Waterman 2, -3, gaps -2 and -3: at most 2; Gotoh 2, -1,
+# -2, -1: at most 3, at (k + 6, 3) from the diagonal of H(2, k + 5) = 4), so the cells that tie are
+#     H(4, k + 2) = 4  -- x = k + 2, y = 4, left and low --  and  H(2, k + 5) = 4  -- x = k + 5, y = 2.
+# In one stripe row 4 is reported after row 2; in a later stripe column k + 5 is reported after
+# every cell of the stripe of column k + 2.  Zero-based columns k + 1 and k + 4:
+#   k = 1: columns 2 and 5, one stripe of 8 and of 16: (k + 2, 4) for both aligners
+#   k = 5: columns 6 and 9, stripes 0 and 1 of 8, stripe 0 of 16: Gotoh (k + 5, 2), Smith-Waterman (k + 2, 4)
+#   k = 13: columns 14 and 17, stripes 0 and 1 of 16 (1 and 2 of 8): (k + 5, 2) for both
+# Edit distance, LOCAL: every cell is 0 and the last report is (N, M).
+HAND = [  # k, Smith-Waterman (score, x, y), Gotoh, edit distance
+    (1, (4, 3, 4), (4, 3, 4), (0, 7, 4)),
+    (5, (4, 7, 4), (4, 10, 2), (0, 11, 4)),
+    (13, (4, 18, 2), (4, 18, 2), (0, 19, 4)),
+]
+
+
+@pytest.mark.parametrize("k,sw,gotoh,ed", HAND, ids=["one_stripe_of_8", "8_boundary_inside_16", "16_boundary"])
+def test_hand_worked_crossed_pairs(k, sw, gotoh, ed):
+    p, t = [0, 1, 2, 3], [3] * k + [2, 3, 0, 0, 1, 0]
+    assert len(t) <= 20
+    for base, want in (("sw", sw), ("gotoh", gotoh), ("ed", ed)):
+        score, x, y, n_max = R.pair(R.aligner(base, "local"), p, t)
+        assert (score, x, y) == want, (base, k)
+        assert n_max == (2 if base != "ed" else 4 * len(t)), (base, k)
+    if k == 5:
+        assert sw != gotoh           # the pair that tells the two selectors apart
+
+
+def _rivals(al):
+    """The report orders nvbio does not have: (width, first)."""
+    w = R.stripe(al)
+    return [(v, False) for v in (1, 4, 8, 16, 32, R.ROW_MAJOR) if v != w] + [(w, True)]
+
+
+def _differing(al, pats, texts, width, first):
+    if len(texts) == 1:
+        texts = list(texts) * len(pats)
+    return sum(R.rival(al, p, t, width, first)[:3] != R.pair(al, p, t)[:3] for p, t in zip(pats, texts))
+
+
+@pytest.mark.parametrize("base", list(R.BASES))
+def test_inputs_tell_orders_apart(base):
+    """The crossed-tie batches of test_gpu_nvbio_sinks.py::test_crossed_ties, before any kernel
+    runs: a kernel that reported in another order would give another sink on at least 8 pairs.
+    Counts of the per-pair batch at L = 3, 8, 9 (133 pairs, all tied), pairs whose sink differs
+    from nvbio's order:
+      Smith-Waterman (16): width 1: 48, 4: 45, 8: 36, 32: 37, row-major: 73, first maximum: 133
+      Gotoh (8):           width 1: 12, 4: 9, 16: 37, 32: 73, row-major: 109, first maximum: 133
+    SEMI_GLOBAL, first against last on the last row: sw 133, ed 133, gotoh 65."""
+    semi = R.aligner(base, "semi")
+    pats, texts = R.crossed_batch(base, R.crossed_lens(semi))
+    assert max(len(t) for t in texts) <= R.CROSS_MAX_TEXT
+    n = _differing(semi, pats, texts, R.stripe(semi), True)
+    print(base, "semi first-against-last", n, "of", len(pats))
+    assert n >= 8
+    al = R.aligner(base, "local")
+    pats, texts = R.crossed_batch(base, R.crossed_lens(al))
+    assert len(pats) % 2 == 1
+    shared = [R.crossed_shared(L, lead) for L in R.crossed_lens(al, per_pair=False) for lead in R.CROSS_LEADS]
+    if base == "ed":
+        # match 0, clamp at 0, boundaries 0: every LOCAL cell is 0 and the last report is (N, M)
+        # under every width; no order to tell apart
+        for p, t in list(zip(pats, texts)) + [(p, ts[0]) for ps, ts in shared for p in ps]:
+            assert R.pair(al, p, t)[:3] == (0, len(t), len(p))
+            assert all(R.rival(al, p, t, w, False)[:3] == (0, len(t), len(p)) for w, _ in _rivals(al))
+        return
+    n_max = R.batch(al, pats, texts)[2]
+    print(base, "local tie share", float((n_max > 1).mean()))
+    assert (n_max > 1).mean() >= 0.8
+    for width, first in _rivals(al):
+        n = _differing(al, pats, texts, width, first)
+        print(base, "local width", width or "row-major", "first" if first else "last", n, "of", len(pats))
+        assert n >= 8, (width, first, n)
+    # one shared text: nested copies, so a pattern's two columns lie 2 j (L + 1) + L + 1 apart and
+    # all but the innermost are split by every width; every pair ties, and the row-major order
+    # and the first maximum differ on at least 8 pairs over the texts
+    assert all(R.pair(al, p, ts[0])[3] == 2 for ps, ts in shared for p in ps)
+    for width, first in _rivals(al):
+        n = sum(_differing(al, ps, ts, width, first) for ps, ts in shared)
+        print(base, "local shared width", width or "row-major", "first" if first else "last", n)
+        if first or width == R.ROW_MAJOR:
+            assert n >= 8, (width, first, n)
 
 
 def test_header_reaches_the_sinks_entry_point():
