@@ -79,6 +79,7 @@ CASES = [
     (["-y", "local", "-a", "2", "-b", "3", "-q", "5", "-r", "2"], G.LOCAL, G.WITHOUT_START, G.TARGET, G.TARGET,
      False, 3000, 1, False),
     (["-y", "local", "-s"], G.LOCAL, G.WITH_START, G.TARGET, G.TARGET, False, 3000, 1, True),
+    (["-y", "banded", "-k", "16"], G.BANDED, G.WITHOUT_START, G.TARGET, G.TARGET, False, 3000, 1, False),
 ]
 
 
@@ -110,6 +111,8 @@ def test_driver_output_contract(tmp_path, case):
 
     batch = G.Batch.from_pairs(q, t)
     kw = dict(algo=algo, start_pos=start_pos, head=head, tail=tail, second_best=int(second), **score)
+    if "-k" in opts:
+        kw["k_band"] = int(opts[opts.index("-k") + 1])
     o = O.align(batch, O.make_params(**kw), q_ops=qm.astype(np.uint8) if rc else None,
                 t_ops=tm.astype(np.uint8) if rc else None)
     want = _expected_lines(qn, tn, batch, o, algo, start_pos, head, second)
